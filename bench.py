@@ -6,7 +6,13 @@ every group, one minibatch draw (train.py:256) and one full train() call (train.
 gather, policy forward (train-mode BN), double-DQN next-state forwards (policy train-mode no-grad + target eval), TD target
 + Huber, backward, [gradient all-reduce], global-norm clip, momentum SGD and the two scalar read-backs the reference does
 (.item()).  That is M2 of SURVEY 8d (65.0 GFLOP/transition); nothing is skipped.  M1 -- the literal "fwd+bwd" of
-BASELINE.json's metric text: policy forward + gather + Huber + backward only -- is timed beside it (`value_fwd_bwd_only`).
+BASELINE.json's metric text: policy forward + gather + Huber + backward only -- is timed beside it by --full (`value_fwd_bwd_only`).
+
+A plain run sets up, warms up, times --steps steps of the headline workload and prints the line: nothing else.  --full adds
+everything else the line can carry: the sustained leg, M1, the per-kernel roofline pass, the second and third legs (other
+precisions / configs), the exposed-communication pass of multi-rank runs and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step left a caller of train() holding (dump_outputs below).  The headline's plans are deterministic (fixed
+summation order), so the same arguments give the same outputs run after run.
 
 Workloads = BASELINE.json's configs (`--workload`, default `auto` = by GPU count):
   configs1   lifting_1-small_empty:           Cin 4 -> Cout 2,                 global minibatch   32, fp32   (auto: N=1, N=2 sharded)
@@ -22,7 +28,7 @@ N GPUs: one process per GPU.  Started under torch.distributed.run (the driver's 
 environment; started bare (`python bench.py --gpus N`) the script launches its own N ranks through torch.distributed.run
 on 127.0.0.1 and exits with their status.
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (driver contract); with --full it carries the `roofline` and `cpu_baseline` objects.
 """
 import argparse
 import ctypes
@@ -72,6 +78,11 @@ def parse():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--workload', default='auto', choices=['auto'] + sorted(WORKLOADS),
                     help='BASELINE config to run (auto: N=1 configs1, N=2 configs1 sharded, N=4 configs3, N=8 configs4, otherwise weak32)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need: sustained leg, M1, roofline pass, second and third legs, exposed-communication '
+                         'pass, CPU baseline (the --no-* switches and --sustained-seconds below shape a --full run)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one left a caller of train() holding as DIR/<name>.npy (rank 0)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-m1', action='store_true', help='skip the forward+backward-only (M1) leg (profiling runs: every launch then belongs to a full step)')
@@ -79,7 +90,7 @@ def parse():
     ap.add_argument('--precision', default=None, choices=['fp32', 'bf16x3', 'bf16'], help="override the workload's arithmetic (tools only)")
     ap.add_argument('--batch', type=int, default=None, help='override: transitions per GPU (and net) per step (tools only)')
     ap.add_argument('--cin', type=int, default=None, help='override: input channels of a single Cout=2 net (tools only)')
-    ap.add_argument('--plan-option', action='append', default=[], metavar='NAME=INT', help='tools only: a simq_plan_options override for every plan of the run (A/B), e.g. deterministic=1')
+    ap.add_argument('--plan-option', action='append', default=[], metavar='NAME=INT', help='tools only: a simq_plan_options override for every plan of the run (A/B), e.g. deterministic=0 (the headline workload runs deterministic plans by default)')
     ap.add_argument('--no-overlap', action='store_true', help='tools only: the target-net forward on the main stream instead of the side stream (A/B of the two-stream overlap)')
     ap.add_argument('--wgrad-xcd-group', type=int, default=None, choices=[0, 1, 2], help='tools only: simq_plan_options.wgrad_xcd_group of every plan, A/B')
     ap.add_argument('--wgrad-overlap', type=int, default=None, choices=[0, 1, 2, 3, 4], help='tools only: simq_plan_options.wgrad_overlap of every plan, A/B')
@@ -97,7 +108,12 @@ def parse():
     ap.add_argument('--watchdog-seconds', type=int, default=120, help='multi-rank runs: abort with a diagnosis when a phase makes no progress for this long')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='torch.distributed backend for --gpus > 1 (nccl == RCCL; gloo only to debug the rank logic on one GPU)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what the headline figure needs
+        args.no_cpu_baseline = args.no_roofline = args.no_m1 = args.no_extras = True
+        args.sustained_seconds = 0.0
+    return args
 
 
 def self_launch(args):
@@ -276,6 +292,40 @@ def resolve_workload(args, world):
     return w
 
 
+DUMP_BUDGET_BYTES = 60 << 20             # --dump-outputs: at most this much in all (the small arrays ride on the margin to 64 MB)
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(out_dir, groups):
+    """--dump-outputs: per robot group, what the last timed step left a caller of train() holding -- the loss and TD error it
+    returned (float64), the policy net's state_dict in the reference layout (every floating-point entry in key order, flattened
+    and concatenated: weights, biases, BN affine parameters and running statistics) and the SGD momentum in the same layout
+    (float32).  An array larger than its share of DUMP_BUDGET_BYTES is written as a fixed seeded sample of its elements (the same
+    positions in every run).  Multi-group workloads prefix the names with group<i>_."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // (2 * len(groups))
+
+    def sample(a):
+        if a.size <= cap:
+            return a
+        idx = np.random.RandomState(DUMP_SAMPLE_SEED).choice(a.size, cap, replace=False)
+        idx.sort()
+        return a[idx]
+
+    for gi, g in enumerate(groups):
+        pre = '' if len(groups) == 1 else 'group%d_' % gi
+        arrays = {'loss': np.array([g['info']['loss']], dtype=np.float64),
+                  'td_error': np.array([g['info']['td_error']], dtype=np.float64)}
+        sd = g['policy'].state_dict()
+        arrays['policy_state'] = torch.cat([v.detach().reshape(-1).float().cpu() for v in sd.values() if v.is_floating_point()]).numpy()
+        views = g['policy'].reference_views(g['opt'].momentum)
+        arrays['momentum'] = torch.cat([v.detach().reshape(-1).float().cpu() for v in views]).numpy()
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, pre + name + '.npy'), sample(a))
+
+
 def main():
     args = parse()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -315,6 +365,12 @@ def main():
     for name in ('plane_xcd', 'fwd_overlap', 'wgrad_overlap', 'wgrad_xcd_group'):
         if getattr(args, name) is not None:
             plan_opts[name] = getattr(args, name)
+    # the headline workload -- the timed path whose outputs --dump-outputs writes -- runs deterministic plans (simq_plan_options.deterministic:
+    # every fp32 sum of the step in a fixed order), so that the same arguments give the same outputs run after run: with the fp32 atomics of
+    # the library's default plans, last-bit differences of the weight gradients grow from step to step (the double-DQN argmax turns them
+    # into different targets) and two runs end far apart.  --plan-option deterministic=0 times the atomic form; the other legs of --full
+    # keep the library's default plans.
+    headline_opts = {} if 'deterministic' in plan_opts else {'deterministic': 1}
     # ... and the host side has none either (round 6): how a learner issues its step is a StepOptions value handed to every train_step call,
     # where a ring runs its copies and gathers is an option of the ring
     step_opts = StepOptions(overlap_target_forward=not args.no_overlap,
@@ -384,9 +440,9 @@ def main():
         torch.cuda.synchronize(dev)
         dog.disarm()
 
-    def run_workload(nets, B, precision, steps, warmup, replay_items, leg_opts=None):
+    def run_workload(nets, B, precision, steps, warmup, replay_items, leg_opts=None, dump_dir=None):
         """nets: [(Cin, Cout)] -- one policy/target pair, optimiser state and replay ring per robot group (train.py:180-195);
-        B: this rank's transitions per net and step."""
+        B: this rank's transitions per net and step; dump_dir: --dump-outputs of the headline workload (rank 0 writes)."""
         gB = B * world
         if replay_items < gB:
             sys.exit('bench.py: the replay ring (%d transitions) is smaller than the global minibatch (%d); raise --replay' % (replay_items, gB))
@@ -446,11 +502,13 @@ def main():
                         exposed_log.append(comm.last_wait_ms())
                     g['drawn'] = draw(g)
                 if defer:
-                    pending.append(info)
-                elif not np.isfinite(info['loss']):
-                    sys.exit('bench: non-finite loss %r' % (info,))
-            for pnd in pending:
-                info = pnd.result()
+                    pending.append((g, info))
+                else:
+                    g['info'] = info
+                    if not np.isfinite(info['loss']):
+                        sys.exit('bench: non-finite loss %r' % (info,))
+            for g, pnd in pending:
+                info = g['info'] = pnd.result()
                 if not np.isfinite(info['loss']):
                     sys.exit('bench: non-finite loss %r' % (info,))
             return info
@@ -468,6 +526,8 @@ def main():
         if pg is not None:
             dt = sdist.max_over_ranks(dt, dev, pg)
         value = gB * len(groups) * steps / dt
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, groups)
 
         # sustained leg (extra key, never `value`): the driver's 20 steps are ~0.2 s -- on a power-managed part that is a cold-clock
         # number.  The same step for >= --sustained-seconds more, in windows of ~0.5 s (a device synchronisation between windows only).
@@ -499,7 +559,7 @@ def main():
         # prices the exposed part at ~0.12 ms).  Timing events around the wait inside libsimq (simq_comm_time_waits); each query synchronises,
         # hence its own pass.
         exposed = None
-        if comm is not None:
+        if comm is not None and args.full:
             comm.time_waits(True)
             for i in range(8):
                 dog.arm('%s exposed-communication pass, step %d' % (precision, i + 1))
@@ -648,7 +708,8 @@ def main():
         torch.cuda.empty_cache()
 
     wl = resolve_workload(args, world)
-    w = run_workload(wl['nets'], wl['per_gpu'], wl['precision'], args.steps, args.warmup, args.replay)
+    w = run_workload(wl['nets'], wl['per_gpu'], wl['precision'], args.steps, args.warmup, args.replay, leg_opts=headline_opts,
+                     dump_dir=args.dump_outputs)
     value, dt, info, gB = w['value'], w['dt'], w['info'], w['gB']
     roof = None
     if not args.no_roofline:
@@ -726,6 +787,7 @@ def main():
                                    % (wl['config'], ' + '.join('Cin=%d->Cout=%d' % n for n in wl['nets']), gB, ' per net' if n_nets > 1 else '',
                                       wl['per_gpu'], ' and net' if n_nets > 1 else '', args.replay),
                        'workload_key': wl['name'], 'nets': n_nets, 'global_batch': gB, 'per_gpu_batch': wl['per_gpu'],
+                       'deterministic_plans': bool(dict(plan_opts, **headline_opts).get('deterministic', 0)),
                        'transitions_per_step': gB * n_nets, 'parallelism': 'dp%d' % world,
                        'concurrent_groups': (args.group_issue if (n_nets > 1 and args.group_streams and world == 1) else None),
                        'gradient_transport': transport, 'simq_comm_world_size': comm_world, 'backend': args.backend if world > 1 else None,

@@ -464,7 +464,7 @@ def test_bench_self_launches_two_ranks_from_a_bare_process():
     """`python bench.py --gpus 2` with no launcher around it starts its own two ranks (torch.distributed.run on 127.0.0.1; here they
     share the one GPU over gloo), rank 0 prints the line: BASELINE configs[1] sharded over the ranks as the headline, the
     weak-scaling leg beside it, a per-rank roofline."""
-    line = _bench_line(['--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--replay', '256'])
+    line = _bench_line(['--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--replay', '256'])
     assert line['n_gpus'] == 2 and line['steps'] == 2 and line['unit'] == 'transitions/s' and line['value'] > 0
     cfg = line['config']
     assert cfg['workload_key'] == 'configs1' and cfg['global_batch'] == 32 and cfg['per_gpu_batch'] == 16 and cfg['parallelism'] == 'dp2'
@@ -486,7 +486,37 @@ def test_bench_maps_gpu_counts_to_the_baseline_configs():
     cfg = line['config']
     assert cfg['workload_key'] == 'configs3' and cfg['nets'] == 2 and cfg['transitions_per_step'] == 32 and line['dtype'] == 'f32'
     assert 'Cin=5->Cout=2 + Cin=5->Cout=1' in cfg['workload'] and np.isfinite(cfg['last_loss'])
-    line = _bench_line(['--workload', 'configs4', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-m1', '--batch', '128',
+    line = _bench_line(['--workload', 'configs4', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-m1', '--batch', '128',
                         '--replay', '256'])
     assert line['config']['workload_key'] == 'configs4' and line['dtype'].startswith('bf16') and line['roofline']['peak'] == 2500.0
     assert line['roofline']['traffic_source'] is None or line['roofline']['traffic_source'].startswith('profiles/')
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line and nothing beside it; --dump-outputs writes what the last timed step left a
+    caller of train() holding, and two runs with the same (default) arguments write the same arrays bit for bit: the headline workload
+    runs deterministic plans, and the other legs' plans are not part of a plain run."""
+    argv = ['--steps', '20', '--warmup', '3']
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ('run%d' % run)
+        line = _bench_line(argv + ['--dump-outputs', str(d)])
+        assert line['steps'] == 20 and line['unit'] == 'transitions/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+        assert line['config']['workload_key'] == 'configs1' and line['value'] > 0
+        assert abs(line['value'] - 32 * 20 / (line['ms_per_step'] * 20e-3)) <= 1e-3 * line['value']
+        assert line['config']['deterministic_plans'] is True
+        for key in ('roofline', 'cpu_baseline', 'sustained', 'value_fwd_bwd_only'):
+            assert line[key] is None, key
+        assert 'bf16_configs2' not in line and 'fp32_mfma_configs1' not in line
+        files = sorted(os.listdir(str(d)))
+        assert files == ['loss.npy', 'momentum.npy', 'policy_state.npy', 'td_error.npy'], files
+        arrays = {f[:-4]: np.load(str(d / f)) for f in files}
+        assert sum(os.path.getsize(str(d / f)) for f in files) <= 64 << 20
+        assert arrays['loss'].dtype == np.float64 and arrays['loss'][0] == line['config']['last_loss']
+        assert arrays['td_error'][0] == line['config']['last_td_error']
+        for k in ('policy_state', 'momentum'):
+            assert arrays[k].dtype == np.float32 and arrays[k].ndim == 1 and arrays[k].size > 10 ** 6 and np.isfinite(arrays[k]).all(), k
+        assert np.abs(arrays['momentum']).max() > 0
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

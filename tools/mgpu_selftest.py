@@ -165,7 +165,7 @@ def main():
     if status == 'PASS' and any('skipped' in ln and 'passed' not in ln for ln in tail):
         status = 'FAIL (skipped)'
     row('4 two-GPU data-parallel tests (fused step over simq_comm, SyncBN)', status, secs, ' | '.join(tail))
-    status, secs, out = run([sys.executable, 'bench.py', '--gpus', str(n), '--steps', '5', '--warmup', '2', '--sustained-seconds', '0', '--no-cpu-baseline'], args.timeout)
+    status, secs, out = run([sys.executable, 'bench.py', '--gpus', str(n), '--steps', '5', '--warmup', '2', '--full', '--sustained-seconds', '0', '--no-cpu-baseline'], args.timeout)
     detail = out[-600:].replace('\n', ' | ')
     for line in reversed(out.splitlines()):
         if line.startswith('{'):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The measurements behind profiles/rNN_* (copy gpurun_out/final/* to profiles/ with the round's prefix afterwards):
-#   1. python bench.py                      -> bench.json   (the judged line: fp32 configs[1] headline + bf16 configs[2] leg, roofline, cpu_baseline)
+#   1. python bench.py --full               -> bench.json   (the judged line: fp32 configs[1] headline + bf16 configs[2] leg, roofline, cpu_baseline)
 #   per workload W in {b32 = fp32 configs[1], bf16_b128 = bf16 configs[2]}:
 #   2. rocprofv3 --kernel-trace             -> bench_W_kernel_trace.txt          (same bench.py, 7 full steps, nothing else)
 #   3. rocprofv3 --pmc SQ_* (own pass)      -> bench_W_pmc_sq.txt                (matrix-pipe busy cycles)
@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/final
 rm -rf $O; mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 prof() {   # name, extra bench args...
   local name=$1; shift
   local B="python $R/bench.py --no-cpu-baseline --no-extras --no-m1 --no-roofline --sustained-seconds 0 --steps 5 --warmup 2 $*"

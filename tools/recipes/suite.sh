@@ -1,5 +1,5 @@
 #!/bin/bash
-# the driver's round-end sequence on one box: GPU suite, smoke(), default bench.py (both legs, roofline, cpu_baseline)
+# the driver's round-end sequence on one box: GPU suite, smoke(), plain bench.py (the headline alone; --full adds the legs, roofline, cpu_baseline)
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 mkdir -p gpurun_out
 python -m pytest tests -q -m gpu --durations=60 "$@" > gpurun_out/t_all.log 2>&1; echo "suite rc=$?"
