@@ -532,6 +532,30 @@ int simq_conv2d_wgrad_bf16_slab(const float* d_x, const float* d_dy, float* d_dw
 int simq_upsample2x_fwd(const float* d_in, float* d_out, int batch, int h, int w, int c, void* stream);
 int simq_upsample2x_bwd(const float* d_dout, float* d_din, int batch, int h, int w, int c, void* stream);
 
+/* ---- shortest-path distance images (shortest_paths.pyx:26-114 GridGraph._spfa, and the Mapper maps of envs.py:2287-2300,
+ * 2513-2516) --------------------------------------------------------------------------------------------------------------------
+ * One problem = one 8-connected grid [rows][cols] of uint8 (free where != 0) and one source pixel.  An edge joins two free cells
+ * inside the grid; straight edges weigh 1, diagonal ones float32(sqrt 2).  The source gets 0 even when blocked (then nothing else is
+ * reachable); unreachable cells get -1.  Every update is fl32(d[u] + w) accepted when strictly smaller, iterated to the fixed point,
+ * so the distances equal the reference SPFA's bit for bit (SPFA's parents, which depend on its queue order, are not produced).
+ * Optional epilogue, in the reference's order: img = d / pixels_per_meter (fp32 division; 1 = none); unreachable_to_max != 0:
+ * img[img < 0] = img.max(); img *= scale (1 = none).
+ * `problems`: host array of n descriptors, validated here (rows, cols >= 1, rows * cols < 2^22, source inside the grid, the grid
+ * inside the grids_bytes of d_grids, the image inside the out_floats of d_out, no two images overlapping; several problems may
+ * share one grid) and copied to the caller's device buffer d_problems (n descriptors) on `stream`.  d_status[n] (int32): 0 =
+ * converged, 1 = the cap of rows * cols + 1 passes was hit (the image is then not the fixed point; cannot happen by the bound
+ * above), 2 = bad descriptor (the kernel checks again and writes nothing else). */
+typedef struct simq_grid_problem {
+    int64_t grid_offset;        /* byte offset of the problem's [rows][cols] uint8 grid in d_grids */
+    int64_t out_offset;         /* float offset of its [rows][cols] fp32 image in d_out */
+    int32_t rows, cols;
+    int32_t src_i, src_j;
+} simq_grid_problem;
+#define SIMQ_GRID_MAX_CELLS (1 << 22)
+int simq_grid_distance_images(const uint8_t* d_grids, int64_t grids_bytes, const simq_grid_problem* problems, int n,
+                              simq_grid_problem* d_problems, float* d_out, int64_t out_floats, float pixels_per_meter,
+                              int unreachable_to_max, float scale, int32_t* d_status, void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of the GEMM-class launches ----------------
  * Between start and stop every implicit-GEMM launch (forward + dgrad; kind 0: the fp32 96x64 tile that dominates the
  * headline workload, kind 2: every other tile / precision) and every wgrad launch (kind 1) is

@@ -32,6 +32,8 @@ _LAZY = {
     'save_checkpoint': ('.checkpoint', 'save_checkpoint'),
     'load_checkpoint': ('.checkpoint', 'load_checkpoint'),
     'resume': ('.checkpoint', 'resume'),
+    'GridGraph': ('.grid_paths', 'GridGraph'),
+    'grid_distance_images': ('.grid_paths', 'grid_distance_images'),
 }
 
 

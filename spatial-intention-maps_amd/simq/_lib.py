@@ -160,6 +160,8 @@ _SIGS = {
     'simq_comm_time_waits': (c_int, [c_void_p, c_int]),
     'simq_comm_last_wait_ms': (c_int, [c_void_p, POINTER(c_float)]),
     'simq_comm_destroy': (c_int, [c_void_p]),
+    'simq_grid_distance_images': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_float, c_int, c_float,
+                                          c_void_p, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)
