@@ -556,6 +556,72 @@ int simq_grid_distance_images(const uint8_t* d_grids, int64_t grids_bytes, const
                               simq_grid_problem* d_problems, float* d_out, int64_t out_floats, float pixels_per_meter,
                               int unreachable_to_max, float scale, int32_t* d_status, void* stream);
 
+/* ---- local state images (Mapper.get_state's crop / rotation: envs.py:2199-2215 _get_local_map / _get_local_distance_map,
+ * 2243-2275 _create_global_overhead_map / _create_global_robot_map, 2368-2375 the nonspatial channels) -----------------------------
+ * One problem = one robot's state: d_out[p][96][96][C] fp32 (NHWC, what simq_forward and the replay ring take), every channel of
+ * every problem in one launch.  A channel is (kind, map, value):
+ *   MAP       local pixel = the global map `map` sampled through the rotation below                       (_get_local_map)
+ *   DISTANCE  as MAP, minus the minimum of the 96 x 96 local image (one fp32 subtract)                    (_get_local_distance_map)
+ *   ROBOTS    max(0, max over the problem's robot stamps of map_value * mask pixel)                       (_create_global_robot_map(seg=False))
+ *   OVERHEAD  seg = the ROBOTS rule with seg_value and seg_mask; seg > 0 ? seg : pixel of base map `map` (_create_global_overhead_map)
+ *   CONSTANT  `value`                                                                                     (envs.py:2375)
+ * Sampling is scipy.ndimage.rotate(crop, angle, order=0) with its defaults (reshape, constant 0 outside) followed by the centre crop.
+ * The caller computes, in float64 as scipy does, for an n x n image rotated by `angle` degrees: c, s = cosdg(angle), sindg(angle);
+ * r = [c, s, -s, c]; shape = int(ptp(R @ corners) + 0.5) per axis; offset = (n - 1) / 2 - R @ ((shape - 1) / 2).  A problem's
+ * rotation has n = 136 (the crop around the robot's pixel) and angle = 90 - degrees(heading); a robot stamp's has n = 96 (its mask)
+ * and angle = degrees(heading) - 90.  Per local pixel (i, j) the kernel forms, in float64 and without contraction,
+ *   (oi, oj) = (i + shape[0] / 2 - 48, j + shape[1] / 2 - 48);  cc_h = offset[h] + (oi * r[2h] + oj * r[2h + 1]);
+ * a pixel with cc_h < 0 or cc_h > n - 1 is 0, otherwise it is the global pixel (pixel_i - 68 + floor(cc_0 + 0.5), pixel_j - 68 +
+ * floor(cc_1 + 0.5)).  A robot stamp covers the global pixels [pixel - shape / 2, pixel - shape / 2 + shape) and is sampled there by
+ * the same rule.  Results equal the reference's bit for bit.
+ * Maps are fp32 [rows][cols] device arrays read in place (d_data: any device address, e.g. an image simq_grid_distance_images
+ * wrote); d_masks is a bank [n_masks][96][96] fp32 (Mapper.robot_masks).  Everything is validated on the host before anything is
+ * copied or launched: the 136 x 136 crop inside its map (68 <= pixel <= rows - 68), every stamp of a problem inside the map, map /
+ * mask / robot indices in range, a channel's map of the problem's shape, rotated shapes in [n, ceil(n * sqrt 2)], finite doubles,
+ * d_out large enough and disjoint from every map and the mask bank.  The descriptors are then copied to d_desc (at least
+ * simq_local_state_desc_bytes(...) bytes of device scratch, 8-byte aligned) on `stream`. */
+#define SIMQ_LOCAL_MAP 0
+#define SIMQ_LOCAL_DISTANCE 1
+#define SIMQ_LOCAL_ROBOTS 2
+#define SIMQ_LOCAL_OVERHEAD 3
+#define SIMQ_LOCAL_CONSTANT 4
+#define SIMQ_LOCAL_CROP 136         /* round_up_to_even(sqrt(2) * 96), envs.py:2201 */
+#define SIMQ_LOCAL_MAX_CHANNELS 64
+typedef struct simq_local_rotation {
+    double r[4];                /* [[c, s], [-s, c]] row-major */
+    double offset[2];
+    int32_t shape[2];           /* of the rotated image */
+} simq_local_rotation;
+typedef struct simq_local_map {
+    const float* d_data;        /* [rows][cols] fp32 on the device */
+    int32_t rows, cols;
+} simq_local_map;
+typedef struct simq_local_robot {
+    simq_local_rotation rot;    /* of the 96 x 96 mask, angle = degrees(heading) - 90 */
+    int32_t pixel_i, pixel_j;   /* position_to_pixel_indices of the robot (envs.py:2391-2396) */
+    int32_t mask;               /* ROBOTS: index into d_masks (a lifting LiftingRobot: the mask with the cube, envs.py:2258-2260) */
+    float seg_value;            /* OVERHEAD: camera.get_seg_value('robot_group_k') as fp32 */
+    float map_value;            /* ROBOTS: 1 (or 0.5: a LiftingRobot that is not lifting) */
+    int32_t seg_mask;           /* OVERHEAD: index into d_masks (always the robot class's own mask, envs.py:2254-2256) */
+} simq_local_robot;
+typedef struct simq_local_problem {
+    simq_local_rotation rot;    /* of the 136 x 136 crop, angle = 90 - degrees(heading) */
+    int32_t pixel_i, pixel_j;   /* the robot's pixel in its global maps */
+    int32_t rows, cols;         /* shape of the environment's global maps */
+    int32_t robot_begin, robot_count;   /* the environment's robots: robots[robot_begin .. robot_begin + robot_count) */
+} simq_local_problem;
+typedef struct simq_local_channel {
+    int32_t kind;               /* SIMQ_LOCAL_* */
+    int32_t map;                /* MAP / DISTANCE / OVERHEAD: index into maps */
+    float value;                /* CONSTANT */
+    int32_t reserved_;
+} simq_local_channel;
+int64_t simq_local_state_desc_bytes(int n_maps, int n_robots, int n, int n_channels);
+/* channels: [n][n_channels], problem-major.  robots / d_masks may be NULL when n_robots == 0. */
+int simq_local_state_images(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks, const simq_local_robot* robots,
+                            int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels,
+                            void* d_desc, int64_t desc_bytes, float* d_out, int64_t out_floats, void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of the GEMM-class launches ----------------
  * Between start and stop every implicit-GEMM launch (forward + dgrad; kind 0: the fp32 96x64 tile that dominates the
  * headline workload, kind 2: every other tile / precision) and every wgrad launch (kind 1) is
