@@ -622,6 +622,42 @@ int simq_local_state_images(const simq_local_map* maps, int n_maps, const float*
                             int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels,
                             void* d_desc, int64_t desc_bytes, float* d_out, int64_t out_floats, void* stream);
 
+/* ---- global intention / history maps (Mapper._create_global_intention_or_history_map, envs.py:2301-2346, and the per-robot spatial
+ * maps of Mapper._get_intention_channels, envs.py:2360-2366) ----------------------------------------------------------------------
+ * One problem = one global map d_out[p][rows][cols] fp32, every map of a call in one launch; the kernel writes every pixel, so the
+ * caller zero-fills nothing.  A map is the maximum, per pixel, over the points of the problem's segments, then dilated with the disk
+ * di^2 + dj^2 <= radius^2 (radius = intention_map_line_thickness - 1; 0: no dilation; pixels outside the map are absent).
+ * A segment is the skimage.draw.line from (r0, c0) to (r1, c1): with n = max(|dr|, |dc|), m = min(|dr|, |dc|), point i = 0 .. n is
+ * i steps along the major axis (the rows when |dr| > |dc|) and (2 * m * i + n) / (2 * n) (integer division) along the minor one;
+ * drop_last leaves point n out (the reference drops it for every segment of a path but the last: a drop_last segment with n = 0
+ * draws nothing).  STORE puts `value` (intention_map_scale as fp32: the circle, binary and line encodings and the spatial channel; a
+ * single pixel is the segment r0 = r1, c0 = c1); RAMP puts (float)clip(y_i, 0, 1) with np.linspace(start, stop, n + 1)'s float64
+ * y_i = i * step + start (product and sum rounded separately), y_n = stop, where the caller computes, in float64 and in the
+ * reference's order, start = 1 - path_length, stop = 1 - (path_length + segment_length), step = (stop - start) / n (0 when n = 0).
+ * The order of segments does not matter.  Results equal the reference's bit for bit.
+ * Everything is validated on the host before anything is copied or launched: end pixels inside the map, modes and flags, finite
+ * doubles, a stored value that is finite, >= 0 and not -0 (the maximum is taken on the fp32 bit patterns), segment ranges inside the
+ * segment array, radius in [0, SIMQ_INTENTION_MAX_RADIUS], rows * cols < 2^28, d_out large enough and disjoint from d_desc.  The
+ * descriptors are then copied to d_desc (at least simq_intention_desc_bytes(...) bytes of device scratch, 8-byte aligned) on `stream`. */
+#define SIMQ_INTENTION_STORE 0
+#define SIMQ_INTENTION_RAMP 1
+#define SIMQ_INTENTION_MAX_RADIUS 8
+typedef struct simq_intention_segment {
+    double start, stop, step;   /* RAMP */
+    int32_t r0, c0, r1, c1;     /* Mapper.position_to_pixel_indices of the two waypoints (envs.py:2391-2396) */
+    int32_t mode;               /* SIMQ_INTENTION_* */
+    int32_t drop_last;          /* 1: point n is not drawn */
+    float value;                /* STORE */
+    int32_t reserved_;
+} simq_intention_segment;
+typedef struct simq_intention_problem {
+    int32_t seg_begin, seg_count;   /* the map's segments: segments[seg_begin .. seg_begin + seg_count); none: a map of zeros */
+} simq_intention_problem;
+int64_t simq_intention_desc_bytes(int n_segments, int n);
+/* segments may be NULL when n_segments == 0. */
+int simq_intention_maps(const simq_intention_segment* segments, int n_segments, const simq_intention_problem* problems, int n, int rows,
+                        int cols, int radius, void* d_desc, int64_t desc_bytes, float* d_out, int64_t out_floats, void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of the GEMM-class launches ----------------
  * Between start and stop every implicit-GEMM launch (forward + dgrad; kind 0: the fp32 96x64 tile that dominates the
  * headline workload, kind 2: every other tile / precision) and every wgrad launch (kind 1) is

@@ -37,6 +37,8 @@ _LAZY = {
     'local_state_images': ('.local_maps', 'local_state_images'),
     'local_map': ('.local_maps', 'local_map'),
     'local_distance_map': ('.local_maps', 'local_distance_map'),
+    'intention_maps': ('.intention_drawing', 'intention_maps'),
+    'intention_map': ('.intention_drawing', 'intention_map'),
 }
 
 

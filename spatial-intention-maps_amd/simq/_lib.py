@@ -165,6 +165,8 @@ _SIGS = {
     'simq_local_state_desc_bytes': (c_int64, [c_int, c_int, c_int, c_int]),
     'simq_local_state_images': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64,
                                         c_void_p, c_int64, c_void_p]),
+    'simq_intention_desc_bytes': (c_int64, [c_int, c_int]),
+    'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -1,0 +1,169 @@
+"""Global intention and history maps on the GPU: the line-drawing stage of the reference's ``Mapper.get_state``.
+
+The reference (envs.py:2301-2346) draws, per robot per step, the paths of the other robots into a zero map of the padded-room shape
+with ``skimage.draw.line`` -- a constant (``binary``, ``line``, ``circle``) or a ramp that falls from 1 along the path (``ramp``,
+``history``) -- and thickens the result with ``dilation(disk(intention_map_line_thickness - 1))``.  ``simq_intention_maps``
+(csrc/intention_maps.hip) draws the maps of many robots in one launch, bit for bit equal to that sequence, into a ``[P, rows, cols]``
+device tensor whose rows ``simq.local_state_images`` reads in place as ``('map', k)`` channels.  The pixels of the waypoints and the
+float64 ramp parameters are computed here in the reference's order of operations and handed to the library; what the library draws
+from them is described in include/simq.h.
+
+The per-robot spatial intention channel (envs.py:2360-2366) is one target pixel at ``intention_map_scale``, always dilated with the
+same disk: ``encoding='circle'`` with the one robot's target as the problem's only entry (an idle robot: no entry, a map of zeros).
+The reference orders those channels from the closest robot to the furthest (envs.py:2350-2354); that ordering stays with the caller,
+who lists the problems in the order the channels are wanted.
+"""
+import ctypes
+import math
+
+import torch
+
+from ._lib import SimqError, lib, ptr, stream_ptr
+from .local_maps import position_to_pixel_indices
+
+ENCODINGS = ('circle', 'ramp', 'binary', 'line', 'history')
+STORE, RAMP = 0, 1
+MAX_RADIUS = 8                   # SIMQ_INTENTION_MAX_RADIUS of include/simq.h
+
+
+class Segment(ctypes.Structure):
+    """simq_intention_segment of include/simq.h."""
+    _fields_ = [('start', ctypes.c_double), ('stop', ctypes.c_double), ('step', ctypes.c_double), ('r0', ctypes.c_int32), ('c0', ctypes.c_int32),
+                ('r1', ctypes.c_int32), ('c1', ctypes.c_int32), ('mode', ctypes.c_int32), ('drop_last', ctypes.c_int32),
+                ('value', ctypes.c_float), ('reserved_', ctypes.c_int32)]
+
+
+class Problem(ctypes.Structure):
+    """simq_intention_problem of include/simq.h."""
+    _fields_ = [('seg_begin', ctypes.c_int32), ('seg_count', ctypes.c_int32)]
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise SimqError('simq intention maps need an MI355X (torch.cuda.is_available() is False); no CPU path')
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _length(a, b):
+    """The distance of envs.py:2556-2557 between two waypoints, on the values as they are given (so that Python floats take the
+    reference's own float operations)."""
+    dx, dy = b[0] - a[0], b[1] - a[1]
+    return math.sqrt(dx**2 + dy**2)
+
+
+def segments(robots, map_shape, encoding, scale=1.0):
+    """The segment descriptors of one map as tuples (r0, c0, r1, c1, mode, drop_last, value, start, stop, step).
+
+    robots: for every drawn robot (every robot of the environment but the mapper's own and the idle ones) what the reference reads
+    from it -- its target position for 'circle', controller.get_intention_path() for 'ramp' / 'binary' / 'line',
+    controller.get_history_path() for 'history' (reversed here, as envs.py:2317 does; 'line' keeps the first and last waypoint here,
+    as envs.py:2315 does)."""
+    if encoding not in ENCODINGS:
+        raise ValueError('encoding %r: choose from %s' % (encoding, list(ENCODINGS)))
+    out = []
+    for waypoints in robots:
+        if encoding == 'circle':
+            try:
+                i, j = position_to_pixel_indices(waypoints[0], waypoints[1], map_shape)
+            except (TypeError, IndexError):
+                raise ValueError("'circle' takes one target position (x, y[, z]) per robot, got %r" % (waypoints,)) from None
+            out.append((i, j, i, j, STORE, 0, scale, 0.0, 0.0, 0.0))
+            continue
+        try:
+            waypoints = [(w[0], w[1]) for w in waypoints]
+        except (TypeError, IndexError):
+            raise ValueError('%r takes a list of waypoint positions (x, y[, z]) per robot, got %r' % (encoding, waypoints)) from None
+        if not waypoints:
+            raise ValueError('a drawn robot has an empty waypoint list (an idle robot is left out of its problem)')
+        if encoding == 'line':
+            waypoints = [waypoints[0], waypoints[-1]]
+        elif encoding == 'history':
+            waypoints = waypoints[::-1]
+        pixels = [position_to_pixel_indices(w[0], w[1], map_shape) for w in waypoints]
+        path_length = 0
+        for k in range(1, len(waypoints)):
+            source, target = waypoints[k - 1], waypoints[k]
+            segment_length = scale * _length(source, target)
+            (r0, c0), (r1, c1) = pixels[k - 1], pixels[k]
+            drop_last = int(k < len(waypoints) - 1)
+            if encoding in ('binary', 'line'):
+                out.append((r0, c0, r1, c1, STORE, drop_last, scale, 0.0, 0.0, 0.0))
+            else:
+                # np.linspace(start, stop, num) of envs.py:2334 with num = len(rr): step = (stop - start) / (num - 1)
+                start, stop = 1 - path_length, 1 - (path_length + segment_length)
+                div = max(abs(r1 - r0), abs(c1 - c0))
+                step = (stop - start) / div if div > 0 else 0.0
+                out.append((r0, c0, r1, c1, RAMP, drop_last, 0.0, float(start), float(stop), float(step)))
+            path_length += segment_length
+    return out
+
+
+def intention_maps(paths, map_shape, encoding, scale=1.0, line_thickness=2, out=None):
+    """The [P, rows, cols] float32 global intention / history maps of P problems in one launch, on the device.
+
+    paths[p]: the drawn robots of problem p as `segments` takes them; an empty list gives a map of zeros (an environment whose other
+    robots are all idle).  map_shape: (rows, cols) of Mapper.create_padded_room_zeros.  encoding: one of 'circle', 'ramp', 'binary',
+    'line', 'history' (env.intention_map_encoding, or 'history' for the history map), or P of them.  scale:
+    env.intention_map_scale.  line_thickness: env.intention_map_line_thickness; the maps are dilated with disk(line_thickness - 1)
+    (1: not at all).  out: a contiguous float32 device tensor [P, rows, cols] to write into, e.g. a slice of a larger map bank; every
+    pixel is written.
+
+    A row of the result is a global map for simq.local_state_images: local_state_images(maps, [('map', k), ...], poses).
+    Raises SimqError, launching nothing, for what the library refuses."""
+    args, out, keep = _prepare(paths, map_shape, encoding, scale, line_thickness, out)
+    lib.call('simq_intention_maps', *args)
+    del keep                                     # (the descriptor scratch: alive until the launch is queued)
+    return out
+
+
+def _prepare(paths, map_shape, encoding, scale, line_thickness, out):
+    """The argument tuple of simq_intention_maps for intention_maps' inputs, the output tensor and the device tensors the call reads
+    (tools/intention_maps_rate.py times the library call alone with it)."""
+    paths = list(paths)
+    P = len(paths)
+    if P < 1:
+        raise ValueError('intention_maps needs at least one problem')
+    try:
+        rows, cols = int(map_shape[0]), int(map_shape[1])
+    except (TypeError, IndexError, ValueError):
+        raise ValueError('map_shape is (rows, cols), got %r' % (map_shape,)) from None
+    if rows < 1 or cols < 1 or len(map_shape) != 2:
+        raise ValueError('map_shape is (rows, cols) with rows, cols >= 1, got %r' % (map_shape,))
+    encodings = [encoding] * P if isinstance(encoding, str) else list(encoding)
+    if len(encodings) != P:
+        raise ValueError('%d encodings for %d problems' % (len(encodings), P))
+    if int(line_thickness) != line_thickness or not 1 <= line_thickness <= MAX_RADIUS + 1:
+        raise ValueError('line_thickness = %r (a whole number in 1 .. %d)' % (line_thickness, MAX_RADIUS + 1))
+    value = float(scale)
+    if not (math.isfinite(value) and value >= 0) or math.copysign(1.0, value) < 0:
+        raise ValueError('scale = %r (finite, >= 0 and not -0)' % (scale,))
+
+    c_segs_list, ranges = [], []
+    for p in range(P):
+        begin = len(c_segs_list)
+        for r0, c0, r1, c1, mode, drop_last, v, start, stop, step in segments(paths[p], (rows, cols), encodings[p], scale):
+            c_segs_list.append(Segment(start, stop, step, r0, c0, r1, c1, mode, drop_last, v, 0))
+        ranges.append((begin, len(c_segs_list) - begin))
+    n_segs = len(c_segs_list)
+    c_segs = (Segment * max(n_segs, 1))(*c_segs_list)
+    c_probs = (Problem * P)(*[Problem(b, c) for b, c in ranges])
+
+    dev = _device()                              # (after the argument checks: those need no device)
+    want = (P, rows, cols)
+    if out is None:
+        out = torch.empty(want, dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or \
+            tuple(out.shape) != want:
+        raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % (want, dev))
+    desc_bytes = lib.c.simq_intention_desc_bytes(n_segs, P)
+    d_desc = torch.empty(max(int(desc_bytes), 8), dtype=torch.uint8, device=dev)
+    args = (c_segs if n_segs else None, n_segs, c_probs, P, rows, cols, int(line_thickness) - 1, ptr(d_desc), ctypes.c_int64(d_desc.numel()),
+            ptr(out), ctypes.c_int64(out.numel()), stream_ptr(dev))
+    return args, out, (d_desc,)
+
+
+def intention_map(robots, map_shape, encoding, scale=1.0, line_thickness=2):
+    """Drop-in for Mapper._create_global_intention_or_history_map(encoding) (envs.py:2301-2346) with the drawn robots' paths passed
+    in: the float32 [rows, cols] numpy map.  With encoding='circle', one target and the environment's line thickness it is the
+    global map of one spatial intention channel (envs.py:2360-2365)."""
+    return intention_maps([robots], map_shape, encoding, scale, line_thickness)[0].cpu().numpy()
