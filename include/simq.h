@@ -658,6 +658,42 @@ int64_t simq_intention_desc_bytes(int n_segments, int n);
 int simq_intention_maps(const simq_intention_segment* segments, int n_segments, const simq_intention_problem* problems, int n, int rows,
                         int cols, int radius, void* d_desc, int64_t desc_bytes, float* d_out, int64_t out_floats, void* stream);
 
+/* ---- occupancy maps: configuration space, thin configuration space and closest free cells (OccupancyMap.update, envs.py:2452-2455,
+ * read through OccupancyMap._closest_valid_cspace_indices, envs.py:2522-2523) ------------------------------------------------------
+ * One problem = one occupancy map [rows][cols] of uint8 (occupied where != 0), one room mask of the same shape (inside the room where
+ * != 0), a dilation radius and a thin radius; every problem of a call in one launch, three outputs per problem, every element written:
+ *   configuration space  d_cspace[out_offset + i * cols + j] (uint8) is 1 where room_mask != 0 and no occupied cell lies at an offset
+ *                        di^2 + dj^2 <= radius^2 inside the map, 0 elsewhere (cells outside the map are absent: the border value 0
+ *                        of scipy.ndimage.binary_dilation with the disk footprint)
+ *   thin space           d_thin[out_offset + i * cols + j] (uint8) is 0 where some cell with room_mask != 0 and occupancy != 0 lies
+ *                        within di^2 + dj^2 <= thin_radius^2, 1 elsewhere
+ *   closest free cells   d_closest[2 * out_offset + h * rows * cols + i * cols + j] (int32, h = 0: row, 1: column; the layout and
+ *                        dtype of scipy.ndimage.distance_transform_edt(1 - configuration_space, return_indices=True)) is the free
+ *                        cell of the configuration space nearest to (i, j) by squared Euclidean distance; a free cell maps to itself
+ * Radius 0 is no dilation.  Ties between nearest free cells follow scipy's two one-dimensional passes: f0[i][j] = the nearest free row
+ * of column j, the smaller row on a tie; the answer at (i, j) is (f0[i][j'], j') for the column j' that minimises
+ * (j' - j)^2 + (f0[i][j'] - i)^2 over the columns that hold a free cell, the smaller j' on a tie -- among the nearest free cells the
+ * smallest column, then the smallest row.  All arithmetic is integer; results equal the reference's element for element.
+ * `problems`: host array of n descriptors, validated here before anything is copied or launched (rows, cols in [1,
+ * SIMQ_OCCUPANCY_MAX_DIM], radii in [0, SIMQ_OCCUPANCY_MAX_RADIUS], both inputs inside the maps_bytes of d_maps, the outputs inside
+ * the cspace_bytes of d_cspace and d_thin each and the closest_ints of d_closest, no two problems' outputs overlapping, the output
+ * buffers and d_status disjoint from each other, from d_maps and from d_problems; several problems may share a room mask) and copied
+ * to the caller's device buffer d_problems (n descriptors) on `stream`.  d_status[n] (int32): 0 = ok, 1 = the configuration space
+ * has no free cell (the closest cells are all -1; both uint8 maps are valid), 2 = bad descriptor (the kernel checks again and writes
+ * nothing else). */
+#define SIMQ_OCCUPANCY_MAX_DIM 256
+#define SIMQ_OCCUPANCY_MAX_RADIUS 16
+typedef struct simq_occupancy_problem {
+    int64_t occupancy_offset;   /* byte offset of the problem's [rows][cols] uint8 occupancy map in d_maps */
+    int64_t mask_offset;        /* byte offset of its [rows][cols] uint8 room mask in d_maps */
+    int64_t out_offset;         /* byte offset of its maps in d_cspace and in d_thin; its closest cells start at int 2 * out_offset */
+    int32_t rows, cols;
+    int32_t radius, thin_radius;
+} simq_occupancy_problem;
+int simq_occupancy_maps(const uint8_t* d_maps, int64_t maps_bytes, const simq_occupancy_problem* problems, int n,
+                        simq_occupancy_problem* d_problems, uint8_t* d_cspace, uint8_t* d_thin, int64_t cspace_bytes, int32_t* d_closest,
+                        int64_t closest_ints, int32_t* d_status, void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of the GEMM-class launches ----------------
  * Between start and stop every implicit-GEMM launch (forward + dgrad; kind 0: the fp32 96x64 tile that dominates the
  * headline workload, kind 2: every other tile / precision) and every wgrad launch (kind 1) is

@@ -39,6 +39,8 @@ _LAZY = {
     'local_distance_map': ('.local_maps', 'local_distance_map'),
     'intention_maps': ('.intention_drawing', 'intention_maps'),
     'intention_map': ('.intention_drawing', 'intention_map'),
+    'occupancy_maps': ('.occupancy', 'occupancy_maps'),
+    'configuration_space': ('.occupancy', 'configuration_space'),
 }
 
 

@@ -167,6 +167,8 @@ _SIGS = {
                                         c_void_p, c_int64, c_void_p]),
     'simq_intention_desc_bytes': (c_int64, [c_int, c_int]),
     'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                    c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)
