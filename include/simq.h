@@ -694,6 +694,58 @@ int simq_occupancy_maps(const uint8_t* d_maps, int64_t maps_bytes, const simq_oc
                         simq_occupancy_problem* d_problems, uint8_t* d_cspace, uint8_t* d_thin, int64_t cspace_bytes, int32_t* d_closest,
                         int64_t closest_ints, int32_t* d_status, void* stream);
 
+/* ---- observation maps: camera frames into the overhead and occupancy maps (Camera.capture_image, envs.py:1926-1954; the scatters of
+ * Mapper.update, envs.py:2053-2061, and OccupancyMap.update, envs.py:2444-2449) ----------------------------------------------------
+ * One problem = one camera frame (depth buffer [height][width] fp32 and body ids [height][width] int32, both in d_frames, a buffer of
+ * 4-byte words) and one pair of persistent maps updated in place: the overhead map [rows][cols] fp32 in d_overhead and the occupancy
+ * map [rows][cols] uint8 in d_occupancy.  Every problem of a call in one launch.  All arithmetic is fp32, every product and sum rounded
+ * on its own (no fused multiply-add), the division correctly rounded; per frame pixel (h, w), frame index k = h * width + w:
+ *   depth  = far_near / (far - far_minus_near * buffer[k])
+ *   p_c    = cam_c + depth * ((principal_c + px[w] * right_c) + py[h] * up_c)                        c = x, y, z
+ *   seg    = 1/8 [id == 0] + 2/8 [min_obstacle <= id <= max_obstacle] + 3/8 [has_receptacle and id == receptacle]
+ *            + 4/8 [min_cube <= id <= max_cube]            (a sum of eighths: exact; an id that matches nothing has seg 0)
+ *   (i, j) = (clip(floor(rows / 2 - p_y * 96), 0, rows - 1), clip(floor(cols / 2 + p_x * 96), 0, cols - 1))
+ *            (Mapper.position_to_pixel_indices, envs.py:2391-2396: a point outside the map lands on its border pixels; the clip is
+ *            taken on the float, so a point beyond the int32 range lands on the border of its side too)
+ * The caller forms the three depth constants (far * near, far, far - near, each rounded to fp32 once), the camera vectors and the
+ * tables px[width], py[height] on the host in the reference's own sequence of float32 operations (envs.py:1931-1943); the library has
+ * no trigonometry and no normalisation.
+ *   overhead map   pixel (i, j) takes the seg of the point with the greatest p_z among those that land on it; among points of equal
+ *                  greatest p_z (-0 equals +0) the one with the largest frame index k -- what the reference's assignment in
+ *                  ascending-z order gives when the sort is stable.  A seg of 0 is written like any other.  A pixel no point lands
+ *                  on keeps its value.
+ *   occupancy map  pixel (i, j) becomes 1 where a point with seg == 2/8 lands, whatever its height, and is otherwise left as it is.
+ * A frame with a point that is not finite (a depth buffer outside what the near and far planes allow) changes neither map of its
+ * problem and gives status 1, the other problems of the launch are not affected; the reference would let such a point win or lose
+ * pixels by the accident of its sort.
+ * `problems`: host array of n descriptors, validated here before anything is copied or launched (height, width >= 1 and height *
+ * width <= SIMQ_OBSERVATION_MAX_POINTS; rows, cols in [1, 2^24), so that rows / 2 and rows - 1 are exact in fp32, and rows * cols <
+ * 2^28; the frame, its ids and both tables inside the frame_words of d_frames; both maps inside overhead_floats / occupancy_bytes; finite camera vectors and constants; has_receptacle 0 or
+ * 1; no two maps of the launch -- overhead or occupancy, of one problem or of two -- sharing a byte, because the order of two updates
+ * of one map matters; every map disjoint from d_frames, d_problems and d_status; alignment) and copied to the caller's device buffer
+ * d_problems (n descriptors) on `stream`.  Several problems may share a frame or the tables.  d_status[n] (int32): 0 = updated, 1 = a
+ * point was not finite (both maps unchanged), 2 = bad descriptor (the kernel checks sizes and offsets again and writes nothing else). */
+#define SIMQ_OBSERVATION_MAX_POINTS (1 << 22)
+typedef struct simq_observation_problem {
+    int64_t depth_offset;       /* word offset of the depth buffer [height][width] fp32 in d_frames */
+    int64_t ids_offset;         /* word offset of the body ids [height][width] int32 in d_frames */
+    int64_t px_offset;          /* word offset of px[width] fp32 in d_frames */
+    int64_t py_offset;          /* word offset of py[height] fp32 in d_frames */
+    int64_t overhead_offset;    /* float offset of the [rows][cols] fp32 overhead map in d_overhead */
+    int64_t occupancy_offset;   /* byte offset of the [rows][cols] uint8 occupancy map in d_occupancy */
+    float cam[3], principal[3], right[3], up[3];
+    float far_near, far, far_minus_near;
+    int32_t min_obstacle, max_obstacle;
+    int32_t receptacle, has_receptacle;    /* has_receptacle 0: no receptacle term (rescue environments) */
+    int32_t min_cube, max_cube;
+    int32_t height, width;      /* of the frame */
+    int32_t rows, cols;         /* of both maps */
+    int32_t reserved_;
+} simq_observation_problem;
+int simq_observation_update(const void* d_frames, int64_t frame_words, const simq_observation_problem* problems, int n,
+                            simq_observation_problem* d_problems, float* d_overhead, int64_t overhead_floats, uint8_t* d_occupancy,
+                            int64_t occupancy_bytes, int32_t* d_status, void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of the GEMM-class launches ----------------
  * Between start and stop every implicit-GEMM launch (forward + dgrad; kind 0: the fp32 96x64 tile that dominates the
  * headline workload, kind 2: every other tile / precision) and every wgrad launch (kind 1) is

@@ -1,0 +1,243 @@
+// libsimq: batched observation maps -- a camera frame into the persistent overhead and occupancy maps
+//   observation_maps_kernel  depth, point cloud and segmentation of Camera.capture_image               envs.py:1926-1954
+//                            the height-ordered scatter of Mapper.update into the overhead map        envs.py:2053-2061
+//                            the obstacle scatter of OccupancyMap.update into the occupancy map       envs.py:2444-2449
+//
+// Exactness.  Everything the reference computes here is float32, one numpy operation per product, sum and quotient.  The projection is
+// compiled with contraction off (the ISA holds v_mul_f32 / v_add_f32 / v_sub_f32 and no fused form) and the division is the compiler's
+// correctly rounded one.  The reference assigns seg values in ascending order of the point's z, so a pixel ends with the seg of its
+// highest point; among equal heights this project fixes the order a stable sort gives: the largest frame index wins.  Both are one
+// maximum over the 64-bit key (order-preserving bits of z) << 32 | frame index, taken in LDS (ds_max_u64): the order in which lanes
+// arrive does not matter.  Finite floats order as their bit patterns with the sign bit flipped (positive) or all bits flipped
+// (negative); -0 is folded into +0 first.  No finite point has key 0, which marks a pixel nothing landed on.
+//
+// Shape.  One workgroup of 1024 lanes per 32 x 256 tile of one problem's maps: 64 KB of keys and 8 KB of occupancy bytes in LDS.  Every
+// workgroup streams all height * width points of its problem, one lane per point (a dozen fp32 operations and two coalesced loads), and
+// keeps those that land in its tile.  Every workgroup of a problem therefore sees a non-finite point itself and none of them writes:
+// no flag crosses workgroups, and there are no global atomics, no workspace and no second launch.  The second pass walks the tile with
+// consecutive lanes on consecutive pixels of a row: a pixel with a key reads its winner's id again and stores the seg, an occupancy byte
+// that was set stores 1 (plain vector stores; every writer of a byte stores the same value); everything else is left untouched.
+#include "common.h"
+#include "../../include/simq.h"
+
+#include <algorithm>
+#include <cmath>
+#include <utility>
+#include <vector>
+
+namespace simq {
+
+namespace {
+
+constexpr int kTileRows = 32;
+constexpr int kTileCols = 256;
+constexpr int kTilePixels = kTileRows * kTileCols;
+constexpr int kThreads = 1024;
+constexpr int kMaxPoints = SIMQ_OBSERVATION_MAX_POINTS;
+constexpr int64_t kMaxCells = 1 << 28;
+constexpr int kMaxSide = 1 << 24;                                                     // rows, cols, rows - 1 and rows / 2 exact in fp32
+
+// Camera.capture_image's seg value of body id `raw`: a sum of eighths, exact in any order
+__device__ __forceinline__ float seg_value(const simq_observation_problem& p, int raw) {
+    float s = raw == 0 ? 0.125f : 0.f;
+    s += (raw >= p.min_obstacle && raw <= p.max_obstacle) ? 0.25f : 0.f;
+    s += (p.has_receptacle && raw == p.receptacle) ? 0.375f : 0.f;
+    s += (raw >= p.min_cube && raw <= p.max_cube) ? 0.5f : 0.f;
+    return s;
+}
+
+// the frame pixel (h, w) with depth-buffer value `buffer` as a world point; hipcc contracts a * b + c into v_fma_f32 by default, numpy
+// rounds the product and the sum separately
+__device__ __forceinline__ void project(const simq_observation_problem& p, float buffer, float px, float py, float& x, float& y, float& z) {
+#pragma clang fp contract(off)
+    const float scaled = p.far_minus_near * buffer;
+    const float denom = p.far - scaled;
+    const float depth = p.far_near / denom;
+    const float rx = px * p.right[0], ry = px * p.right[1], rz = px * p.right[2];
+    const float ux = py * p.up[0], uy = py * p.up[1], uz = py * p.up[2];
+    const float dx = (p.principal[0] + rx) + ux, dy = (p.principal[1] + ry) + uy, dz = (p.principal[2] + rz) + uz;
+    const float sx = depth * dx, sy = depth * dy, sz = depth * dz;
+    x = p.cam[0] + sx;
+    y = p.cam[1] + sy;
+    z = p.cam[2] + sz;
+}
+
+// Mapper.position_to_pixel_indices of one coordinate: clip(floor(half + sign * v * 96), 0, size - 1), the product and the sum rounded apart
+__device__ __forceinline__ int pixel_index(float half, float v, bool minus, int size) {
+#pragma clang fp contract(off)
+    const float scaled = v * 96.f;
+    const float t = minus ? half - scaled : half + scaled;
+    float f = floorf(t);
+    f = f > 0.f ? f : 0.f;
+    const float top = (float)(size - 1);
+    f = f < top ? f : top;
+    return (int)f;
+}
+
+__device__ __forceinline__ bool descriptor_ok(const simq_observation_problem& p, int64_t frame_words, int64_t overhead_floats,
+                                              int64_t occupancy_bytes) {
+    if (p.height < 1 || p.width < 1 || (int64_t)p.height * p.width > kMaxPoints) return false;
+    if (p.rows < 1 || p.cols < 1 || p.rows >= kMaxSide || p.cols >= kMaxSide || (int64_t)p.rows * p.cols >= kMaxCells) return false;
+    const int64_t points = (int64_t)p.height * p.width, cells = (int64_t)p.rows * p.cols;
+    return p.depth_offset >= 0 && p.depth_offset <= frame_words - points && p.ids_offset >= 0 && p.ids_offset <= frame_words - points &&
+           p.px_offset >= 0 && p.px_offset <= frame_words - p.width && p.py_offset >= 0 && p.py_offset <= frame_words - p.height &&
+           p.overhead_offset >= 0 && p.overhead_offset <= overhead_floats - cells && p.occupancy_offset >= 0 &&
+           p.occupancy_offset <= occupancy_bytes - cells;
+}
+
+__global__ void __launch_bounds__(kThreads) observation_maps_kernel(const uint32_t* __restrict__ frames, int64_t frame_words,
+                                                                    const simq_observation_problem* __restrict__ probs, int max_tiles,
+                                                                    float* overhead, int64_t overhead_floats, uint8_t* occupancy,
+                                                                    int64_t occupancy_bytes, int32_t* __restrict__ status) {
+    __shared__ unsigned long long keys[kTilePixels];
+    __shared__ uint8_t occupied[kTilePixels];
+    __shared__ int not_finite;
+    const int tid = threadIdx.x;
+    const int p = blockIdx.x / max_tiles, t = blockIdx.x - p * max_tiles;
+    const simq_observation_problem pr = probs[p];                                     // (uniform over the workgroup)
+    if (tid == 0) not_finite = 0;
+    for (int k = tid; k < kTilePixels; k += kThreads) {
+        keys[k] = 0ull;
+        occupied[k] = 0;
+    }
+    __syncthreads();
+    if (!descriptor_ok(pr, frame_words, overhead_floats, occupancy_bytes)) {          // (the host validated already: nothing is read or written)
+        if (t == 0 && tid == 0) status[p] = 2;
+        return;
+    }
+    const int tiles_j = (pr.cols + kTileCols - 1) / kTileCols, tiles_i = (pr.rows + kTileRows - 1) / kTileRows;
+    if (t >= tiles_i * tiles_j) return;                                               // (the grid is sized by the launch's largest map)
+    const int ti = t / tiles_j, tj = t - ti * tiles_j;
+    const int i0 = ti * kTileRows, j0 = tj * kTileCols;
+
+    const float* depth = reinterpret_cast<const float*>(frames + pr.depth_offset);
+    const int32_t* ids = reinterpret_cast<const int32_t*>(frames + pr.ids_offset);
+    const float* px = reinterpret_cast<const float*>(frames + pr.px_offset);
+    const float* py = reinterpret_cast<const float*>(frames + pr.py_offset);
+    const int points = pr.height * pr.width;
+    const float half_rows = (float)pr.rows * 0.5f, half_cols = (float)pr.cols * 0.5f;  // (exact: descriptor_ok holds rows, cols < 2^24)
+    bool bad = false;
+    for (int k = tid; k < points; k += kThreads) {
+        const int h = k / pr.width, w = k - h * pr.width;
+        float x, y, z;
+        project(pr, depth[k], px[w], py[h], x, y, z);
+        if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
+            bad = true;
+            continue;
+        }
+        const int li = pixel_index(half_rows, y, true, pr.rows) - i0, lj = pixel_index(half_cols, x, false, pr.cols) - j0;
+        if (li < 0 || li >= kTileRows || lj < 0 || lj >= kTileCols) continue;
+        const int raw = ids[k];
+        uint32_t zb = z == 0.f ? 0u : __float_as_uint(z);                             // -0 and +0 are one height
+        zb = (zb & 0x80000000u) ? ~zb : (zb | 0x80000000u);
+        atomicMax(&keys[li * kTileCols + lj], ((unsigned long long)zb << 32) | (unsigned)k);
+        if (seg_value(pr, raw) == 0.25f) occupied[li * kTileCols + lj] = 1;       // (2/8: the obstacle term and no other)
+    }
+    if (bad) not_finite = 1;
+    __syncthreads();
+    const bool skip = not_finite != 0;
+    if (t == 0 && tid == 0) status[p] = skip ? 1 : 0;
+    if (skip) return;
+
+    float* o_map = overhead + pr.overhead_offset;
+    uint8_t* o_occ = occupancy + pr.occupancy_offset;
+    for (int k = tid; k < kTilePixels; k += kThreads) {
+        const int li = k / kTileCols, lj = k - li * kTileCols;
+        const int gi = i0 + li, gj = j0 + lj;
+        if (gi >= pr.rows || gj >= pr.cols) continue;
+        const unsigned long long key = keys[k];
+        const int64_t cell = (int64_t)gi * pr.cols + gj;
+        if (key != 0ull) o_map[cell] = seg_value(pr, ids[(uint32_t)key]);
+        if (occupied[k]) o_occ[cell] = 1;
+    }
+}
+
+// [a, a + na) and [b, b + nb) (bytes) share a byte
+bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+}  // namespace
+
+}  // namespace simq
+
+using namespace simq;
+
+extern "C" int simq_observation_update(const void* d_frames, int64_t frame_words, const simq_observation_problem* problems, int n,
+                                       simq_observation_problem* d_problems, float* d_overhead, int64_t overhead_floats,
+                                       uint8_t* d_occupancy, int64_t occupancy_bytes, int32_t* d_status, void* stream) {
+    SIMQ_REQUIRE(d_frames && problems && d_problems && d_overhead && d_occupancy && d_status, "observation_update: NULL pointer");
+    SIMQ_REQUIRE(n >= 1 && n <= (1 << 20), "observation_update: n = %d (1 .. 2^20 problems)", n);
+    SIMQ_REQUIRE(frame_words >= 0 && overhead_floats >= 0 && occupancy_bytes >= 0 && frame_words < (1LL << 40) &&
+                     overhead_floats < (1LL << 40) && occupancy_bytes < (1LL << 40),
+                 "observation_update: buffer sizes %lld, %lld, %lld (each in [0, 2^40))", (long long)frame_words, (long long)overhead_floats,
+                 (long long)occupancy_bytes);
+    SIMQ_REQUIRE(((uintptr_t)d_frames & 3) == 0 && ((uintptr_t)d_overhead & 3) == 0 && ((uintptr_t)d_problems & 7) == 0 &&
+                     ((uintptr_t)d_status & 3) == 0,
+                 "observation_update: d_problems must be 8-byte, d_frames, d_overhead and d_status 4-byte aligned");
+    const int64_t prob_bytes = (int64_t)sizeof(simq_observation_problem) * n, status_bytes = 4LL * n;
+    std::vector<std::pair<uintptr_t, uintptr_t>> spans;                               // the bytes this launch may write, [first, second)
+    spans.reserve(2 * (size_t)n);
+    int max_tiles = 1;
+    for (int i = 0; i < n; ++i) {
+        const simq_observation_problem& p = problems[i];
+        SIMQ_REQUIRE(p.height >= 1 && p.width >= 1 && (int64_t)p.height * p.width <= kMaxPoints,
+                     "observation_update: problem %d: a frame of %d x %d (height, width >= 1, at most %d points)", i, p.height, p.width,
+                     kMaxPoints);
+        SIMQ_REQUIRE(p.rows >= 1 && p.cols >= 1 && p.rows < kMaxSide && p.cols < kMaxSide && (int64_t)p.rows * p.cols < kMaxCells,
+                     "observation_update: problem %d: maps of %d x %d (rows, cols in [1, 2^24), rows * cols < 2^28)", i, p.rows, p.cols);
+        const int64_t points = (int64_t)p.height * p.width, cells = (int64_t)p.rows * p.cols;
+        SIMQ_REQUIRE(p.depth_offset >= 0 && p.depth_offset <= frame_words - points,
+                     "observation_update: problem %d: depth words [%lld, %lld) outside the %lld of d_frames", i, (long long)p.depth_offset,
+                     (long long)(p.depth_offset + points), (long long)frame_words);
+        SIMQ_REQUIRE(p.ids_offset >= 0 && p.ids_offset <= frame_words - points,
+                     "observation_update: problem %d: id words [%lld, %lld) outside the %lld of d_frames", i, (long long)p.ids_offset,
+                     (long long)(p.ids_offset + points), (long long)frame_words);
+        SIMQ_REQUIRE(p.px_offset >= 0 && p.px_offset <= frame_words - p.width && p.py_offset >= 0 && p.py_offset <= frame_words - p.height,
+                     "observation_update: problem %d: px words [%lld, +%d) or py words [%lld, +%d) outside the %lld of d_frames", i,
+                     (long long)p.px_offset, p.width, (long long)p.py_offset, p.height, (long long)frame_words);
+        SIMQ_REQUIRE(p.overhead_offset >= 0 && p.overhead_offset <= overhead_floats - cells,
+                     "observation_update: problem %d: overhead floats [%lld, %lld) outside the %lld of d_overhead", i,
+                     (long long)p.overhead_offset, (long long)(p.overhead_offset + cells), (long long)overhead_floats);
+        SIMQ_REQUIRE(p.occupancy_offset >= 0 && p.occupancy_offset <= occupancy_bytes - cells,
+                     "observation_update: problem %d: occupancy bytes [%lld, %lld) outside the %lld of d_occupancy", i,
+                     (long long)p.occupancy_offset, (long long)(p.occupancy_offset + cells), (long long)occupancy_bytes);
+        bool finite = std::isfinite(p.far_near) && std::isfinite(p.far) && std::isfinite(p.far_minus_near);
+        for (int c = 0; c < 3; ++c)
+            finite = finite && std::isfinite(p.cam[c]) && std::isfinite(p.principal[c]) && std::isfinite(p.right[c]) && std::isfinite(p.up[c]);
+        SIMQ_REQUIRE(finite, "observation_update: problem %d: a camera vector or depth constant is not finite", i);
+        SIMQ_REQUIRE(p.has_receptacle == 0 || p.has_receptacle == 1, "observation_update: problem %d: has_receptacle = %d (0 or 1)", i,
+                     p.has_receptacle);
+        const uintptr_t a = (uintptr_t)(d_overhead + p.overhead_offset), b = (uintptr_t)(d_occupancy + p.occupancy_offset);
+        spans.emplace_back(a, a + 4 * (uintptr_t)cells);
+        spans.emplace_back(b, b + (uintptr_t)cells);
+        const int64_t tiles = (int64_t)((p.rows + kTileRows - 1) / kTileRows) * ((p.cols + kTileCols - 1) / kTileCols);
+        max_tiles = std::max(max_tiles, (int)tiles);
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); ++i)
+        SIMQ_REQUIRE(spans[i].first >= spans[i - 1].second,
+                     "observation_update: two maps of one launch share memory at address %p (every problem needs an overhead map and an "
+                     "occupancy map of its own: the order of two updates of one map matters)", (void*)spans[i].first);
+    const struct { const char* name; const void* p; int64_t bytes; } others[] = {
+        {"d_frames", d_frames, frame_words * 4}, {"d_problems", d_problems, prob_bytes}, {"d_status", d_status, status_bytes}};
+    for (const auto& s : spans)
+        for (const auto& o : others)
+            SIMQ_REQUIRE(!overlaps((const void*)s.first, (int64_t)(s.second - s.first), o.p, o.bytes), "observation_update: a map overlaps %s",
+                         o.name);
+    for (size_t a = 0; a < 3; ++a)
+        for (size_t b = a + 1; b < 3; ++b)
+            SIMQ_REQUIRE(!overlaps(others[a].p, others[a].bytes, others[b].p, others[b].bytes), "observation_update: %s overlaps %s",
+                         others[a].name, others[b].name);
+    const int64_t blocks = (int64_t)n * max_tiles;
+    SIMQ_REQUIRE(blocks <= 0x7fffffffLL, "observation_update: %d problems of up to %d tiles take %lld workgroups (at most 2^31 - 1)", n,
+                 max_tiles, (long long)blocks);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SIMQ_CHECK_HIP(hipMemcpyAsync(d_problems, problems, (size_t)prob_bytes, hipMemcpyHostToDevice, s));
+    observation_maps_kernel<<<(unsigned)blocks, kThreads, 0, s>>>(static_cast<const uint32_t*>(d_frames), frame_words, d_problems, max_tiles,
+                                                                  d_overhead, overhead_floats, d_occupancy, occupancy_bytes, d_status);
+    SIMQ_CHECK_LAUNCH();
+    note_launch("observation_maps");
+    return 0;
+}

@@ -41,6 +41,9 @@ _LAZY = {
     'intention_map': ('.intention_drawing', 'intention_map'),
     'occupancy_maps': ('.occupancy', 'occupancy_maps'),
     'configuration_space': ('.occupancy', 'configuration_space'),
+    'camera_geometry': ('.observation', 'camera_geometry'),
+    'observation_update': ('.observation', 'observation_update'),
+    'observe': ('.observation', 'observe'),
 }
 
 

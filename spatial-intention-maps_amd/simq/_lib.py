@@ -169,6 +169,7 @@ _SIGS = {
     'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                     c_void_p]),
+    'simq_observation_update': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)

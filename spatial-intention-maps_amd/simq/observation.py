@@ -1,0 +1,254 @@
+"""Observation maps on the GPU: a camera frame into the persistent overhead and occupancy maps.
+
+The reference turns the simulator's depth buffer and body-id segmentation into a point cloud (``Camera.capture_image``,
+envs.py:1926-1954), sorts the points by height and scatters their segmentation values into ``global_overhead_map_without_robots``
+(``Mapper.update``, envs.py:2053-2061) and the obstacle points into ``occupancy_map`` (``OccupancyMap.update``, envs.py:2444-2449), per
+robot per step, on the host.  ``simq_observation_update`` (csrc/observation_maps.hip) does it for many frames in one launch, updating
+both maps in place on the device, bit for bit equal to that sequence; the rules are stated in include/simq.h.  The updated occupancy
+map is what ``simq.occupancy_maps`` reads and the overhead map is the base map of the ``overhead`` channel of
+``simq.local_state_images``: neither ever needs to be a host array.
+
+The camera's unit vectors and pixel tables are formed here, on the host, in the reference's own sequence of numpy float32 operations
+(``camera_geometry``); the library has no trigonometry and no normalisation.
+"""
+import collections
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from ._lib import SimqError, lib, ptr, stream_ptr
+
+MAX_POINTS = 1 << 22             # SIMQ_OBSERVATION_MAX_POINTS of include/simq.h
+
+# What the projection of one camera pose needs: float32 vectors [3], the tables pixel_x [width] and pixel_y [height], and the three
+# depth constants far * near, far, far - near as float32.
+CameraGeometry = collections.namedtuple('CameraGeometry', ('position', 'principal', 'right', 'up', 'pixel_x', 'pixel_y', 'far_near', 'far',
+                                                           'far_minus_near'))
+# The body ids Camera._ensure_initialized collects (envs.py:1911-1915); receptacle None: an environment without one.
+IdRanges = collections.namedtuple('IdRanges', ('min_obstacle', 'max_obstacle', 'receptacle', 'min_cube', 'max_cube'))
+
+
+class ObservationProblem(ctypes.Structure):
+    """simq_observation_problem of include/simq.h."""
+    _fields_ = [('depth_offset', ctypes.c_int64), ('ids_offset', ctypes.c_int64), ('px_offset', ctypes.c_int64), ('py_offset', ctypes.c_int64),
+                ('overhead_offset', ctypes.c_int64), ('occupancy_offset', ctypes.c_int64),
+                ('cam', ctypes.c_float * 3), ('principal', ctypes.c_float * 3), ('right', ctypes.c_float * 3), ('up', ctypes.c_float * 3),
+                ('far_near', ctypes.c_float), ('far', ctypes.c_float), ('far_minus_near', ctypes.c_float),
+                ('min_obstacle', ctypes.c_int32), ('max_obstacle', ctypes.c_int32), ('receptacle', ctypes.c_int32),
+                ('has_receptacle', ctypes.c_int32), ('min_cube', ctypes.c_int32), ('max_cube', ctypes.c_int32),
+                ('height', ctypes.c_int32), ('width', ctypes.c_int32), ('rows', ctypes.c_int32), ('cols', ctypes.c_int32),
+                ('reserved_', ctypes.c_int32)]
+
+
+def camera_geometry(camera_position, camera_target, camera_up, near, far, aspect, image_height, fov=60):
+    """The CameraGeometry of one camera pose: what Camera._get_camera_params returns (position, target, up), the class's NEAR, FAR and
+    ASPECT, Camera.image_pixel_height and Camera.FOV (degrees, vertical).  Every array is float32 and is formed in the sequence of numpy
+    operations of envs.py:1931-1943, so the values are the ones the reference multiplies the depth with on this machine; the image
+    width is int(aspect * image_height) as in Camera.__init__ (envs.py:1895)."""
+    near, far, aspect, fov = float(near), float(far), float(aspect), float(fov)   # (Python scalars, as the class constants are)
+    height = int(image_height)
+    width = int(aspect * height)
+    if height < 1 or width < 1:
+        raise ValueError('camera_geometry: an image of %d x %d' % (height, width))
+    position = np.array(camera_position, dtype=np.float32)
+    principal = np.array(camera_target, dtype=np.float32) - position
+    principal = principal / np.linalg.norm(principal)
+    up = np.array(camera_up, dtype=np.float32)
+    up = up - np.dot(up, principal) * principal
+    up = up / np.linalg.norm(up)
+    right = np.cross(principal, up)
+    right = right / np.linalg.norm(right)
+    limit_y = math.tan(math.radians(fov / 2))
+    limit_x = limit_y * aspect
+    pixel_x = (2 * limit_x) * (np.arange(width, dtype=np.float32) / width - 0.5)
+    pixel_y = (2 * limit_y) * (0.5 - (np.arange(height, dtype=np.float32) + 1) / height)
+    arrays = [np.ascontiguousarray(a, np.float32) for a in (position, principal, right, up, pixel_x, pixel_y)]
+    for a, shape in zip(arrays, ((3,), (3,), (3,), (3,), (width,), (height,))):
+        if a.shape != shape:
+            raise ValueError('camera_geometry: position, target and up are 3-vectors')
+    # a Python scalar meets the float32 depth buffer as a float32 (envs.py:1928)
+    return CameraGeometry(*arrays, np.float32(far * near), np.float32(far), np.float32(far - near))
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise SimqError('simq observation maps need an MI355X (torch.cuda.is_available() is False); no CPU path')
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _frames(frames, dtype, tdtype, what):
+    """The 2-D frames of a sequence or of one [P, height, width] array / tensor."""
+    if isinstance(frames, (np.ndarray, torch.Tensor)) and frames.ndim != 3:
+        raise ValueError('%s is a sequence of 2-D %s frames or one [P, height, width] array, got %d dimensions' % (what, dtype.__name__, frames.ndim))
+    try:
+        frames = list(frames)
+    except TypeError:
+        raise ValueError('%s is a sequence of 2-D %s frames or one [P, height, width] array, got %s' % (what, dtype.__name__, type(frames).__name__)) from None
+    out = []
+    for k, f in enumerate(frames):
+        if isinstance(f, torch.Tensor):
+            if f.dtype != tdtype or f.dim() != 2 or not f.is_contiguous():
+                raise ValueError('%s[%d] must be a 2-D contiguous %s tensor, got %s %s' % (what, k, dtype.__name__, f.dtype, tuple(f.shape)))
+        elif not isinstance(f, np.ndarray) or f.dtype != dtype or f.ndim != 2:
+            raise ValueError('%s[%d] must be a 2-D %s numpy array or tensor, got %s' % (
+                what, k, dtype.__name__, '%s %s' % (f.dtype, f.shape) if isinstance(f, np.ndarray) else type(f).__name__))
+        else:
+            f = np.ascontiguousarray(f)
+        out.append(f)
+    return out
+
+
+def _maps(maps, tdtype, dev, what):
+    """The 2-D device maps of one [P, rows, cols] tensor or of a sequence of 2-D tensors: updated in place, so nothing is copied."""
+    if isinstance(maps, torch.Tensor):
+        if maps.dim() != 3:
+            raise ValueError('%s is one [P, rows, cols] device tensor or a sequence of 2-D device tensors, got %d dimensions' % (what, maps.dim()))
+    elif isinstance(maps, np.ndarray):
+        raise ValueError('%s must live on the device: it is updated in place (simq.observe takes numpy maps)' % what)
+    try:
+        maps = list(maps)
+    except TypeError:
+        raise ValueError('%s is one [P, rows, cols] device tensor or a sequence of 2-D device tensors, got %s' % (what, type(maps).__name__)) from None
+    for k, m in enumerate(maps):
+        if not isinstance(m, torch.Tensor) or m.dtype != tdtype or m.dim() != 2 or not m.is_contiguous() or m.device != dev:
+            raise ValueError('%s[%d] must be a 2-D contiguous %s tensor on %s, updated in place' % (what, k, str(tdtype).replace('torch.', ''), dev))
+    return maps
+
+
+def _per_problem(values, P, cls, what):
+    if isinstance(values, cls):
+        return [values] * P
+    values = list(values)
+    if len(values) != P or not all(isinstance(v, cls) for v in values):
+        raise ValueError('%s is one %s or one per frame (%d frames)' % (what, cls.__name__, P))
+    return values
+
+
+def _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
+    """The argument tuple of simq_observation_update, the status tensor and the device tensors the call reads
+    (tools/observation_maps_rate.py times the upload and the library call with it)."""
+    depth = _frames(depth, np.float32, torch.float32, 'depth')
+    ids = _frames(ids, np.int32, torch.int32, 'ids')
+    P = len(depth)
+    if P < 1 or len(ids) != P:
+        raise ValueError('observation_update needs at least one frame and as many id frames as depth frames (%d, %d)' % (P, len(ids)))
+    geometries = _per_problem(geometries, P, CameraGeometry, 'geometries')
+    id_ranges = _per_problem(id_ranges, P, IdRanges, 'id_ranges')
+    dev = _device()
+    overhead_maps = _maps(overhead_maps, torch.float32, dev, 'overhead_maps')
+    occupancy_maps = _maps(occupancy_maps, torch.uint8, dev, 'occupancy_maps')
+    if len(overhead_maps) != P or len(occupancy_maps) != P:
+        raise ValueError('%d frames but %d overhead maps and %d occupancy maps' % (P, len(overhead_maps), len(occupancy_maps)))
+
+    # one buffer of 4-byte words: each distinct geometry's tables once, then the depth frames, then the id frames
+    tables, words = {}, 0
+    host = []                                    # (word offset, numpy array) of what is uploaded through one staging array
+    for g in geometries:
+        if id(g) not in tables:
+            tables[id(g)] = (words, words + g.pixel_x.size)
+            host += [(words, np.ascontiguousarray(g.pixel_x, np.float32)), (words + g.pixel_x.size, np.ascontiguousarray(g.pixel_y, np.float32))]
+            words += g.pixel_x.size + g.pixel_y.size
+    offsets = []
+    for p in range(P):
+        shape = tuple(depth[p].shape)
+        if tuple(ids[p].shape) != shape or shape != (geometries[p].pixel_y.size, geometries[p].pixel_x.size):
+            raise ValueError('frame %d: depth %s, ids %s, but its geometry is for %d x %d images' % (
+                p, shape, tuple(ids[p].shape), geometries[p].pixel_y.size, geometries[p].pixel_x.size))
+        n = shape[0] * shape[1]
+        if n < 1 or n > MAX_POINTS:
+            raise ValueError('frame %d: %d x %d (1 .. %d points)' % (p, shape[0], shape[1], MAX_POINTS))
+        offsets.append((words, words + n))
+        words += 2 * n
+    frames = torch.empty(words, dtype=torch.int32, device=dev)
+    device_blocks = []
+    for p in range(P):
+        for o, a in zip(offsets[p], (depth[p], ids[p])):
+            if isinstance(a, torch.Tensor) and a.device == dev:
+                device_blocks.append((o, a))
+            else:
+                host.append((o, a.cpu().numpy() if isinstance(a, torch.Tensor) else a))
+    lo = min(o for o, a in host)
+    hi = max(o + a.size for o, a in host)
+    staging = np.zeros(hi - lo, np.int32)
+    for o, a in host:
+        staging[o - lo:o - lo + a.size] = a.reshape(-1).view(np.int32)
+    frames[lo:hi].copy_(torch.from_numpy(staging))
+    for o, a in device_blocks:                   # (after the staging copy, whose span may cover them)
+        frames[o:o + a.numel()].copy_(a.reshape(-1).view(torch.int32))
+
+    # the maps where they are: offsets from the lowest address of each kind
+    base_o = min(m.data_ptr() for m in overhead_maps)
+    base_c = min(m.data_ptr() for m in occupancy_maps)
+    if any((m.data_ptr() - base_o) % 4 for m in overhead_maps):
+        raise ValueError('overhead_maps: the maps must be 4-byte aligned to each other')
+    overhead_floats = max((m.data_ptr() - base_o) // 4 + m.numel() for m in overhead_maps)
+    occupancy_bytes = max(m.data_ptr() - base_c + m.numel() for m in occupancy_maps)
+    probs = (ObservationProblem * P)()
+    for p in range(P):
+        g, r, om, cm = geometries[p], id_ranges[p], overhead_maps[p], occupancy_maps[p]
+        if tuple(om.shape) != tuple(cm.shape):
+            raise ValueError('problem %d: an overhead map of %s but an occupancy map of %s' % (p, tuple(om.shape), tuple(cm.shape)))
+        q = probs[p]
+        q.depth_offset, q.ids_offset = offsets[p]
+        q.px_offset, q.py_offset = tables[id(g)]
+        q.overhead_offset = (om.data_ptr() - base_o) // 4
+        q.occupancy_offset = cm.data_ptr() - base_c
+        for name, v in (('cam', g.position), ('principal', g.principal), ('right', g.right), ('up', g.up)):
+            setattr(q, name, (ctypes.c_float * 3)(*[float(x) for x in v]))
+        q.far_near, q.far, q.far_minus_near = float(g.far_near), float(g.far), float(g.far_minus_near)
+        q.min_obstacle, q.max_obstacle, q.min_cube, q.max_cube = int(r.min_obstacle), int(r.max_obstacle), int(r.min_cube), int(r.max_cube)
+        q.has_receptacle = 0 if r.receptacle is None else 1
+        q.receptacle = 0 if r.receptacle is None else int(r.receptacle)
+        q.height, q.width = depth[p].shape
+        q.rows, q.cols = om.shape
+    d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    args = (ptr(frames), ctypes.c_int64(words), probs, P, ptr(d_probs), ctypes.c_void_p(base_o), ctypes.c_int64(overhead_floats),
+            ctypes.c_void_p(base_c), ctypes.c_int64(occupancy_bytes), ptr(status), stream_ptr(dev))
+    return args, status, (frames, d_probs, overhead_maps, occupancy_maps)
+
+
+def observation_update(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
+    """Mapper.update (envs.py:2053-2065) for P camera frames in one launch: both maps of every problem are updated in place on the device.
+
+    depth: P depth buffers [height, width] float32 as the simulator returns them (numpy arrays, uploaded; or contiguous device tensors),
+    or one [P, height, width] array / tensor; frames of different cameras may be mixed.  ids: the same for the body-id segmentation,
+    int32.  geometries: one CameraGeometry (camera_geometry) per frame, or one for all; frames that share a geometry object share its
+    tables on the device.  id_ranges: one IdRanges per frame, or one for all.  overhead_maps: one float32 [P, rows, cols] device tensor
+    or P 2-D float32 device tensors of any shapes (Mapper.global_overhead_map_without_robots); occupancy_maps: the same in uint8
+    (OccupancyMap.occupancy_map), each of its overhead map's shape.  Nothing but the frames, the tables and the descriptors is uploaded.
+
+    Separately allocated maps are described to the library as offsets from the lowest address of their kind, so the buffer it is told
+    of reaches from the lowest map to the end of the highest and takes in whatever the allocator placed between them.  The library
+    checks and writes the maps' own spans only, but it refuses a buffer of 2^40 elements or more: maps of one call whose allocations
+    lie that far apart (in practice: on different devices or in different address ranges) must go into one tensor or into two calls.
+
+    Returns (overhead_maps, occupancy_maps) as given.  Raises ValueError for a wrong dtype, rank, contiguity or device, SimqError for
+    what the library refuses (two problems naming one map among it; nothing is launched) and for the frames that held a point that is
+    not finite: their maps are unchanged, every other problem of the call is updated."""
+    args, status, keep = _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps)
+    lib.call('simq_observation_update', *args)
+    st = status.cpu().numpy()
+    del keep
+    if st.any():
+        bad = np.flatnonzero(st)
+        if (st[bad] == 1).all():
+            raise SimqError('simq_observation_update: %d frame(s) hold a point that is not finite (a depth buffer outside what the near and far '
+                            'planes allow); their maps are unchanged (problems %s)' % (bad.size, bad[:8].tolist()))
+        raise SimqError('simq_observation_update: %d problem(s) failed (status %s at problems %s)' % (bad.size, st[bad[:8]].tolist(), bad[:8].tolist()))
+    return overhead_maps, occupancy_maps
+
+
+def observe(depth, ids, geometry, id_ranges, overhead_map, occupancy_map):
+    """Mapper.update for one frame and one pair of numpy maps (float32 and uint8 [rows, cols]): returns the two updated arrays, the
+    arguments are left as they are."""
+    dev = _device()
+    for m, dtype, what in ((overhead_map, np.float32, 'overhead_map'), (occupancy_map, np.uint8, 'occupancy_map')):
+        if not isinstance(m, np.ndarray) or m.dtype != dtype or m.ndim != 2:
+            raise ValueError('%s must be a 2-D %s numpy array' % (what, dtype.__name__))
+    om = torch.from_numpy(np.ascontiguousarray(overhead_map)).to(dev)
+    cm = torch.from_numpy(np.ascontiguousarray(occupancy_map)).to(dev)
+    observation_update([depth], [ids], geometry, id_ranges, [om], [cm])
+    return om.cpu().numpy(), cm.cpu().numpy()
