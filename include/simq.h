@@ -537,7 +537,8 @@ int simq_upsample2x_bwd(const float* d_dout, float* d_din, int batch, int h, int
  * One problem = one 8-connected grid [rows][cols] of uint8 (free where != 0) and one source pixel.  An edge joins two free cells
  * inside the grid; straight edges weigh 1, diagonal ones float32(sqrt 2).  The source gets 0 even when blocked (then nothing else is
  * reachable); unreachable cells get -1.  Every update is fl32(d[u] + w) accepted when strictly smaller, iterated to the fixed point,
- * so the distances equal the reference SPFA's bit for bit (SPFA's parents, which depend on its queue order, are not produced).
+ * so the distances equal the reference SPFA's bit for bit (SPFA's parents, which depend on its queue order, come from
+ * simq_grid_paths below, which emulates the search itself).
  * Optional epilogue, in the reference's order: img = d / pixels_per_meter (fp32 division; 1 = none); unreachable_to_max != 0:
  * img[img < 0] = img.max(); img *= scale (1 = none).
  * `problems`: host array of n descriptors, validated here (rows, cols >= 1, rows * cols < 2^22, source inside the grid, the grid
@@ -555,6 +556,68 @@ typedef struct simq_grid_problem {
 int simq_grid_distance_images(const uint8_t* d_grids, int64_t grids_bytes, const simq_grid_problem* problems, int n,
                               simq_grid_problem* d_problems, float* d_out, int64_t out_floats, float pixels_per_meter,
                               int unreachable_to_max, float scale, int32_t* d_status, void* stream);
+
+/* ---- shortest-path waypoints: SPFA's parents and the dense path (shortest_paths.pyx:69-137 GridGraph._spfa and the walk of
+ * GridGraph.shortest_path; the front half of OccupancyMap.shortest_path, envs.py:2477-2490) --------------------------------------
+ * One problem = one grid [rows][cols] of uint8 (free where != 0), a source pixel and a target pixel; one wavefront emulates the
+ * reference's search exactly, problems are the parallel axis, every problem of a call in one launch.  The rules that decide the
+ * parents (they depend on the order of the queue, unlike the distances):
+ *   edges       leave a free cell u only (a blocked source relaxes nothing) and go to the free neighbours inside the grid in the order
+ *               (di, dj) = (0,-1) (0,1) (-1,-1) (-1,0) (-1,1) (1,-1) (1,0) (1,1): direction codes 0 .. 7; weights 1 and float32(sqrt 2)
+ *   relaxation  new = fl32(d[u] + w) is accepted when strictly smaller than d[v]; the parent of v becomes u on every acceptance;
+ *               d starts at inf = float32(2 * rows * cols) of the full grid, the source at 0
+ *   queue       first in, first out, slots numbered from 1 (head = 0, the source in slot tail = 1); a pop takes slot ++head.  An
+ *               accepted v that is not queued goes to slot ++tail; a queued one is not moved.  After each push the two slots tail
+ *               and head + 1 are exchanged when d[queue[tail]] < d[queue[head + 1]] (strict; the same slot when the pushed vertex
+ *               is the only one queued)
+ *   order       the eight relaxations of one pop are sequential: the push at edge k compares against the front's distance as it
+ *               stands after edges <= k of that pop (the front may be a neighbour of u that a later edge lowers)
+ * The walk starts at the target and follows the parents until it meets the source or a cell without parent.  Outputs per problem:
+ *   dense path  int32 (i, j) pairs, target first, at pair path_offset of d_paths, at most path_capacity pairs; its length in
+ *               d_lengths[p].  Length 1 (the target alone) for an unreachable target, a blocked source and target == source.
+ *   parents     (parents_offset >= 0) int32 [rows][cols] at d_parents + parents_offset: the ravelled index i * cols + j of the parent
+ *               in the full grid, -1 where none
+ *   distances   (dist_offset >= 0) fp32 [rows][cols] at d_dist + dist_offset, -1 where unreachable, 0 at the source even when it is
+ *               blocked: what simq_grid_distance_images writes without its epilogue
+ *   end pixels  d_endpoints[4 p .. 4 p + 4): the source and target the search used (after the snap below)
+ * Two optional front stages, those of OccupancyMap.shortest_path:
+ *   thin_offset >= 0     the skimage.draw.line from the source to the target as given (the rule of simq_intention_maps above) is
+ *                        read from the problem's second uint8 map in d_grids; when every cell on it is 1 (the reference's
+ *                        (1 - cspace_thin[rr, cc]).sum() == 0 in uint8 arithmetic), the problem ends with status 1 and length 0:
+ *                        no search, no path, no image; the end pixels hold the pair as given
+ *   closest_offset >= 0  source and target are replaced by closest[:, i, j] before the search: int32 [2][rows][cols] at d_closest +
+ *                        closest_offset, the layout simq_occupancy_maps writes.  The line above is tested on the pixels as given.
+ * The search state lives in LDS over a window of the grid that the caller declares: rows [box_i0, box_i0 + box_rows), columns
+ * [box_j0, box_j0 + box_cols), which must hold every free cell (empty when there is none).  The window plus a blocked one-cell halo
+ * has (box_rows + 2) * (box_cols + 2) <= SIMQ_GRID_PATH_MAX_BOX_CELLS cells (8 bytes each of the 160 KiB); a Mapper room needs
+ * 94 x 94.  The kernel reads the whole grid once and gives status 2 when a free cell lies outside the window.
+ * `problems`: host array of n descriptors, validated here before anything is copied or launched (rows, cols >= 1, rows * cols <
+ * SIMQ_GRID_MAX_CELLS; source and target inside the grid; the window inside the grid and under the cap; path_capacity >= 1; every
+ * input and output inside the declared extent of its buffer; no two problems' outputs overlapping; the output buffers, d_lengths,
+ * d_endpoints, d_status and d_problems disjoint from each other and from the inputs; 4-byte alignment of the int32 / fp32 buffers, 8
+ * of d_problems) and copied to the caller's device buffer d_problems (n descriptors) on `stream`.  Several problems may share a
+ * grid.  d_closest, d_parents, d_dist may be NULL when no problem uses them.  d_status[n] (int32): 0 = path traced, 1 = straight line
+ * clear, 2 = bad descriptor (the kernel checks again -- sizes, pixels, the snapped pixels, the window -- and writes nothing else),
+ * 3 = path_capacity too small: d_lengths[p] holds the needed count, nothing is written past the capacity, the images are complete,
+ * 4 = the search passed its cap of 64 * free cells + 64 pops (cannot happen: SPFA here pops each cell 1.0 - 1.1 times). */
+typedef struct simq_grid_path_problem {
+    int64_t grid_offset;        /* byte offset of the problem's [rows][cols] uint8 grid in d_grids */
+    int64_t thin_offset;        /* byte offset of its [rows][cols] uint8 thin map in d_grids, or -1 */
+    int64_t closest_offset;     /* int32 offset of its [2][rows][cols] closest cells in d_closest, or -1 */
+    int64_t path_offset;        /* pair offset of its dense path in d_paths (int32 offset 2 * path_offset) */
+    int64_t parents_offset;     /* int32 offset of its [rows][cols] parent image in d_parents, or -1 */
+    int64_t dist_offset;        /* float offset of its [rows][cols] distance image in d_dist, or -1 */
+    int32_t path_capacity;      /* pairs */
+    int32_t rows, cols;
+    int32_t src_i, src_j, tgt_i, tgt_j;
+    int32_t box_i0, box_j0, box_rows, box_cols;
+    int32_t reserved_;
+} simq_grid_path_problem;
+#define SIMQ_GRID_PATH_MAX_BOX_CELLS 20000
+int simq_grid_paths(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* d_closest, int64_t closest_ints,
+                    const simq_grid_path_problem* problems, int n, simq_grid_path_problem* d_problems, int32_t* d_paths,
+                    int64_t path_pairs, int32_t* d_lengths, int32_t* d_endpoints, int32_t* d_parents, int64_t parents_ints, float* d_dist,
+                    int64_t dist_floats, int32_t* d_status, void* stream);
 
 /* ---- local state images (Mapper.get_state's crop / rotation: envs.py:2199-2215 _get_local_map / _get_local_distance_map,
  * 2243-2275 _create_global_overhead_map / _create_global_robot_map, 2368-2375 the nonspatial channels) -----------------------------

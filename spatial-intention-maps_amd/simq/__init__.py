@@ -34,6 +34,9 @@ _LAZY = {
     'resume': ('.checkpoint', 'resume'),
     'GridGraph': ('.grid_paths', 'GridGraph'),
     'grid_distance_images': ('.grid_paths', 'grid_distance_images'),
+    'WaypointGraph': ('.waypoints', 'WaypointGraph'),
+    'grid_dense_paths': ('.waypoints', 'grid_dense_paths'),
+    'shortest_paths': ('.waypoints', 'shortest_paths'),
     'local_state_images': ('.local_maps', 'local_state_images'),
     'local_map': ('.local_maps', 'local_map'),
     'local_distance_map': ('.local_maps', 'local_distance_map'),

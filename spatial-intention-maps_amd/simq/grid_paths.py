@@ -5,7 +5,8 @@ SPFA from a source pixel; ``OccupancyMap`` rebuilds it on every map update (envs
 images per robot per step (envs.py:2287-2300).  ``simq_grid_distance_images`` (csrc/grid_paths.hip) computes such images for many
 (grid, source) problems in one launch, bit for bit equal to SPFA's distances: every update is fl32(d[u] + w) accepted when strictly
 smaller, iterated to the fixed point, whose value does not depend on the visiting order.  SPFA's parents -- the waypoints of
-``GridGraph.shortest_path`` -- do depend on its queue order, so this module produces distances only.
+``GridGraph.shortest_path`` -- do depend on its queue order, so this module produces distances only; ``simq.waypoints`` emulates the
+search itself and has the waypoints (``simq.WaypointGraph``, ``simq.grid_dense_paths``, ``simq.shortest_paths``).
 """
 import ctypes
 
@@ -175,4 +176,4 @@ class GridGraph:
     def shortest_path(self, source, target):
         raise NotImplementedError('simq.GridGraph computes distances only: the waypoints of shortest_path follow the parents SPFA '
                                   'records, and those depend on the order it visits cells wherever equal-length paths tie, which no '
-                                  'parallel algorithm reproduces; keep the reference GridGraph for navigation')
+                                  'parallel relaxation reproduces; simq.WaypointGraph emulates the search itself and has them')

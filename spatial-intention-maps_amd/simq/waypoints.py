@@ -1,0 +1,357 @@
+"""Shortest-path waypoints on the GPU: the navigation half of the reference's ``shortest_paths.GridGraph``.
+
+``GridGraph.shortest_path`` (shortest_paths.pyx:121-154) walks the parents its SPFA recorded from the target back to the source,
+simplifies that dense path with ``skimage.measure.approximate_polygon`` and drops the waypoints a clear line makes unnecessary;
+``OccupancyMap.shortest_path`` (envs.py:2477-2504) puts a straight-line test and the snap to the closest free cells in front and the
+conversion to positions behind.  SPFA's parents depend on the order of its queue, so ``simq_grid_paths`` (csrc/grid_waypoints.hip)
+emulates the search itself, one problem per wavefront, and returns parents, distances and dense paths that equal the reference's bit
+for bit.  The simplification stays on the host: it is float64 trigonometry whose ties are libm noise, and the
+waypoints are consumed on the host anyway.
+"""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from ._lib import SimqError, lib, ptr, stream_ptr
+from .grid_paths import GridGraph, _check_grid, _device, _pixel
+from .local_maps import PIXELS_PER_METER, position_to_pixel_indices
+
+MAX_BOX_CELLS = 20000            # SIMQ_GRID_PATH_MAX_BOX_CELLS of include/simq.h
+TRACED, STRAIGHT, BAD_DESCRIPTOR, CAPACITY = 0, 1, 2, 3
+
+
+class GridPathProblem(ctypes.Structure):
+    """simq_grid_path_problem of include/simq.h."""
+    _fields_ = [(n, ctypes.c_int64) for n in ('grid_offset', 'thin_offset', 'closest_offset', 'path_offset', 'parents_offset',
+                                              'dist_offset')] + \
+               [(n, ctypes.c_int32) for n in ('path_capacity', 'rows', 'cols', 'src_i', 'src_j', 'tgt_i', 'tgt_j', 'box_i0', 'box_j0',
+                                              'box_rows', 'box_cols', 'reserved_')]
+
+
+DensePaths = collections.namedtuple('DensePaths', 'paths status endpoints parents distances')
+
+
+def line(r0, c0, r1, c1):
+    """skimage.draw.line in closed form (the rule of simq_intention_maps, include/simq.h): with n = max(|dr|, |dc|) and m = min(|dr|,
+    |dc|), point i is i steps along the major axis and (2 * m * i + n) // (2 * n) along the minor one."""
+    dr, dc = abs(r1 - r0), abs(c1 - c0)
+    sr, sc = (1 if r1 > r0 else -1), (1 if c1 > c0 else -1)
+    n, m = max(dr, dc), min(dr, dc)
+    i = np.arange(n + 1, dtype=np.int64)
+    minor = (2 * m * i + n) // (2 * n) if n > 0 else np.zeros(1, np.int64)
+    if dr > dc:
+        return r0 + sr * i, c0 + sc * minor
+    return r0 + sr * minor, c0 + sc * i
+
+
+def pixel_indices_to_position(pixel_i, pixel_j, image_shape):
+    """Mapper.pixel_indices_to_position (envs.py:2399-2402)."""
+    position_x = ((pixel_j + 0.5) - image_shape[1] / 2) / PIXELS_PER_METER
+    position_y = (image_shape[0] / 2 - (pixel_i + 0.5)) / PIXELS_PER_METER
+    return position_x, position_y
+
+
+def _default_simplify():
+    try:
+        from skimage.measure import approximate_polygon      # pylint: disable=import-outside-toplevel
+    except ImportError:
+        raise SimqError('shortest_path simplifies the dense path with skimage.measure.approximate_polygon and scikit-image is not '
+                        'installed: install it, or pass simplify=callable(coords, tolerance) (dense_path needs neither)') from None
+    return approximate_polygon
+
+
+def walk(parents, source, target):
+    """The dense path of shortest_paths.pyx:126-137 over a host parent image: int32 [n, 2], target first."""
+    cols = parents.shape[1]
+    flat = parents.reshape(-1)
+    u = source[0] * cols + source[1]
+    v = target[0] * cols + target[1]
+    path = [(v // cols, v % cols)]
+    while v != u:
+        v = int(flat[v])
+        if v < 0:
+            break
+        path.append((v // cols, v % cols))
+    return np.asarray(path, np.int32)
+
+
+def prune(grid, dense, simplify):
+    """shortest_paths.pyx:139-154 on a host grid: simplify(dense, tolerance=1), keep a waypoint only where the line from the last kept
+    one to its successor crosses a cell that is not 1 (the reference's uint8 `1 - grid`), reverse.  Returns [(i, j)] source first."""
+    sparse = np.asarray(simplify(np.array(dense), tolerance=1))
+    path = [sparse[0]]
+    for k in range(1, sparse.shape[0] - 1):
+        rr, cc = line(int(path[-1][0]), int(path[-1][1]), int(sparse[k + 1][0]), int(sparse[k + 1][1]))
+        if (1 - grid[rr, cc]).sum() > 0:
+            path.append(sparse[k])
+    if len(sparse) > 1:
+        path.append(sparse[-1])
+    return [(int(q[0]), int(q[1])) for q in path[::-1]]
+
+
+def _as_list(maps, what, check=_check_grid):
+    if isinstance(maps, (np.ndarray, torch.Tensor)) and maps.ndim == 3:
+        maps = list(maps)
+    return [check(m, '%s[%d]' % (what, k)) for k, m in enumerate(maps)]
+
+
+def _check_closest(c, what):
+    ok = isinstance(c, (np.ndarray, torch.Tensor)) and c.ndim == 3 and c.shape[0] == 2 and \
+        (c.dtype == torch.int32 and c.is_contiguous() if isinstance(c, torch.Tensor) else c.dtype == np.int32 and c.flags['C_CONTIGUOUS'])
+    if not ok:
+        raise ValueError('%s must be a contiguous int32 [2, rows, cols] array or tensor (closest_cspace_indices)' % what)
+    return c
+
+
+def _pack(items, used, dtype, dev):
+    """One device buffer holding items[k] for k in used, and {k: element offset} (offsets kept multiples of 16 elements)."""
+    off, total = {}, 0
+    for k in used:
+        off[k] = total
+        n = int(np.prod(items[k].shape))
+        total += (n + 15) // 16 * 16
+    buf = torch.zeros(max(total, 1), dtype=dtype, device=dev)
+    for k in used:
+        t = items[k] if isinstance(items[k], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(items[k]))
+        buf[off[k]:off[k] + t.numel()].copy_(t.reshape(-1))
+    return buf, off
+
+
+def _boxes(grids, used, dev):
+    """{k: (i0, j0, rows, cols)}: the bounding box of the free cells of each used grid; device grids are reduced there and the boxes
+    of all of them downloaded at once."""
+    boxes, rows_on_dev, keys = {}, [], []
+    for k in used:
+        g = grids[k]
+        if isinstance(g, torch.Tensor) and g.device.type == 'cuda':
+            R, C = g.shape
+            ri, ci = torch.arange(R, device=g.device), torch.arange(C, device=g.device)
+            fr, fc = (g != 0).any(1), (g != 0).any(0)
+            rows_on_dev.append(torch.stack([torch.where(fr, ri, R).min(), torch.where(fr, ri, -1).max(),
+                                            torch.where(fc, ci, C).min(), torch.where(fc, ci, -1).max()]))
+            keys.append(k)
+        else:
+            g = g.numpy() if isinstance(g, torch.Tensor) else g
+            ii, jj = np.nonzero(g)
+            boxes[k] = (0, 0, 0, 0) if ii.size == 0 else (int(ii.min()), int(jj.min()), int(ii.max() - ii.min() + 1),
+                                                         int(jj.max() - jj.min() + 1))
+    if keys:
+        for k, (i0, i1, j0, j1) in zip(keys, torch.stack(rows_on_dev).cpu().tolist()):
+            boxes[k] = (0, 0, 0, 0) if i1 < 0 else (i0, j0, i1 - i0 + 1, j1 - j0 + 1)
+    return boxes
+
+
+def _launch(dev, packed, closest_buf, descs, parents, distances):
+    """One simq_grid_paths call over `descs`: dicts with the descriptor's grid / thin / closest offsets, shape, pixels, box and capacity."""
+    P = len(descs)
+    probs = (GridPathProblem * P)()
+    po = io = 0
+    for p, d in enumerate(descs):
+        cells = d['rows'] * d['cols']
+        probs[p] = GridPathProblem(d['grid'], d['thin'], d['closest'], po, io if parents else -1, io if distances else -1, d['capacity'],
+                                   d['rows'], d['cols'], d['src'][0], d['src'][1], d['tgt'][0], d['tgt'][1], *d['box'], 0)
+        po += d['capacity']
+        io += cells
+    d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+    paths = torch.empty((po, 2), dtype=torch.int32, device=dev)
+    small = torch.empty((P, 6), dtype=torch.int32, device=dev)          # lengths | status | end pixels
+    lengths, status, ends = small.view(-1)[:P], small.view(-1)[P:2 * P], small.view(-1)[2 * P:]
+    par = torch.empty(io, dtype=torch.int32, device=dev) if parents else None
+    dist = torch.empty(io, dtype=torch.float32, device=dev) if distances else None
+    lib.call('simq_grid_paths', ptr(packed), ctypes.c_int64(packed.numel()), ptr(closest_buf),
+             ctypes.c_int64(0 if closest_buf is None else closest_buf.numel()), probs, P, ptr(d_probs), ptr(paths), ctypes.c_int64(po),
+             ptr(lengths), ptr(ends), ptr(par), ctypes.c_int64(io), ptr(dist), ctypes.c_int64(io), ptr(status), stream_ptr(dev))
+    host = small.cpu().numpy().reshape(-1)
+    return paths, host[:P].copy(), host[P:2 * P].copy(), host[2 * P:].reshape(P, 4).copy(), par, dist
+
+
+def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, distances=False, thin=None, closest=None):
+    """The dense paths of P (grid, source, target) problems in one launch: SPFA from the source, then the walk over its parents from
+    the target (shortest_paths.pyx:69-137), bit for bit.
+
+    grids, grid_index: as grid_distance_images (2-D uint8 numpy arrays or device tensors, or one [G, rows, cols] array / tensor; free
+    where nonzero; problem p uses grids[grid_index[p]], grid p when omitted).  sources, targets: P pixels (i, j) each.  thin, closest:
+    the front half of OccupancyMap.shortest_path (envs.py:2483-2489), one entry per grid: with thin[k] (uint8, cspace_thin) a problem
+    whose skimage.draw.line from source to target crosses only cells equal to 1 ends as STRAIGHT without a search; with closest[k]
+    (int32 [2, rows, cols], closest_cspace_indices) source and target are replaced by closest[:, i, j] before the search (the line is
+    tested on the pixels as given).
+
+    Returns DensePaths(paths, status, endpoints, parents, distances): paths, a list of P int32 numpy arrays [n, 2], target first (n = 1,
+    the target alone, for an unreachable target, a blocked source and target == source; n = 0 for a STRAIGHT problem); status, int32
+    numpy [P] of TRACED / STRAIGHT; endpoints, int32 numpy [P, 4], the (source, target) pixels the search used; parents (when asked),
+    a list of P int32 device tensors [rows, cols] holding the ravelled index of each cell's parent, -1 where none; distances (when
+    asked), P float32 device tensors [rows, cols], -1 where unreachable.  The images of a STRAIGHT problem are not written.
+
+    The search state lives in LDS over the bounding box of the grid's free cells: a box of more than MAX_BOX_CELLS cells with its
+    one-cell halo is refused (SimqError, nothing launched).  A path longer than the first buffer is fetched with one more launch."""
+    grids = _as_list(grids, 'grids')
+    srcs, tgts = [_pixel(s) for s in sources], [_pixel(t) for t in targets]
+    if not grids or not srcs:
+        raise ValueError('grid_dense_paths needs at least one grid and one source')
+    if len(srcs) != len(tgts):
+        raise ValueError('%d sources but %d targets' % (len(srcs), len(tgts)))
+    if grid_index is None:
+        if len(grids) != len(srcs):
+            raise ValueError('%d grids but %d sources (grid_index shares grids between problems)' % (len(grids), len(srcs)))
+        grid_index = range(len(srcs))
+    grid_index = [int(k) for k in grid_index]
+    if len(grid_index) != len(srcs) or any(k < 0 or k >= len(grids) for k in grid_index):
+        raise ValueError('grid_index must name one of the %d grids for each of the %d sources' % (len(grids), len(srcs)))
+    if thin is not None:
+        thin = _as_list(thin, 'thin')
+    if closest is not None:
+        closest = _as_list(closest, 'closest', _check_closest)
+    used = sorted(set(grid_index))
+    for name, extra in (('thin', thin), ('closest', closest)):
+        if extra is not None:
+            if len(extra) != len(grids):
+                raise ValueError('%s must hold one map per grid (%d), got %d' % (name, len(grids), len(extra)))
+            for k in used:
+                if tuple(extra[k].shape[-2:]) != tuple(grids[k].shape):
+                    raise ValueError('%s[%d] is %s but grids[%d] is %s' % (name, k, tuple(extra[k].shape), k, tuple(grids[k].shape)))
+    dev = _device()
+
+    G = len(grids)
+    packed, goff = _pack(list(grids) + (list(thin) if thin is not None else []), used + ([G + k for k in used] if thin is not None else []),
+                         torch.uint8, dev)
+    closest_buf, coff = _pack(closest, used, torch.int32, dev) if closest is not None else (None, {})
+    boxes = _boxes(grids, used, dev)
+    descs = []
+    for k, s, t in zip(grid_index, srcs, tgts):
+        rows, cols = grids[k].shape
+        box = boxes[k]
+        descs.append(dict(grid=goff[k], thin=goff[G + k] if thin is not None else -1, closest=coff.get(k, -1), rows=rows, cols=cols, src=s,
+                          tgt=t, box=box, capacity=max(1, min(box[2] * box[3], 2 * (box[2] + box[3]) + 8))))
+    paths, lengths, status, ends, par, dist = _launch(dev, packed, closest_buf, descs, parents, distances)
+    _raise_for(status)
+    starts = np.concatenate([[0], np.cumsum([d['capacity'] for d in descs])])
+    host = paths.cpu().numpy()
+    out = [host[starts[p]:starts[p] + min(lengths[p], descs[p]['capacity'])].copy() for p in range(len(descs))]
+    short = np.flatnonzero(status == CAPACITY)
+    if short.size:                                       # a longer buffer for those problems, once; no image is written again
+        again = [dict(descs[p], capacity=int(lengths[p]), thin=-1, closest=-1, src=tuple(int(x) for x in ends[p, :2]),
+                      tgt=tuple(int(x) for x in ends[p, 2:]))
+                 for p in short]
+        paths2, lengths2, status2, _, _, _ = _launch(dev, packed, None, again, False, False)
+        _raise_for(status2, allow_capacity=False)
+        host2, o = paths2.cpu().numpy(), 0
+        for p, n in zip(short, lengths2):
+            out[p] = host2[o:o + n].copy()
+            o += int(lengths[p])
+            status[p] = TRACED
+    views = [None, None]
+    for h, flat in enumerate((par, dist)):
+        if flat is not None:
+            views[h], o = [], 0
+            for d in descs:
+                views[h].append(flat[o:o + d['rows'] * d['cols']].view(d['rows'], d['cols']))
+                o += d['rows'] * d['cols']
+    return DensePaths(out, status, ends, views[0], views[1])
+
+
+def _raise_for(status, allow_capacity=True):
+    bad = np.flatnonzero((status != TRACED) & (status != STRAIGHT) & ((status != CAPACITY) | (not allow_capacity)))
+    if bad.size:
+        raise SimqError('simq_grid_paths: %d problem(s) failed (status %s at problems %s; 2: a free cell outside the declared box or a '
+                        'closest cell outside the grid, 3: path buffer, 4: pop cap)' % (bad.size, status[bad[:8]].tolist(), bad[:8].tolist()))
+
+
+class WaypointGraph(GridGraph):
+    """shortest_paths.GridGraph with its waypoints: GridGraph's distance methods plus dense_path and shortest_path.
+
+    Results are cached per source, as _spfa_with_cache does: the parent and distance images come back as host arrays from one launch,
+    and every further target from that source is a host walk with no launch.  shortest_path_image of a source already searched for a
+    path returns that search's distance image."""
+
+    #: replaces the device search when set: callable(grid, source) -> (distances float32 [rows, cols], parents int32 [rows, cols]);
+    #: the tests pin the host half (walk, pruning, reversal) through it without a device
+    search = None
+
+    def __init__(self, grid):
+        super().__init__(grid)
+        self.parents = {}
+
+    def _parents(self, source):
+        if source not in self.parents:
+            if self.search is not None:
+                dist, par = self.search(self.grid, source)
+            else:
+                if self._dev_grid is None:
+                    self._dev_grid = torch.from_numpy(self.grid).to(_device())
+                got = grid_dense_paths([self._dev_grid], [source], [source], parents=True, distances=True)
+                par, dist = got.parents[0].cpu().numpy(), got.distances[0].cpu().numpy()
+            self.parents[source] = np.asarray(par, np.int32)
+            self.cache.setdefault(source, np.asarray(dist, np.float32))
+        return self.parents[source]
+
+    def dense_path(self, source, target):
+        """The dense path of shortest_paths.pyx:126-137 as an int32 array [n, 2], target first."""
+        source, target = self._pixel_in_grid(source, 'source'), self._pixel_in_grid(target, 'target')
+        return walk(self._parents(source), source, target)
+
+    def shortest_path(self, source, target, simplify=None):
+        """The waypoints of GridGraph.shortest_path (shortest_paths.pyx:121-154) as a list of (i, j), source first.  simplify:
+        callable(coords, tolerance) standing in for skimage.measure.approximate_polygon (the default, imported here)."""
+        simplify = _default_simplify() if simplify is None else simplify
+        return prune(self.grid, self.dense_path(source, target), simplify)
+
+
+def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positions, map_index=None, simplify=None):
+    """OccupancyMap.shortest_path (envs.py:2477-2504) for P robots in one launch, on the device tensors simq.occupancy_maps returned.
+
+    cspace, cspace_thin: M uint8 maps each ([M, rows, cols] tensor or a list), closest: M int32 [2, rows, cols]; source_positions,
+    target_positions: P positions (x, y[, z]); map_index: the map of each problem (problem p uses map p when omitted).  Positions
+    become pixels and pixels positions on the host, in float64 as the reference's scalars; the straight-line test, the snap to the
+    closest free cells, the search and the walk run on the device; simplification (simplify, default
+    skimage.measure.approximate_polygon) and pruning run on the host, over the free-cell boxes of the maps that had a problem that was
+    not straight -- nothing else of a configuration space is downloaded.  Returns P lists of positions: the two given tuples when the
+    line is clear or the path has fewer than two waypoints, otherwise (x, y, 0) tuples with the given tuples at both ends."""
+    maps = _as_list(cspace, 'cspace')
+    P = len(source_positions)
+    if len(target_positions) != P or P < 1:
+        raise ValueError('%d source positions but %d target positions' % (P, len(target_positions)))
+    if map_index is None:
+        if len(maps) != P:
+            raise ValueError('%d maps but %d positions (map_index shares maps between problems)' % (len(maps), P))
+        map_index = range(P)
+    map_index = [int(k) for k in map_index]
+    if len(map_index) != P or any(k < 0 or k >= len(maps) for k in map_index):
+        raise ValueError('map_index must name one of the %d maps for each of the %d positions' % (len(maps), P))
+    srcs = [position_to_pixel_indices(s[0], s[1], tuple(maps[k].shape)) for s, k in zip(source_positions, map_index)]
+    tgts = [position_to_pixel_indices(t[0], t[1], tuple(maps[k].shape)) for t, k in zip(target_positions, map_index)]
+    got = grid_dense_paths(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest)
+    if (got.status == TRACED).any():
+        simplify = _default_simplify() if simplify is None else simplify
+    host_maps, result = {}, []
+    for p, k in enumerate(map_index):
+        source_position, target_position = source_positions[p], target_positions[p]
+        if got.status[p] == STRAIGHT:
+            result.append([source_position, target_position])
+            continue
+        if k not in host_maps:
+            host_maps[k] = _download_box(maps[k], got.paths, [q for q in range(P) if map_index[q] == k and got.status[q] == TRACED])
+        shape = tuple(maps[k].shape)
+        path = []
+        for i, j in prune(host_maps[k], got.paths[p], simplify):
+            position_x, position_y = pixel_indices_to_position(i, j, shape)
+            path.append((position_x, position_y, 0))
+        if len(path) < 2:
+            path = [source_position, target_position]
+        else:
+            path[0] = source_position
+            path[-1] = target_position
+        result.append(path)
+    return result
+
+
+def _download_box(grid, paths, problems):
+    """A host grid of zeros holding the cells of `grid` over the box that the dense paths of `problems` span: every line the pruning
+    draws joins two cells of one path, so it stays inside that box."""
+    pts = np.concatenate([paths[q] for q in problems])
+    i0, j0, i1, j1 = int(pts[:, 0].min()), int(pts[:, 1].min()), int(pts[:, 0].max()) + 1, int(pts[:, 1].max()) + 1
+    host = np.zeros(tuple(grid.shape), np.uint8)
+    part = grid[i0:i1, j0:j1]
+    host[i0:i1, j0:j1] = part.cpu().numpy() if isinstance(part, torch.Tensor) else part
+    return host
