@@ -809,6 +809,40 @@ int simq_observation_update(const void* d_frames, int64_t frame_words, const sim
                             simq_observation_problem* d_problems, float* d_overhead, int64_t overhead_floats, uint8_t* d_occupancy,
                             int64_t occupancy_bytes, int32_t* d_status, void* stream);
 
+/* ---- Q-map visualisations: the state and output panels of utils.get_state_output_visualization (utils.py:97-131), as the training
+ * loop draws them for tensorboard (train.py:292-304) and enjoy.py --debug on every step --------------------------------------------
+ * One problem = one state [96][96][channels] fp32 NHWC (a batch row, a slice of a replay ring: read in place) and one output
+ * [n][96][96] fp32 (a Q-map, or the stacked ground-truth and predicted intention of train.py:300-303), 1 <= n <= SIMQ_VISUALIZATION_MAX_OUTPUTS,
+ * 1 <= channels <= SIMQ_LOCAL_MAX_CHANNELS; every problem of a call in one launch.  Problem p's image starts at float out_offset of
+ * d_out and is [96][W][3] fp32, W = 96 + 1 + 96 * n + (n - 1) (chw = 0), or [3][96][W], the transpose(2, 0, 1) of train.py:297
+ * (chw = 1).  Along a row:
+ *   columns [0, 96)            the state panel (get_state_visualization): state channels (0, 0, 0) for channels = 1, (1, 0, 0) for
+ *                              channels = 2, (1, 0, channels - 1) otherwise
+ *   column 96, and one column between two output panels: 0 (the vertical bars; none after the last panel)
+ *   output panel q = 0 .. n-1  columns [97 + 97 * q, 97 + 97 * q + 96).  With mn, mx the minimum and maximum over the WHOLE [n][96][96]
+ *                              output (scale_min_max: one pair for all channels), in fp32, every operation rounded on its own:
+ *                                d = (mx - mn) + 1e-6f;  x = (v - mn) / d  (the correctly rounded quotient, no reciprocal);
+ *                                k = (uint8) rint_half_even(255 * x)       (to_uint8_image)
+ *                                colour c: (one_minus_alpha * state[i][j][0]) + (alpha_f * jet[k][c])   (get_output_visualization)
+ *                              one_minus_alpha = (float)(1.0 - alpha) and alpha_f = (float)alpha, formed here on the host as numpy forms
+ *                              them from a python scalar; the two products and the sum are not fused.
+ * d_jet is the caller's colour map [256][3] fp32 (utils.JET); the library holds none.  Results equal the reference's bit for bit
+ * under numpy >= 2 (a python float combined with a float32 array stays float32) for finite outputs; a NaN or an infinity in an output,
+ * or a range mx - mn that overflows, is outside that claim (the reference casts a NaN to uint8 there): k is then clamped into [0, 255].
+ * `problems`: host array of n_problems descriptors, validated here before anything is copied or launched (n and channels in range,
+ * alpha finite, chw 0 or 1; every pointer non-NULL and 4-byte aligned, d_problems 8-byte; every address range below 2^63; each image
+ * inside the out_floats of d_out and no two images sharing a float; every image disjoint from every state, every output, d_jet and
+ * d_problems) and copied to the caller's device buffer d_problems (n_problems descriptors) on `stream`. */
+#define SIMQ_VISUALIZATION_MAX_OUTPUTS 4
+typedef struct simq_visualization_problem {
+    const float* d_state;       /* [96][96][channels] fp32 on the device */
+    const float* d_output;      /* [n][96][96] fp32 on the device */
+    int64_t out_offset;         /* float offset of the problem's image in d_out */
+    int32_t n, channels;
+} simq_visualization_problem;
+int simq_state_output_visualizations(const simq_visualization_problem* problems, int n_problems, simq_visualization_problem* d_problems,
+                                     const float* d_jet, double alpha, int chw, float* d_out, int64_t out_floats, void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of the GEMM-class launches ----------------
  * Between start and stop every implicit-GEMM launch (forward + dgrad; kind 0: the fp32 96x64 tile that dominates the
  * headline workload, kind 2: every other tile / precision) and every wgrad launch (kind 1) is

@@ -47,6 +47,10 @@ _LAZY = {
     'camera_geometry': ('.observation', 'camera_geometry'),
     'observation_update': ('.observation', 'observation_update'),
     'observe': ('.observation', 'observe'),
+    'state_output_visualizations': ('.visualization', 'state_output_visualizations'),
+    'state_output_visualization': ('.visualization', 'state_output_visualization'),
+    'state_visualization': ('.visualization', 'state_visualization'),
+    'jet_table': ('.visualization', 'jet_table'),
 }
 
 

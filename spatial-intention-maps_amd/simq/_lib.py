@@ -8,7 +8,7 @@ context / stream table.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 
 import torch  # noqa: F401  (must precede the CDLL: shares the HIP runtime)
 
@@ -172,6 +172,7 @@ _SIGS = {
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                     c_void_p]),
     'simq_observation_update': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'simq_state_output_visualizations': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)
