@@ -18,11 +18,9 @@
 // nothing (every edge then satisfies d[v] <= fl32(d[u] + w) with the final values), capped at rows * cols + 1 passes: a pass relaxes
 // every edge with values at least as new as one Jacobi sweep would, and rows * cols - 1 Jacobi sweeps reach the fixed point.  Hitting
 // the cap writes status 1 and stops.
-#include "common.h"
+#include "batch_abi.h"
 #include "../../include/simq.h"
 
-#include <algorithm>
-#include <utility>
 #include <vector>
 
 namespace simq {
@@ -254,7 +252,7 @@ extern "C" int simq_grid_distance_images(const uint8_t* d_grids, int64_t grids_b
     SIMQ_REQUIRE(pixels_per_meter > 0.f && pixels_per_meter <= 3.4e38f, "grid_distance_images: pixels_per_meter = %g (> 0, finite; 1 = none)",
                  (double)pixels_per_meter);
     SIMQ_REQUIRE(scale >= -3.4e38f && scale <= 3.4e38f, "grid_distance_images: scale = %g (finite; 1 = none)", (double)scale);
-    std::vector<std::pair<int64_t, int64_t>> spans;
+    std::vector<Span> spans;
     spans.reserve(n);
     for (int i = 0; i < n; ++i) {
         const simq_grid_problem& p = problems[i];
@@ -263,20 +261,19 @@ extern "C" int simq_grid_distance_images(const uint8_t* d_grids, int64_t grids_b
         SIMQ_REQUIRE(p.src_i >= 0 && p.src_i < p.rows && p.src_j >= 0 && p.src_j < p.cols,
                      "grid_distance_images: problem %d: source (%d, %d) outside its %d x %d grid", i, p.src_i, p.src_j, p.rows, p.cols);
         const int64_t cells = (int64_t)p.rows * p.cols;
-        SIMQ_REQUIRE(p.grid_offset >= 0 && p.grid_offset <= grids_bytes - cells,
+        SIMQ_REQUIRE(fits(p.grid_offset, cells, grids_bytes),
                      "grid_distance_images: problem %d: grid bytes [%lld, %lld) outside the %lld of d_grids", i, (long long)p.grid_offset,
                      (long long)(p.grid_offset + cells), (long long)grids_bytes);
-        SIMQ_REQUIRE(p.out_offset >= 0 && p.out_offset <= out_floats - cells,
+        SIMQ_REQUIRE(fits(p.out_offset, cells, out_floats),
                      "grid_distance_images: problem %d: image floats [%lld, %lld) outside the %lld of d_out", i, (long long)p.out_offset,
                      (long long)(p.out_offset + cells), (long long)out_floats);
-        spans.emplace_back(p.out_offset, p.out_offset + cells);
+        spans.push_back({(uint64_t)p.out_offset, (uint64_t)(p.out_offset + cells), i});
     }
-    std::sort(spans.begin(), spans.end());
-    for (size_t i = 1; i < spans.size(); ++i)
-        SIMQ_REQUIRE(spans[i].first >= spans[i - 1].second, "grid_distance_images: two images overlap in d_out at float %lld",
-                     (long long)spans[i].first);
+    const size_t clash = first_overlap(spans);
+    SIMQ_REQUIRE(clash == 0, "grid_distance_images: two images overlap in d_out at float %lld", (long long)spans[clash].lo);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SIMQ_CHECK_HIP(hipMemcpyAsync(d_problems, problems, sizeof(simq_grid_problem) * (size_t)n, hipMemcpyHostToDevice, s));
+    const HostBlock block = {problems, sizeof(simq_grid_problem) * (size_t)n};
+    SIMQ_CHECK_HIP(upload_descriptors(d_problems, &block, 1, nullptr, s));
     grid_distance_kernel<<<n, kLanes, 0, s>>>(d_grids, d_problems, d_out, pixels_per_meter, unreachable_to_max, scale, d_status);
     SIMQ_CHECK_LAUNCH();
     note_launch("grid_distance");

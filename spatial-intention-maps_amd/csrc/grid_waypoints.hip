@@ -17,11 +17,10 @@
 // 16-bit ring entry, the parent as a direction byte, a flag byte (bit 0 free, bit 1 queued).  The ring is laid out for window cells + 1
 // entries and uses free cells + 1 of them: at most every vertex is queued at once, and slot numbers only ever grow, so positions wrap
 // (a cluttered grid pushes 1 - 7 % more often than it has vertices).
-#include "common.h"
+#include "batch_abi.h"
 #include "../../include/simq.h"
 
 #include <algorithm>
-#include <utility>
 #include <vector>
 
 namespace simq {
@@ -272,17 +271,10 @@ __global__ void __launch_bounds__(kLanes) grid_paths_kernel(const uint8_t* __res
     }
 }
 
-struct Span {
-    int64_t lo, hi;
-    int problem;
-    bool operator<(const Span& o) const { return lo < o.lo; }
-};
-
 int disjoint(std::vector<Span>& spans, const char* what) {
-    std::sort(spans.begin(), spans.end());
-    for (size_t i = 1; i < spans.size(); ++i)
-        SIMQ_REQUIRE(spans[i].lo >= spans[i - 1].hi, "grid_paths: problems %d and %d overlap in %s at element %lld", spans[i - 1].problem,
-                     spans[i].problem, what, (long long)spans[i].lo);
+    const size_t i = first_overlap(spans);
+    SIMQ_REQUIRE(i == 0, "grid_paths: problems %d and %d overlap in %s at element %lld", spans[i - 1].problem, spans[i].problem, what,
+                 (long long)spans[i].lo);
     return 0;
 }
 
@@ -310,13 +302,13 @@ extern "C" int simq_grid_paths(const uint8_t* d_grids, int64_t grids_bytes, cons
         SIMQ_REQUIRE(p.tgt_i >= 0 && p.tgt_i < p.rows && p.tgt_j >= 0 && p.tgt_j < p.cols,
                      "grid_paths: problem %d: target (%d, %d) outside its %d x %d grid", i, p.tgt_i, p.tgt_j, p.rows, p.cols);
         const int64_t cells = (int64_t)p.rows * p.cols;
-        SIMQ_REQUIRE(p.grid_offset >= 0 && p.grid_offset <= grids_bytes - cells,
+        SIMQ_REQUIRE(fits(p.grid_offset, cells, grids_bytes),
                      "grid_paths: problem %d: grid_offset: bytes [%lld, %lld) outside the %lld of d_grids", i, (long long)p.grid_offset,
                      (long long)(p.grid_offset + cells), (long long)grids_bytes);
-        SIMQ_REQUIRE(p.thin_offset == -1 || (p.thin_offset >= 0 && p.thin_offset <= grids_bytes - cells),
+        SIMQ_REQUIRE(p.thin_offset == -1 || fits(p.thin_offset, cells, grids_bytes),
                      "grid_paths: problem %d: thin_offset: bytes [%lld, %lld) outside the %lld of d_grids (-1: no straight-line test)", i,
                      (long long)p.thin_offset, (long long)(p.thin_offset + cells), (long long)grids_bytes);
-        SIMQ_REQUIRE(p.closest_offset == -1 || (d_closest && p.closest_offset >= 0 && p.closest_offset <= closest_ints - 2 * cells),
+        SIMQ_REQUIRE(p.closest_offset == -1 || (d_closest && fits(p.closest_offset, 2 * cells, closest_ints)),
                      "grid_paths: problem %d: closest_offset: ints [%lld, %lld) outside the %lld of d_closest (-1: no snap)", i,
                      (long long)p.closest_offset, (long long)(p.closest_offset + 2 * cells), (long long)(d_closest ? closest_ints : 0));
         SIMQ_REQUIRE(p.box_rows >= 0 && p.box_cols >= 0 && p.box_i0 >= 0 && p.box_j0 >= 0 && p.box_i0 <= p.rows - p.box_rows &&
@@ -328,42 +320,44 @@ extern "C" int simq_grid_paths(const uint8_t* d_grids, int64_t grids_bytes, cons
                      "(the search state lives in LDS)", i, p.box_rows, p.box_cols, (long long)(p.box_rows + 2) * (p.box_cols + 2),
                      SIMQ_GRID_PATH_MAX_BOX_CELLS);
         SIMQ_REQUIRE(p.path_capacity >= 1, "grid_paths: problem %d: path_capacity = %d (>= 1 pair)", i, p.path_capacity);
-        SIMQ_REQUIRE(p.path_offset >= 0 && p.path_offset <= path_pairs - p.path_capacity,
+        SIMQ_REQUIRE(fits(p.path_offset, p.path_capacity, path_pairs),
                      "grid_paths: problem %d: path_offset: pairs [%lld, %lld) outside the %lld of d_paths", i, (long long)p.path_offset,
                      (long long)(p.path_offset + p.path_capacity), (long long)path_pairs);
-        path_spans.push_back({p.path_offset, p.path_offset + p.path_capacity, i});
-        SIMQ_REQUIRE(p.parents_offset == -1 || (d_parents && p.parents_offset >= 0 && p.parents_offset <= parents_ints - cells),
+        path_spans.push_back({(uint64_t)p.path_offset, (uint64_t)(p.path_offset + p.path_capacity), i});
+        SIMQ_REQUIRE(p.parents_offset == -1 || (d_parents && fits(p.parents_offset, cells, parents_ints)),
                      "grid_paths: problem %d: parents_offset: ints [%lld, %lld) outside the %lld of d_parents (-1: no parent image)", i,
                      (long long)p.parents_offset, (long long)(p.parents_offset + cells), (long long)(d_parents ? parents_ints : 0));
-        if (p.parents_offset >= 0) parent_spans.push_back({p.parents_offset, p.parents_offset + cells, i});
-        SIMQ_REQUIRE(p.dist_offset == -1 || (d_dist && p.dist_offset >= 0 && p.dist_offset <= dist_floats - cells),
+        if (p.parents_offset >= 0) parent_spans.push_back({(uint64_t)p.parents_offset, (uint64_t)(p.parents_offset + cells), i});
+        SIMQ_REQUIRE(p.dist_offset == -1 || (d_dist && fits(p.dist_offset, cells, dist_floats)),
                      "grid_paths: problem %d: dist_offset: floats [%lld, %lld) outside the %lld of d_dist (-1: no distance image)", i,
                      (long long)p.dist_offset, (long long)(p.dist_offset + cells), (long long)(d_dist ? dist_floats : 0));
-        if (p.dist_offset >= 0) dist_spans.push_back({p.dist_offset, p.dist_offset + cells, i});
+        if (p.dist_offset >= 0) dist_spans.push_back({(uint64_t)p.dist_offset, (uint64_t)(p.dist_offset + cells), i});
         lds = std::max(lds, lds_bytes(p.box_rows, p.box_cols));
     }
     if (disjoint(path_spans, "d_paths") || disjoint(parent_spans, "d_parents") || disjoint(dist_spans, "d_dist")) return -1;
 
-    // alignment, and the buffers against each other: an output may share no byte with another buffer of the call
-    struct Buf { const char* name; uintptr_t lo; int64_t bytes; bool output; int align; };
-    const Buf bufs[] = {
-        {"d_grids", (uintptr_t)d_grids, grids_bytes, false, 1},
-        {"d_closest", (uintptr_t)d_closest, d_closest ? 4 * closest_ints : 0, false, 4},
-        {"d_problems", (uintptr_t)d_problems, (int64_t)sizeof(simq_grid_path_problem) * n, true, 8},
-        {"d_paths", (uintptr_t)d_paths, 8 * path_pairs, true, 4},
-        {"d_lengths", (uintptr_t)d_lengths, 4 * (int64_t)n, true, 4},
-        {"d_endpoints", (uintptr_t)d_endpoints, 16 * (int64_t)n, true, 4},
-        {"d_parents", (uintptr_t)d_parents, d_parents ? 4 * parents_ints : 0, true, 4},
-        {"d_dist", (uintptr_t)d_dist, d_dist ? 4 * dist_floats : 0, true, 4},
-        {"d_status", (uintptr_t)d_status, 4 * (int64_t)n, true, 4},
+    // alignment, and the buffers against each other: an output may share no byte with another buffer of the call.  This walk is
+    // not batch_abi.h's first_conflict: it names the written buffer first, meets a buffer's alignment before its pairs and skips an
+    // empty buffer, and which refusal comes first when several rules are broken is part of this entry point's behaviour.
+    const Buffer bufs[] = {
+        {"d_grids", d_grids, grids_bytes, false},
+        {"d_closest", d_closest, d_closest ? 4 * closest_ints : 0, false},
+        {"d_problems", d_problems, (int64_t)sizeof(simq_grid_path_problem) * n, true},
+        {"d_paths", d_paths, 8 * path_pairs, true},
+        {"d_lengths", d_lengths, 4 * (int64_t)n, true},
+        {"d_endpoints", d_endpoints, 16 * (int64_t)n, true},
+        {"d_parents", d_parents, d_parents ? 4 * parents_ints : 0, true},
+        {"d_dist", d_dist, d_dist ? 4 * dist_floats : 0, true},
+        {"d_status", d_status, 4 * (int64_t)n, true},
     };
+    const int align[] = {1, 4, 8, 4, 4, 4, 4, 4, 4};
     const int nb = (int)(sizeof(bufs) / sizeof(bufs[0]));
     for (int a = 0; a < nb; ++a) {
-        SIMQ_REQUIRE(bufs[a].lo % bufs[a].align == 0, "grid_paths: %s is not %d-byte aligned", bufs[a].name, bufs[a].align);
+        SIMQ_REQUIRE((uintptr_t)bufs[a].p % align[a] == 0, "grid_paths: %s is not %d-byte aligned", bufs[a].name, align[a]);
         for (int b = 0; b < nb; ++b) {
-            if (a == b || !bufs[a].output || bufs[a].bytes <= 0 || bufs[b].bytes <= 0 || (bufs[b].output && b < a)) continue;
-            SIMQ_REQUIRE(bufs[a].lo + (uintptr_t)bufs[a].bytes <= bufs[b].lo || bufs[b].lo + (uintptr_t)bufs[b].bytes <= bufs[a].lo,
-                         "grid_paths: %s and %s overlap", bufs[a].name, bufs[b].name);
+            if (a == b || !bufs[a].written || bufs[a].bytes <= 0 || bufs[b].bytes <= 0 || (bufs[b].written && b < a)) continue;
+            SIMQ_REQUIRE(!overlaps(bufs[a].p, bufs[a].bytes, bufs[b].p, bufs[b].bytes), "grid_paths: %s and %s overlap", bufs[a].name,
+                         bufs[b].name);
         }
     }
     lds = (lds + 15) & ~(int64_t)15;
@@ -371,7 +365,8 @@ extern "C" int simq_grid_paths(const uint8_t* d_grids, int64_t grids_bytes, cons
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     SIMQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(grid_paths_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
-    SIMQ_CHECK_HIP(hipMemcpyAsync(d_problems, problems, sizeof(simq_grid_path_problem) * (size_t)n, hipMemcpyHostToDevice, s));
+    const HostBlock block = {problems, sizeof(simq_grid_path_problem) * (size_t)n};
+    SIMQ_CHECK_HIP(upload_descriptors(d_problems, &block, 1, nullptr, s));
     grid_paths_kernel<<<n, kLanes, (size_t)lds, s>>>(d_grids, d_closest, d_problems, d_paths, d_lengths, d_endpoints, d_parents, d_dist,
                                                      d_status, (unsigned)lds);
     SIMQ_CHECK_LAUNCH();

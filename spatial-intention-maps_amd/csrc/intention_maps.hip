@@ -17,12 +17,10 @@
 // is skipped), keeps the points inside the halo with the LDS maximum, then every lane dilates one column of the tile out of LDS and
 // writes it: consecutive lanes write consecutive floats of a row.  Every pixel of the map is written by exactly one workgroup, so the
 // caller zero-fills nothing.
-#include "common.h"
+#include "batch_abi.h"
 #include "../../include/simq.h"
 
 #include <cmath>
-#include <cstring>
-#include <vector>
 
 namespace simq {
 
@@ -114,12 +112,6 @@ __global__ void __launch_bounds__(kThreads) intention_maps_kernel(Desc d, float*
     }
 }
 
-// [a, a + na) and [b, b + nb) (bytes) share a byte
-bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 }  // namespace
 
 }  // namespace simq
@@ -175,23 +167,19 @@ extern "C" int simq_intention_maps(const simq_intention_segment* segments, int n
                      n_segments);
     }
 
-    std::vector<char> host((size_t)need_desc);
+    const HostBlock parts[2] = {{segments, sizeof(simq_intention_segment) * (size_t)n_segments},
+                                {problems, sizeof(simq_intention_problem) * (size_t)n}};
+    const char* at[2];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SIMQ_CHECK_HIP(upload_descriptors(d_desc, parts, 2, at, s));
     Desc d;
-    char* base = static_cast<char*>(d_desc);
-    const size_t seg_bytes = sizeof(simq_intention_segment) * (size_t)n_segments;
-    if (seg_bytes) std::memcpy(host.data(), segments, seg_bytes);
-    std::memcpy(host.data() + seg_bytes, problems, sizeof(simq_intention_problem) * (size_t)n);
-    d.segs = reinterpret_cast<const simq_intention_segment*>(base);
-    d.probs = reinterpret_cast<const simq_intention_problem*>(base + seg_bytes);
+    d.segs = reinterpret_cast<const simq_intention_segment*>(at[0]);
+    d.probs = reinterpret_cast<const simq_intention_problem*>(at[1]);
     d.rows = rows;
     d.cols = cols;
     d.radius = radius;
     d.tiles_i = tiles_i;
     d.tiles_j = tiles_j;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // `host` is pageable memory that dies on return: the runtime finishes a pageable host-to-device copy (staged behind the stream's earlier
-    // work) before hipMemcpyAsync returns, which is what makes this safe -- and what makes the call block the host until `stream` has drained
-    SIMQ_CHECK_HIP(hipMemcpyAsync(d_desc, host.data(), host.size(), hipMemcpyHostToDevice, s));
     intention_maps_kernel<<<(unsigned)blocks, kThreads, 0, s>>>(d, d_out);
     SIMQ_CHECK_LAUNCH();
     note_launch("intention_maps");

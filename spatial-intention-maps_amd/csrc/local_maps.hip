@@ -14,12 +14,10 @@
 // reduces the minimum of every DISTANCE channel over the 9216 pixels (wave shuffles, then LDS across the 16 waves); phase 2 walks the
 // flattened (pixel, channel) index so that consecutive lanes write consecutive floats of the NHWC image.  Robot stamps are evaluated
 // per pixel through the second rotation; no global robot map is materialised.
-#include "common.h"
+#include "batch_abi.h"
 #include "../../include/simq.h"
 
 #include <cmath>
-#include <cstring>
-#include <vector>
 
 namespace simq {
 
@@ -72,12 +70,6 @@ __device__ __forceinline__ float robot_value(const Desc& d, const simq_local_pro
     return acc;
 }
 
-// minimum that keeps a NaN, as ndarray.min() does (fminf would drop it): a map holding a NaN gives an all-NaN distance image, as in the
-// reference.  Which of +0 / -0 is the minimum of a set holding both is not fixed here (nor by numpy's vectorised min).
-__device__ __forceinline__ float min_nan(float a, float b) {
-    return a != a ? a : (b != b ? b : (b < a ? b : a));
-}
-
 __global__ void __launch_bounds__(kThreads) local_state_kernel(Desc d, float* __restrict__ out) {
     __shared__ int gidx[kPix];                    // gi * cols + gj of the local pixel, -1 outside the crop
     __shared__ float wave_min[kWaves];
@@ -111,14 +103,10 @@ __global__ void __launch_bounds__(kThreads) local_state_kernel(Desc d, float* __
             const int g = gidx[pix];
             v = min_nan(v, g >= 0 ? m[g] : 0.f);
         }
-        for (int o = 32; o >= 1; o >>= 1) v = min_nan(v, __shfl_xor(v, o, 64));
+        v = wave_reduce(v, min_nan);
         if ((tid & 63) == 0) wave_min[tid >> 6] = v;
         __syncthreads();
-        if (tid == 0) {
-            float w = wave_min[0];
-            for (int k = 1; k < kWaves; ++k) w = min_nan(w, wave_min[k]);
-            chan_min[c] = w;
-        }
+        if (tid == 0) chan_min[c] = reduce_waves(wave_min, kWaves, min_nan);
         __syncthreads();
     }
 
@@ -151,12 +139,6 @@ bool finite_rotation(const simq_local_rotation& t) {
     for (double x : t.r)
         if (!std::isfinite(x)) return false;
     return std::isfinite(t.offset[0]) && std::isfinite(t.offset[1]);
-}
-
-// [a, a + na) and [b, b + nb) (bytes) share a byte
-bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
 }
 
 }  // namespace
@@ -246,26 +228,20 @@ extern "C" int simq_local_state_images(const simq_local_map* maps, int n_maps, c
         }
     }
 
-    std::vector<char> host((size_t)need_desc);
+    const HostBlock parts[4] = {{maps, sizeof(simq_local_map) * (size_t)n_maps},
+                                {robots, sizeof(simq_local_robot) * (size_t)n_robots},
+                                {problems, sizeof(simq_local_problem) * (size_t)n},
+                                {channels, sizeof(simq_local_channel) * (size_t)n * n_channels}};
+    const char* at[4];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SIMQ_CHECK_HIP(upload_descriptors(d_desc, parts, 4, at, s));
     Desc d;
-    char* base = static_cast<char*>(d_desc);
-    size_t off = 0;
-    auto pack = [&](const void* src, size_t bytes) {
-        const char* at = base + off;
-        if (bytes) std::memcpy(host.data() + off, src, bytes);
-        off += bytes;
-        return at;
-    };
-    d.maps = reinterpret_cast<const simq_local_map*>(pack(maps, sizeof(simq_local_map) * (size_t)n_maps));
-    d.robots = reinterpret_cast<const simq_local_robot*>(pack(robots, sizeof(simq_local_robot) * (size_t)n_robots));
-    d.probs = reinterpret_cast<const simq_local_problem*>(pack(problems, sizeof(simq_local_problem) * (size_t)n));
-    d.chans = reinterpret_cast<const simq_local_channel*>(pack(channels, sizeof(simq_local_channel) * (size_t)n * n_channels));
+    d.maps = reinterpret_cast<const simq_local_map*>(at[0]);
+    d.robots = reinterpret_cast<const simq_local_robot*>(at[1]);
+    d.probs = reinterpret_cast<const simq_local_problem*>(at[2]);
+    d.chans = reinterpret_cast<const simq_local_channel*>(at[3]);
     d.masks = d_masks;
     d.C = n_channels;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // `host` is pageable memory that dies on return: the runtime finishes a pageable host-to-device copy (staged behind the stream's earlier
-    // work) before hipMemcpyAsync returns, which is what makes this safe -- and what makes the call block the host until `stream` has drained
-    SIMQ_CHECK_HIP(hipMemcpyAsync(d_desc, host.data(), host.size(), hipMemcpyHostToDevice, s));
     local_state_kernel<<<n, kThreads, 0, s>>>(d, d_out);
     SIMQ_CHECK_LAUNCH();
     note_launch("local_state");

@@ -17,12 +17,11 @@
 // no flag crosses workgroups, and there are no global atomics, no workspace and no second launch.  The second pass walks the tile with
 // consecutive lanes on consecutive pixels of a row: a pixel with a key reads its winner's id again and stores the seg, an occupancy byte
 // that was set stores 1 (plain vector stores; every writer of a byte stores the same value); everything else is left untouched.
-#include "common.h"
+#include "batch_abi.h"
 #include "../../include/simq.h"
 
 #include <algorithm>
 #include <cmath>
-#include <utility>
 #include <vector>
 
 namespace simq {
@@ -152,12 +151,6 @@ __global__ void __launch_bounds__(kThreads) observation_maps_kernel(const uint32
     }
 }
 
-// [a, a + na) and [b, b + nb) (bytes) share a byte
-bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 }  // namespace
 
 }  // namespace simq
@@ -177,7 +170,7 @@ extern "C" int simq_observation_update(const void* d_frames, int64_t frame_words
                      ((uintptr_t)d_status & 3) == 0,
                  "observation_update: d_problems must be 8-byte, d_frames, d_overhead and d_status 4-byte aligned");
     const int64_t prob_bytes = (int64_t)sizeof(simq_observation_problem) * n, status_bytes = 4LL * n;
-    std::vector<std::pair<uintptr_t, uintptr_t>> spans;                               // the bytes this launch may write, [first, second)
+    std::vector<Span> spans;                                                          // the bytes this launch may write, as addresses
     spans.reserve(2 * (size_t)n);
     int max_tiles = 1;
     for (int i = 0; i < n; ++i) {
@@ -188,19 +181,19 @@ extern "C" int simq_observation_update(const void* d_frames, int64_t frame_words
         SIMQ_REQUIRE(p.rows >= 1 && p.cols >= 1 && p.rows < kMaxSide && p.cols < kMaxSide && (int64_t)p.rows * p.cols < kMaxCells,
                      "observation_update: problem %d: maps of %d x %d (rows, cols in [1, 2^24), rows * cols < 2^28)", i, p.rows, p.cols);
         const int64_t points = (int64_t)p.height * p.width, cells = (int64_t)p.rows * p.cols;
-        SIMQ_REQUIRE(p.depth_offset >= 0 && p.depth_offset <= frame_words - points,
+        SIMQ_REQUIRE(fits(p.depth_offset, points, frame_words),
                      "observation_update: problem %d: depth words [%lld, %lld) outside the %lld of d_frames", i, (long long)p.depth_offset,
                      (long long)(p.depth_offset + points), (long long)frame_words);
-        SIMQ_REQUIRE(p.ids_offset >= 0 && p.ids_offset <= frame_words - points,
+        SIMQ_REQUIRE(fits(p.ids_offset, points, frame_words),
                      "observation_update: problem %d: id words [%lld, %lld) outside the %lld of d_frames", i, (long long)p.ids_offset,
                      (long long)(p.ids_offset + points), (long long)frame_words);
-        SIMQ_REQUIRE(p.px_offset >= 0 && p.px_offset <= frame_words - p.width && p.py_offset >= 0 && p.py_offset <= frame_words - p.height,
+        SIMQ_REQUIRE(fits(p.px_offset, p.width, frame_words) && fits(p.py_offset, p.height, frame_words),
                      "observation_update: problem %d: px words [%lld, +%d) or py words [%lld, +%d) outside the %lld of d_frames", i,
                      (long long)p.px_offset, p.width, (long long)p.py_offset, p.height, (long long)frame_words);
-        SIMQ_REQUIRE(p.overhead_offset >= 0 && p.overhead_offset <= overhead_floats - cells,
+        SIMQ_REQUIRE(fits(p.overhead_offset, cells, overhead_floats),
                      "observation_update: problem %d: overhead floats [%lld, %lld) outside the %lld of d_overhead", i,
                      (long long)p.overhead_offset, (long long)(p.overhead_offset + cells), (long long)overhead_floats);
-        SIMQ_REQUIRE(p.occupancy_offset >= 0 && p.occupancy_offset <= occupancy_bytes - cells,
+        SIMQ_REQUIRE(fits(p.occupancy_offset, cells, occupancy_bytes),
                      "observation_update: problem %d: occupancy bytes [%lld, %lld) outside the %lld of d_occupancy", i,
                      (long long)p.occupancy_offset, (long long)(p.occupancy_offset + cells), (long long)occupancy_bytes);
         bool finite = std::isfinite(p.far_near) && std::isfinite(p.far) && std::isfinite(p.far_minus_near);
@@ -210,31 +203,28 @@ extern "C" int simq_observation_update(const void* d_frames, int64_t frame_words
         SIMQ_REQUIRE(p.has_receptacle == 0 || p.has_receptacle == 1, "observation_update: problem %d: has_receptacle = %d (0 or 1)", i,
                      p.has_receptacle);
         const uintptr_t a = (uintptr_t)(d_overhead + p.overhead_offset), b = (uintptr_t)(d_occupancy + p.occupancy_offset);
-        spans.emplace_back(a, a + 4 * (uintptr_t)cells);
-        spans.emplace_back(b, b + (uintptr_t)cells);
+        spans.push_back({a, a + 4 * (uintptr_t)cells, i});
+        spans.push_back({b, b + (uintptr_t)cells, i});
         const int64_t tiles = (int64_t)((p.rows + kTileRows - 1) / kTileRows) * ((p.cols + kTileCols - 1) / kTileCols);
         max_tiles = std::max(max_tiles, (int)tiles);
     }
-    std::sort(spans.begin(), spans.end());
-    for (size_t i = 1; i < spans.size(); ++i)
-        SIMQ_REQUIRE(spans[i].first >= spans[i - 1].second,
-                     "observation_update: two maps of one launch share memory at address %p (every problem needs an overhead map and an "
-                     "occupancy map of its own: the order of two updates of one map matters)", (void*)spans[i].first);
-    const struct { const char* name; const void* p; int64_t bytes; } others[] = {
-        {"d_frames", d_frames, frame_words * 4}, {"d_problems", d_problems, prob_bytes}, {"d_status", d_status, status_bytes}};
-    for (const auto& s : spans)
-        for (const auto& o : others)
-            SIMQ_REQUIRE(!overlaps((const void*)s.first, (int64_t)(s.second - s.first), o.p, o.bytes), "observation_update: a map overlaps %s",
-                         o.name);
-    for (size_t a = 0; a < 3; ++a)
-        for (size_t b = a + 1; b < 3; ++b)
-            SIMQ_REQUIRE(!overlaps(others[a].p, others[a].bytes, others[b].p, others[b].bytes), "observation_update: %s overlaps %s",
-                         others[a].name, others[b].name);
+    const size_t clash = first_overlap(spans);
+    SIMQ_REQUIRE(clash == 0,
+                 "observation_update: two maps of one launch share memory at address %p (every problem needs an overhead map and an "
+                 "occupancy map of its own: the order of two updates of one map matters)", (void*)spans[clash].lo);
+    const Buffer others[] = {
+        {"d_frames", d_frames, frame_words * 4, false}, {"d_problems", d_problems, prob_bytes, true}, {"d_status", d_status, status_bytes, true}};
+    for (const Span& s : spans)
+        for (const Buffer& o : others)
+            SIMQ_REQUIRE(!overlaps((const void*)s.lo, (int64_t)(s.hi - s.lo), o.p, o.bytes), "observation_update: a map overlaps %s", o.name);
+    int a = 0, b = 0;
+    SIMQ_REQUIRE(!first_conflict(others, 3, &a, &b), "observation_update: %s overlaps %s", others[a].name, others[b].name);
     const int64_t blocks = (int64_t)n * max_tiles;
     SIMQ_REQUIRE(blocks <= 0x7fffffffLL, "observation_update: %d problems of up to %d tiles take %lld workgroups (at most 2^31 - 1)", n,
                  max_tiles, (long long)blocks);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SIMQ_CHECK_HIP(hipMemcpyAsync(d_problems, problems, (size_t)prob_bytes, hipMemcpyHostToDevice, s));
+    const HostBlock block = {problems, (size_t)prob_bytes};
+    SIMQ_CHECK_HIP(upload_descriptors(d_problems, &block, 1, nullptr, s));
     observation_maps_kernel<<<(unsigned)blocks, kThreads, 0, s>>>(static_cast<const uint32_t*>(d_frames), frame_words, d_problems, max_tiles,
                                                                   d_overhead, overhead_floats, d_occupancy, occupancy_bytes, d_status);
     SIMQ_CHECK_LAUNCH();

@@ -14,11 +14,9 @@
 // 65 words keeps a column walk of adjacent lanes on distinct banks).  Column passes run one lane per column, down and up; the per-pixel
 // phases run over the flat pixel index, so that consecutive lanes read consecutive LDS bytes and write consecutive elements of a row.
 // Rows, columns and row indices fit a byte because SIMQ_OCCUPANCY_MAX_DIM is 256.
-#include "common.h"
+#include "batch_abi.h"
 #include "../../include/simq.h"
 
-#include <algorithm>
-#include <utility>
 #include <vector>
 
 namespace simq {
@@ -191,12 +189,6 @@ __global__ void __launch_bounds__(kThreads) occupancy_maps_kernel(const uint8_t*
     if (tid == 0) status[blockIdx.x] = chi < 0 ? 1 : 0;
 }
 
-// [a, a + na) and [b, b + nb) (bytes) share a byte
-bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 }  // namespace
 
 }  // namespace simq
@@ -214,7 +206,7 @@ extern "C" int simq_occupancy_maps(const uint8_t* d_maps, int64_t maps_bytes, co
                  (long long)closest_ints);
     SIMQ_REQUIRE(((uintptr_t)d_problems & 7) == 0 && ((uintptr_t)d_closest & 3) == 0 && ((uintptr_t)d_status & 3) == 0,
                  "occupancy_maps: d_problems must be 8-byte, d_closest and d_status 4-byte aligned");
-    std::vector<std::pair<int64_t, int64_t>> spans;
+    std::vector<Span> spans;
     spans.reserve(n);
     for (int i = 0; i < n; ++i) {
         const simq_occupancy_problem& p = problems[i];
@@ -224,36 +216,32 @@ extern "C" int simq_occupancy_maps(const uint8_t* d_maps, int64_t maps_bytes, co
         SIMQ_REQUIRE(p.thin_radius >= 0 && p.thin_radius <= kMaxRadius, "occupancy_maps: problem %d: thin_radius = %d (0 .. %d)", i,
                      p.thin_radius, kMaxRadius);
         const int64_t cells = (int64_t)p.rows * p.cols;
-        SIMQ_REQUIRE(p.occupancy_offset >= 0 && p.occupancy_offset <= maps_bytes - cells,
+        SIMQ_REQUIRE(fits(p.occupancy_offset, cells, maps_bytes),
                      "occupancy_maps: problem %d: occupancy bytes [%lld, %lld) outside the %lld of d_maps", i, (long long)p.occupancy_offset,
                      (long long)(p.occupancy_offset + cells), (long long)maps_bytes);
-        SIMQ_REQUIRE(p.mask_offset >= 0 && p.mask_offset <= maps_bytes - cells,
+        SIMQ_REQUIRE(fits(p.mask_offset, cells, maps_bytes),
                      "occupancy_maps: problem %d: room mask bytes [%lld, %lld) outside the %lld of d_maps", i, (long long)p.mask_offset,
                      (long long)(p.mask_offset + cells), (long long)maps_bytes);
-        SIMQ_REQUIRE(p.out_offset >= 0 && p.out_offset <= cspace_bytes - cells,
+        SIMQ_REQUIRE(fits(p.out_offset, cells, cspace_bytes),
                      "occupancy_maps: problem %d: output bytes [%lld, %lld) outside the %lld of d_cspace / d_thin", i, (long long)p.out_offset,
                      (long long)(p.out_offset + cells), (long long)cspace_bytes);
         SIMQ_REQUIRE(2 * p.out_offset <= closest_ints - 2 * cells,
                      "occupancy_maps: problem %d: closest ints [%lld, %lld) outside the %lld of d_closest", i, (long long)(2 * p.out_offset),
                      (long long)(2 * p.out_offset + 2 * cells), (long long)closest_ints);
-        spans.emplace_back(p.out_offset, p.out_offset + cells);
+        spans.push_back({(uint64_t)p.out_offset, (uint64_t)(p.out_offset + cells), i});
     }
-    std::sort(spans.begin(), spans.end());
-    for (size_t i = 1; i < spans.size(); ++i)
-        SIMQ_REQUIRE(spans[i].first >= spans[i - 1].second, "occupancy_maps: two problems' outputs overlap at byte %lld",
-                     (long long)spans[i].first);
+    const size_t clash = first_overlap(spans);
+    SIMQ_REQUIRE(clash == 0, "occupancy_maps: two problems' outputs overlap at byte %lld", (long long)spans[clash].lo);
     // every buffer the launch writes against every other buffer of the call
     const int64_t prob_bytes = (int64_t)sizeof(simq_occupancy_problem) * n, status_bytes = 4LL * n;
-    const struct { const char* name; const void* p; int64_t bytes; bool written; } bufs[] = {
+    const Buffer bufs[] = {
         {"d_cspace", d_cspace, cspace_bytes, true}, {"d_thin", d_thin, cspace_bytes, true}, {"d_closest", d_closest, closest_ints * 4, true},
         {"d_status", d_status, status_bytes, true}, {"d_maps", d_maps, maps_bytes, false}, {"d_problems", d_problems, prob_bytes, true}};
-    for (size_t a = 0; a < 6; ++a)
-        for (size_t b = a + 1; b < 6; ++b)
-            if (bufs[a].written || bufs[b].written)
-                SIMQ_REQUIRE(!overlaps(bufs[a].p, bufs[a].bytes, bufs[b].p, bufs[b].bytes), "occupancy_maps: %s overlaps %s", bufs[a].name,
-                             bufs[b].name);
+    int a = 0, b = 0;
+    SIMQ_REQUIRE(!first_conflict(bufs, 6, &a, &b), "occupancy_maps: %s overlaps %s", bufs[a].name, bufs[b].name);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SIMQ_CHECK_HIP(hipMemcpyAsync(d_problems, problems, (size_t)prob_bytes, hipMemcpyHostToDevice, s));
+    const HostBlock block = {problems, (size_t)prob_bytes};
+    SIMQ_CHECK_HIP(upload_descriptors(d_problems, &block, 1, nullptr, s));
     occupancy_maps_kernel<<<n, kThreads, 0, s>>>(d_maps, maps_bytes, d_problems, d_cspace, d_thin, cspace_bytes, d_closest, closest_ints, d_status);
     SIMQ_CHECK_LAUNCH();
     note_launch("occupancy_maps");

@@ -13,7 +13,7 @@
 // Shape.  One workgroup of 1024 lanes per problem.  Phase 1 reduces the minimum and the maximum of the whole [n][96][96] output (wave
 // shuffles, then LDS across the 16 waves; no atomics, no workspace); phase 2 walks the flattened index of the image so that consecutive
 // lanes write consecutive floats, in either layout.  The colour map sits in LDS (3 KB).
-#include "common.h"
+#include "batch_abi.h"
 #include "../../include/simq.h"
 
 #include <algorithm>
@@ -34,14 +34,6 @@ constexpr int kJet = 256 * 3;
 
 // width of the image of an output with n channels: the state panel, a bar, n panels with a bar between two of them
 constexpr int image_width(int n) { return kW + 1 + kW * n + (n - 1); }
-
-// minimum / maximum that keep a NaN, as ndarray.min() / max() do: an output holding one gives NaN everywhere, and k = 0 below
-__device__ __forceinline__ float min_nan(float a, float b) {
-    return a != a ? a : (b != b ? b : (b < a ? b : a));
-}
-__device__ __forceinline__ float max_nan(float a, float b) {
-    return a != a ? a : (b != b ? b : (b > a ? b : a));
-}
 
 // to_uint8_image(scale_min_max(.)) of one value: the difference, the quotient and the product each rounded to fp32 on its own
 __device__ __forceinline__ int colour_index(float v, float mn, float d) {
@@ -77,21 +69,15 @@ __global__ void __launch_bounds__(kThreads) state_output_kernel(const simq_visua
         lo = min_nan(lo, v);
         hi = max_nan(hi, v);
     }
-    for (int o = 32; o >= 1; o >>= 1) {
-        lo = min_nan(lo, __shfl_xor(lo, o, 64));
-        hi = max_nan(hi, __shfl_xor(hi, o, 64));
-    }
+    lo = wave_reduce(lo, min_nan);                // (a NaN in the output stays: NaN everywhere, and k = 0 below)
+    hi = wave_reduce(hi, max_nan);
     if ((tid & 63) == 0) {
         wave_min[tid >> 6] = lo;
         wave_max[tid >> 6] = hi;
     }
     __syncthreads();
     if (tid == 0) {
-        float a = wave_min[0], b = wave_max[0];
-        for (int k = 1; k < kWaves; ++k) {
-            a = min_nan(a, wave_min[k]);
-            b = max_nan(b, wave_max[k]);
-        }
+        const float a = reduce_waves(wave_min, kWaves, min_nan), b = reduce_waves(wave_max, kWaves, max_nan);
         range[0] = a;
         range[1] = (b - a) + 1e-6f;
     }
@@ -129,11 +115,6 @@ __global__ void __launch_bounds__(kThreads) state_output_kernel(const simq_visua
     }
 }
 
-struct Span {
-    uintptr_t begin, end;                         // bytes [begin, end)
-    int problem;
-};
-
 }  // namespace
 
 }  // namespace simq
@@ -170,7 +151,7 @@ extern "C" int simq_state_output_visualizations(const simq_visualization_problem
         SIMQ_REQUIRE((uintptr_t)p.d_state < top && (uintptr_t)p.d_output < top,
                      "state_output_visualizations: problem %d: a buffer address is not below 2^63", i);
         const int64_t floats = (int64_t)kW * image_width(p.n) * 3;
-        SIMQ_REQUIRE(p.out_offset >= 0 && p.out_offset <= out_floats - floats,
+        SIMQ_REQUIRE(fits(p.out_offset, floats, out_floats),
                      "state_output_visualizations: problem %d: image floats [%lld, %lld) outside the %lld of d_out", i, (long long)p.out_offset,
                      (long long)(p.out_offset + floats), (long long)out_floats);
         const uintptr_t o = (uintptr_t)(d_out + p.out_offset), s = (uintptr_t)p.d_state, q = (uintptr_t)p.d_output;
@@ -180,22 +161,21 @@ extern "C" int simq_state_output_visualizations(const simq_visualization_problem
     }
     inputs.push_back({(uintptr_t)d_jet, (uintptr_t)d_jet + 4 * (uintptr_t)kJet, -1});
     inputs.push_back({(uintptr_t)d_problems, (uintptr_t)d_problems + (uintptr_t)prob_bytes, -2});
-    auto by_begin = [](const Span& a, const Span& b) { return a.begin < b.begin; };
-    std::sort(images.begin(), images.end(), by_begin);
-    for (size_t i = 1; i < images.size(); ++i)
-        SIMQ_REQUIRE(images[i].begin >= images[i - 1].end, "state_output_visualizations: the images of problems %d and %d share memory in d_out",
-                     images[i - 1].problem, images[i].problem);
+    const size_t clash = first_overlap(images);
+    SIMQ_REQUIRE(clash == 0, "state_output_visualizations: the images of problems %d and %d share memory in d_out",
+                 images[clash - 1].problem, images[clash].problem);
     // the images are sorted and disjoint: an input overlaps one of them iff it overlaps the last image that begins before the input ends
     for (const Span& in : inputs) {
-        auto it = std::lower_bound(images.begin(), images.end(), Span{in.end, 0, 0}, by_begin);
+        auto it = std::lower_bound(images.begin(), images.end(), Span{in.hi, 0, 0}, span_before);
         if (it == images.begin()) continue;
         --it;
-        SIMQ_REQUIRE(it->end <= in.begin, "state_output_visualizations: the image of problem %d overlaps %s%s", it->problem,
+        SIMQ_REQUIRE(it->hi <= in.lo, "state_output_visualizations: the image of problem %d overlaps %s%s", it->problem,
                      in.problem == -1 ? "d_jet" : (in.problem == -2 ? "d_problems" : "an input (state or output) of problem "),
                      in.problem >= 0 ? std::to_string(in.problem).c_str() : "");
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SIMQ_CHECK_HIP(hipMemcpyAsync(d_problems, problems, (size_t)prob_bytes, hipMemcpyHostToDevice, s));
+    const HostBlock block = {problems, (size_t)prob_bytes};
+    SIMQ_CHECK_HIP(upload_descriptors(d_problems, &block, 1, nullptr, s));
     state_output_kernel<<<n_problems, kThreads, 0, s>>>(d_problems, d_jet, (float)alpha, (float)(1.0 - alpha), chw, d_out);
     SIMQ_CHECK_LAUNCH();
     note_launch("state_output_visualization");

@@ -10,9 +10,9 @@ search itself and has the waypoints (``simq.WaypointGraph``, ``simq.grid_dense_p
 """
 import ctypes
 
-import numpy as np
 import torch
 
+from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
 
 
@@ -22,31 +22,19 @@ class GridProblem(ctypes.Structure):
                 ('src_i', ctypes.c_int32), ('src_j', ctypes.c_int32)]
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise SimqError('simq grid distance images need an MI355X (torch.cuda.is_available() is False); no CPU path')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _check_grid(grid, what='grid'):
-    """A 2-D C-contiguous uint8 array, as the reference's `unsigned char[:, ::1]` (numpy), or a contiguous uint8 torch tensor."""
-    if isinstance(grid, torch.Tensor):
-        if grid.dtype != torch.uint8 or grid.dim() != 2 or not grid.is_contiguous():
-            raise ValueError('%s must be a 2-D contiguous uint8 tensor, got %s %s' % (what, grid.dtype, tuple(grid.shape)))
-        return grid
-    if not isinstance(grid, np.ndarray) or grid.dtype != np.uint8 or grid.ndim != 2 or not grid.flags['C_CONTIGUOUS']:
-        desc = ('%s %s%s' % (grid.dtype, grid.shape, '' if grid.flags['C_CONTIGUOUS'] else ' non-contiguous')
-                if isinstance(grid, np.ndarray) else type(grid).__name__)
-        raise ValueError('%s must be a 2-D C-contiguous uint8 numpy array (unsigned char[:, ::1]), got %s' % (what, desc))
-    return grid
-
-
-def _pixel(px):
+def pixel(px):
     try:
         i, j = px
         return int(i), int(j)
     except (TypeError, ValueError):
         raise ValueError('a pixel is a pair (i, j), got %r' % (px,)) from None
+
+
+def index_grids(grid_index, n_grids, n_sources):
+    """grid_index of grid_distance_images / grid_dense_paths as a list of ints (problem p uses grid p when it is None)."""
+    return _batch.problem_index(grid_index, n_grids, n_sources,
+                                '%d grids but %d sources (grid_index shares grids between problems)' % (n_grids, n_sources),
+                                'grid_index must name one of the %d grids for each of the %d sources' % (n_grids, n_sources))
 
 
 def grid_distance_images(grids, sources, pixels_per_meter=None, unreachable_to_max=False, scale=None, out=None, grid_index=None):
@@ -62,38 +50,17 @@ def grid_distance_images(grids, sources, pixels_per_meter=None, unreachable_to_m
     contiguous float32 tensor of that shape on the device), otherwise a list of P [rows_p, cols_p] views into one packed buffer (`out`:
     a contiguous float32 device tensor of at least sum(rows_p * cols_p) elements).  Raises SimqError for an out-of-range source or an
     oversized grid (the library checks before it launches anything) and when a problem hit the library's pass cap."""
-    if isinstance(grids, (np.ndarray, torch.Tensor)) and grids.ndim == 3:
-        grids = list(grids)
-    grids = [_check_grid(g, 'grids[%d]' % k) for k, g in enumerate(grids)]
-    srcs = [_pixel(s) for s in sources]
+    grids, _ = _batch.as_maps(grids, 'grids')
+    srcs = [pixel(s) for s in sources]
     if not grids or not srcs:
         raise ValueError('grid_distance_images needs at least one grid and one source')
-    if grid_index is None:
-        if len(grids) != len(srcs):
-            raise ValueError('%d grids but %d sources (grid_index shares grids between problems)' % (len(grids), len(srcs)))
-        grid_index = range(len(srcs))
-    grid_index = [int(k) for k in grid_index]
-    if len(grid_index) != len(srcs) or any(k < 0 or k >= len(grids) for k in grid_index):
-        raise ValueError('grid_index must name one of the %d grids for each of the %d sources' % (len(grids), len(srcs)))
-    dev = _device()
+    grid_index = index_grids(grid_index, len(grids), len(srcs))
+    dev = _batch.device('grid distance images')
 
     # one packed uint8 buffer holding each grid the problems use once
     used = sorted(set(grid_index))
-    goff, total = {}, 0
-    for k in used:
-        goff[k] = total
-        total += grids[k].shape[0] * grids[k].shape[1]
-    packed = torch.empty(total, dtype=torch.uint8, device=dev)
-    on_dev = [k for k in used if isinstance(grids[k], torch.Tensor) and grids[k].device == dev]
-    if len(on_dev) < len(used):
-        staging = np.zeros(total, np.uint8)
-        for k in used:
-            if k not in on_dev:
-                g = grids[k].cpu().numpy() if isinstance(grids[k], torch.Tensor) else grids[k]
-                staging[goff[k]:goff[k] + g.size] = g.reshape(-1)
-        packed.copy_(torch.from_numpy(staging))
-    for k in on_dev:
-        packed[goff[k]:goff[k] + grids[k].numel()].copy_(grids[k].reshape(-1))
+    packed, offsets = _batch.pack([grids[k] for k in used], torch.uint8, dev)
+    goff = dict(zip(used, offsets))
 
     shapes = [tuple(grids[k].shape) for k in grid_index]
     uniform = len(set(shapes)) == 1
@@ -101,8 +68,7 @@ def grid_distance_images(grids, sources, pixels_per_meter=None, unreachable_to_m
     want = (len(srcs),) + shapes[0] if uniform else (n_out,)
     if out is None:
         out = torch.empty(want, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or out.numel() < n_out or \
-            (uniform and tuple(out.shape) != want):
+    elif not _batch.out_fits(out, torch.float32, dev, want if uniform else None, n_out):
         raise ValueError('out must be a contiguous float32 tensor on %s of %s' % (
             dev, 'shape %s' % (want,) if uniform else 'at least %d elements' % n_out))
     probs = (GridProblem * len(srcs))()
@@ -117,18 +83,11 @@ def grid_distance_images(grids, sources, pixels_per_meter=None, unreachable_to_m
     lib.call('simq_grid_distance_images', ptr(packed), ctypes.c_int64(packed.numel()), probs, len(srcs), ptr(d_probs), ptr(out),
              ctypes.c_int64(out.numel()), ctypes.c_float(ppm), int(bool(unreachable_to_max)), ctypes.c_float(sc), ptr(status),
              stream_ptr(dev))
-    st = status.cpu().numpy()
-    if st.any():
-        bad = np.flatnonzero(st)
+    bad, codes = _batch.bad_problems(status)
+    if bad.size:
         raise SimqError('simq_grid_distance_images: %d problem(s) did not converge (status %s at problems %s)'
-                        % (bad.size, st[bad[:8]].tolist(), bad[:8].tolist()))
-    if uniform:
-        return out
-    flat, views, o = out.view(-1), [], 0
-    for (r, c) in shapes:
-        views.append(flat[o:o + r * c].view(r, c))
-        o += r * c
-    return views
+                        % (bad.size, codes[:8].tolist(), bad[:8].tolist()))
+    return out if uniform else _batch.views(out.view(-1), shapes)
 
 
 class GridGraph:
@@ -141,13 +100,13 @@ class GridGraph:
     def __init__(self, grid):
         if isinstance(grid, torch.Tensor):
             raise ValueError('GridGraph takes a 2-D C-contiguous uint8 numpy array (unsigned char[:, ::1]), got a tensor')
-        self.grid = _check_grid(grid).copy()
+        self.grid = _batch.check_grid(grid).copy()
         self.num_rows, self.num_cols = self.grid.shape
         self.cache = {}
         self._dev_grid = None
 
     def _pixel_in_grid(self, px, what):
-        i, j = _pixel(px)
+        i, j = pixel(px)
         if not (0 <= i < self.num_rows and 0 <= j < self.num_cols):
             raise SimqError('%s (%d, %d) outside the %d x %d grid' % (what, i, j, self.num_rows, self.num_cols))
         return i, j
@@ -158,7 +117,7 @@ class GridGraph:
         todo = list(dict.fromkeys(k for k in keys if k not in self.cache))
         if todo:
             if self._dev_grid is None:
-                self._dev_grid = torch.from_numpy(self.grid).to(_device())
+                self._dev_grid = torch.from_numpy(self.grid).to(_batch.device('grid distance images'))
             imgs = grid_distance_images([self._dev_grid], todo, grid_index=[0] * len(todo))
             for k, img in zip(todo, imgs.cpu().numpy()):
                 self.cache[k] = img

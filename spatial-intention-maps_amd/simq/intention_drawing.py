@@ -18,7 +18,8 @@ import math
 
 import torch
 
-from ._lib import SimqError, lib, ptr, stream_ptr
+from . import _batch
+from ._lib import lib, ptr, stream_ptr
 from .local_maps import position_to_pixel_indices
 
 ENCODINGS = ('circle', 'ramp', 'binary', 'line', 'history')
@@ -36,12 +37,6 @@ class Segment(ctypes.Structure):
 class Problem(ctypes.Structure):
     """simq_intention_problem of include/simq.h."""
     _fields_ = [('seg_begin', ctypes.c_int32), ('seg_count', ctypes.c_int32)]
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise SimqError('simq intention maps need an MI355X (torch.cuda.is_available() is False); no CPU path')
-    return torch.device('cuda', torch.cuda.current_device())
 
 
 def _length(a, b):
@@ -148,12 +143,11 @@ def _prepare(paths, map_shape, encoding, scale, line_thickness, out):
     c_segs = (Segment * max(n_segs, 1))(*c_segs_list)
     c_probs = (Problem * P)(*[Problem(b, c) for b, c in ranges])
 
-    dev = _device()                              # (after the argument checks: those need no device)
+    dev = _batch.device('intention maps')       # (after the argument checks: those need no device)
     want = (P, rows, cols)
     if out is None:
         out = torch.empty(want, dtype=torch.float32, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or \
-            tuple(out.shape) != want:
+    elif not _batch.out_fits(out, torch.float32, dev, want):
         raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % (want, dev))
     desc_bytes = lib.c.simq_intention_desc_bytes(n_segs, P)
     d_desc = torch.empty(max(int(desc_bytes), 8), dtype=torch.uint8, device=dev)

@@ -15,6 +15,7 @@ import math
 import numpy as np
 import torch
 
+from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
 
 WIDTH = 96                       # Mapper.LOCAL_MAP_PIXEL_WIDTH (envs.py:2010)
@@ -91,24 +92,6 @@ def position_to_pixel_indices(position_x, position_y, image_shape):
     return int(np.clip(pixel_i, 0, image_shape[0] - 1)), int(np.clip(pixel_j, 0, image_shape[1] - 1))
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise SimqError('simq local state images need an MI355X (torch.cuda.is_available() is False); no CPU path')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _check_map(m, what):
-    """A 2-D C-contiguous float32 array (numpy, uploaded) or a contiguous float32 tensor (on the device: read in place)."""
-    if isinstance(m, torch.Tensor):
-        if m.dtype != torch.float32 or m.dim() != 2 or not m.is_contiguous():
-            raise ValueError('%s must be a 2-D contiguous float32 tensor, got %s %s' % (what, m.dtype, tuple(m.shape)))
-        return m
-    if not isinstance(m, np.ndarray) or m.dtype != np.float32 or m.ndim != 2:
-        raise ValueError('%s must be a 2-D float32 numpy array or tensor, got %s' % (
-            what, '%s %s' % (m.dtype, m.shape) if isinstance(m, np.ndarray) else type(m).__name__))
-    return np.ascontiguousarray(m)
-
-
 def _is_spec(x):
     return isinstance(x, str) or (isinstance(x, (tuple, list)) and len(x) >= 1 and isinstance(x[0], str))
 
@@ -161,10 +144,8 @@ def local_state_images(maps, channels, poses, robots=None, masks=None, out=None,
 def _prepare(maps, channels, poses, robots, masks, out, map_shape):
     """The argument tuple of simq_local_state_images for local_state_images' inputs, the output tensor and the device tensors the
     call reads (tools/local_maps_rate.py times the library call alone with it)."""
-    if isinstance(maps, (np.ndarray, torch.Tensor)) and maps.ndim == 3:
-        maps = list(maps)
-    dev = _device()
-    maps = [_check_map(m, 'maps[%d]' % k) for k, m in enumerate(maps)]
+    dev = _batch.device('local state images')
+    maps, _ = _batch.as_maps(maps, 'maps', _batch.check_map)      # (numpy maps are uploaded, device tensors read in place)
     poses = list(poses)
     P = len(poses)
     if P < 1:
@@ -254,8 +235,7 @@ def _prepare(maps, channels, poses, robots, masks, out, map_shape):
     want = (P, WIDTH, WIDTH, C)
     if out is None:
         out = torch.empty(want, dtype=torch.float32, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or \
-            tuple(out.shape) != want:
+    elif not _batch.out_fits(out, torch.float32, dev, want):
         raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % (want, dev))
     desc_bytes = lib.c.simq_local_state_desc_bytes(len(d_maps), n_robots, P, C)
     d_desc = torch.empty(max(int(desc_bytes), 8), dtype=torch.uint8, device=dev)

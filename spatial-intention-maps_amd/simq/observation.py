@@ -18,6 +18,7 @@ import math
 import numpy as np
 import torch
 
+from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
 
 MAX_POINTS = 1 << 22             # SIMQ_OBSERVATION_MAX_POINTS of include/simq.h
@@ -72,32 +73,11 @@ def camera_geometry(camera_position, camera_target, camera_up, near, far, aspect
     return CameraGeometry(*arrays, np.float32(far * near), np.float32(far), np.float32(far - near))
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise SimqError('simq observation maps need an MI355X (torch.cuda.is_available() is False); no CPU path')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _frames(frames, dtype, tdtype, what):
-    """The 2-D frames of a sequence or of one [P, height, width] array / tensor."""
-    if isinstance(frames, (np.ndarray, torch.Tensor)) and frames.ndim != 3:
-        raise ValueError('%s is a sequence of 2-D %s frames or one [P, height, width] array, got %d dimensions' % (what, dtype.__name__, frames.ndim))
-    try:
-        frames = list(frames)
-    except TypeError:
-        raise ValueError('%s is a sequence of 2-D %s frames or one [P, height, width] array, got %s' % (what, dtype.__name__, type(frames).__name__)) from None
-    out = []
-    for k, f in enumerate(frames):
-        if isinstance(f, torch.Tensor):
-            if f.dtype != tdtype or f.dim() != 2 or not f.is_contiguous():
-                raise ValueError('%s[%d] must be a 2-D contiguous %s tensor, got %s %s' % (what, k, dtype.__name__, f.dtype, tuple(f.shape)))
-        elif not isinstance(f, np.ndarray) or f.dtype != dtype or f.ndim != 2:
-            raise ValueError('%s[%d] must be a 2-D %s numpy array or tensor, got %s' % (
-                what, k, dtype.__name__, '%s %s' % (f.dtype, f.shape) if isinstance(f, np.ndarray) else type(f).__name__))
-        else:
-            f = np.ascontiguousarray(f)
-        out.append(f)
-    return out
+def _frames(frames, dtype, what):
+    """The 2-D frames of a sequence or of one [P, height, width] array / tensor (and as_maps' block, which the interleaved layout of
+    depth and id frames has no use for)."""
+    return _batch.as_maps(frames, what, lambda f, name: _batch.check_map(f, name, dtype),
+                          'a sequence of 2-D %s frames or one [P, height, width] array' % dtype.__name__)
 
 
 def _maps(maps, tdtype, dev, what):
@@ -129,26 +109,25 @@ def _per_problem(values, P, cls, what):
 def _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
     """The argument tuple of simq_observation_update, the status tensor and the device tensors the call reads
     (tools/observation_maps_rate.py times the upload and the library call with it)."""
-    depth = _frames(depth, np.float32, torch.float32, 'depth')
-    ids = _frames(ids, np.int32, torch.int32, 'ids')
+    depth, _ = _frames(depth, np.float32, 'depth')
+    ids, _ = _frames(ids, np.int32, 'ids')
     P = len(depth)
     if P < 1 or len(ids) != P:
         raise ValueError('observation_update needs at least one frame and as many id frames as depth frames (%d, %d)' % (P, len(ids)))
     geometries = _per_problem(geometries, P, CameraGeometry, 'geometries')
     id_ranges = _per_problem(id_ranges, P, IdRanges, 'id_ranges')
-    dev = _device()
+    dev = _batch.device('observation maps')
     overhead_maps = _maps(overhead_maps, torch.float32, dev, 'overhead_maps')
     occupancy_maps = _maps(occupancy_maps, torch.uint8, dev, 'occupancy_maps')
     if len(overhead_maps) != P or len(occupancy_maps) != P:
         raise ValueError('%d frames but %d overhead maps and %d occupancy maps' % (P, len(overhead_maps), len(occupancy_maps)))
 
-    # one buffer of 4-byte words: each distinct geometry's tables once, then the depth frames, then the id frames
-    tables, words = {}, 0
-    host = []                                    # (word offset, numpy array) of what is uploaded through one staging array
+    # one buffer of 4-byte words: each distinct geometry's tables once, then every frame's depth and ids
+    tables, words, parts = {}, 0, []
     for g in geometries:
         if id(g) not in tables:
             tables[id(g)] = (words, words + g.pixel_x.size)
-            host += [(words, np.ascontiguousarray(g.pixel_x, np.float32)), (words + g.pixel_x.size, np.ascontiguousarray(g.pixel_y, np.float32))]
+            parts += [np.ascontiguousarray(g.pixel_x, np.float32), np.ascontiguousarray(g.pixel_y, np.float32)]
             words += g.pixel_x.size + g.pixel_y.size
     offsets = []
     for p in range(P):
@@ -160,23 +139,9 @@ def _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
         if n < 1 or n > MAX_POINTS:
             raise ValueError('frame %d: %d x %d (1 .. %d points)' % (p, shape[0], shape[1], MAX_POINTS))
         offsets.append((words, words + n))
+        parts += [depth[p], ids[p]]
         words += 2 * n
-    frames = torch.empty(words, dtype=torch.int32, device=dev)
-    device_blocks = []
-    for p in range(P):
-        for o, a in zip(offsets[p], (depth[p], ids[p])):
-            if isinstance(a, torch.Tensor) and a.device == dev:
-                device_blocks.append((o, a))
-            else:
-                host.append((o, a.cpu().numpy() if isinstance(a, torch.Tensor) else a))
-    lo = min(o for o, a in host)
-    hi = max(o + a.size for o, a in host)
-    staging = np.zeros(hi - lo, np.int32)
-    for o, a in host:
-        staging[o - lo:o - lo + a.size] = a.reshape(-1).view(np.int32)
-    frames[lo:hi].copy_(torch.from_numpy(staging))
-    for o, a in device_blocks:                   # (after the staging copy, whose span may cover them)
-        frames[o:o + a.numel()].copy_(a.reshape(-1).view(torch.int32))
+    frames, _ = _batch.pack(parts, torch.int32, dev)
 
     # the maps where they are: offsets from the lowest address of each kind
     base_o = min(m.data_ptr() for m in overhead_maps)
@@ -230,21 +195,20 @@ def observation_update(depth, ids, geometries, id_ranges, overhead_maps, occupan
     not finite: their maps are unchanged, every other problem of the call is updated."""
     args, status, keep = _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps)
     lib.call('simq_observation_update', *args)
-    st = status.cpu().numpy()
+    bad, codes = _batch.bad_problems(status)
     del keep
-    if st.any():
-        bad = np.flatnonzero(st)
-        if (st[bad] == 1).all():
+    if bad.size:
+        if (codes == 1).all():
             raise SimqError('simq_observation_update: %d frame(s) hold a point that is not finite (a depth buffer outside what the near and far '
                             'planes allow); their maps are unchanged (problems %s)' % (bad.size, bad[:8].tolist()))
-        raise SimqError('simq_observation_update: %d problem(s) failed (status %s at problems %s)' % (bad.size, st[bad[:8]].tolist(), bad[:8].tolist()))
+        raise SimqError('simq_observation_update: %d problem(s) failed (status %s at problems %s)' % (bad.size, codes[:8].tolist(), bad[:8].tolist()))
     return overhead_maps, occupancy_maps
 
 
 def observe(depth, ids, geometry, id_ranges, overhead_map, occupancy_map):
     """Mapper.update for one frame and one pair of numpy maps (float32 and uint8 [rows, cols]): returns the two updated arrays, the
     arguments are left as they are."""
-    dev = _device()
+    dev = _batch.device('observation maps')
     for m, dtype, what in ((overhead_map, np.float32, 'overhead_map'), (occupancy_map, np.uint8, 'occupancy_map')):
         if not isinstance(m, np.ndarray) or m.dtype != dtype or m.ndim != 2:
             raise ValueError('%s must be a 2-D %s numpy array' % (what, dtype.__name__))

@@ -13,8 +13,8 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
-from .grid_paths import _check_grid
 
 MAX_DIM = 256                    # SIMQ_OCCUPANCY_MAX_DIM of include/simq.h
 MAX_RADIUS = 16                  # SIMQ_OCCUPANCY_MAX_RADIUS
@@ -28,26 +28,7 @@ class OccupancyProblem(ctypes.Structure):
                 ('rows', ctypes.c_int32), ('cols', ctypes.c_int32), ('radius', ctypes.c_int32), ('thin_radius', ctypes.c_int32)]
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise SimqError('simq occupancy maps need an MI355X (torch.cuda.is_available() is False); no CPU path')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _maps(maps, what):
-    """The 2-D maps of a sequence or of one [G, rows, cols] array / tensor, and that array itself when it is one contiguous block
-    (uploaded with one copy instead of G)."""
-    whole = None
-    if isinstance(maps, (np.ndarray, torch.Tensor)):
-        if maps.ndim != 3:
-            raise ValueError('%s is a sequence of 2-D uint8 maps or one [G, rows, cols] array, got %d dimensions' % (what, maps.ndim))
-        if maps.is_contiguous() if isinstance(maps, torch.Tensor) else maps.flags['C_CONTIGUOUS']:
-            whole = maps
-    try:
-        maps = list(maps)
-    except TypeError:
-        raise ValueError('%s is a sequence of 2-D uint8 maps or one [G, rows, cols] array, got %s' % (what, type(maps).__name__)) from None
-    return [_check_grid(m, '%s[%d]' % (what, k)) for k, m in enumerate(maps)], whole
+MAPS = 'a sequence of 2-D uint8 maps or one [G, rows, cols] array'
 
 
 def _radii(radius, P, what):
@@ -61,28 +42,6 @@ def _radii(radius, P, what):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= MAX_RADIUS:
             raise ValueError('%s = %r (a whole number in 0 .. %d)' % (what, v, MAX_RADIUS))
     return [int(v) for v in values]
-
-
-def _size(a):
-    return a.numel() if isinstance(a, torch.Tensor) else a.size
-
-
-def _upload(packed, blocks, dev):
-    """Copy the (byte offset, array) `blocks` into the packed device buffer: the device tensors with a device copy each, the rest
-    through one staging array."""
-    host = [(o, a) for o, a in blocks if not (isinstance(a, torch.Tensor) and a.device == dev)]
-    if host:
-        # one staging copy covering the host arrays' span (device-resident maps inside the span are written after it)
-        lo = min(o for o, a in host)
-        hi = max(o + _size(a) for o, a in host)
-        staging = np.zeros(hi - lo, np.uint8)
-        for o, a in host:
-            a = a.cpu().numpy() if isinstance(a, torch.Tensor) else a
-            staging[o - lo:o - lo + a.size] = a.reshape(-1)
-        packed[lo:hi].copy_(torch.from_numpy(staging))
-    for o, a in blocks:
-        if isinstance(a, torch.Tensor) and a.device == dev:
-            packed[o:o + a.numel()].copy_(a.reshape(-1))
 
 
 def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, out=None):
@@ -102,39 +61,29 @@ def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, 
 
     Raises ValueError for a wrong dtype, rank or contiguity, SimqError for what the library refuses (launching nothing) and for the
     problems whose configuration space has no free cell (their closest cells are undefined)."""
-    occupancy, occupancy_block = _maps(occupancy, 'occupancy')
-    room_masks, _ = _maps(room_masks, 'room_masks')
+    occupancy, occupancy_block = _batch.as_maps(occupancy, 'occupancy', expects=MAPS)
+    room_masks, _ = _batch.as_maps(room_masks, 'room_masks', expects=MAPS)
     P = len(occupancy)
     if P < 1 or not room_masks:
         raise ValueError('occupancy_maps needs at least one occupancy map and one room mask')
-    if room_index is None:
-        if len(room_masks) != P:
-            raise ValueError('%d occupancy maps but %d room masks (room_index shares masks between problems)' % (P, len(room_masks)))
-        room_index = range(P)
-    room_index = [int(k) for k in room_index]
-    if len(room_index) != P or any(k < 0 or k >= len(room_masks) for k in room_index):
-        raise ValueError('room_index must name one of the %d room masks for each of the %d occupancy maps' % (len(room_masks), P))
+    room_index = _batch.problem_index(
+        room_index, len(room_masks), P, '%d occupancy maps but %d room masks (room_index shares masks between problems)' % (P, len(room_masks)),
+        'room_index must name one of the %d room masks for each of the %d occupancy maps' % (len(room_masks), P))
     shapes = [tuple(m.shape) for m in occupancy]
     for p, k in enumerate(room_index):
         if tuple(room_masks[k].shape) != shapes[p]:
             raise ValueError('occupancy[%d] is %s but its room mask room_masks[%d] is %s' % (p, shapes[p], k, tuple(room_masks[k].shape)))
     radii, thin_radii = _radii(radius, P, 'radius'), _radii(thin_radius, P, 'thin_radius')
-    dev = _device()                              # (after the argument checks: those need no device)
+    dev = _batch.device('occupancy maps')       # (after the argument checks: those need no device)
 
-    # one packed uint8 buffer: the occupancy maps, then each room mask the problems use once
+    # one packed uint8 buffer: the occupancy maps (one contiguous block with one copy), then each room mask the problems use once
     used = sorted(set(room_index))
-    offsets, total = [], 0
+    offsets, n_cells = [], 0
     for r, c in shapes:
-        offsets.append(total)
-        total += r * c
-    n_cells = total
-    moff = {}
-    for k in used:
-        moff[k] = total
-        total += room_masks[k].shape[0] * room_masks[k].shape[1]
-    packed = torch.empty(total, dtype=torch.uint8, device=dev)
-    blocks = [(0, occupancy_block)] if occupancy_block is not None else list(zip(offsets, occupancy))
-    _upload(packed, blocks + [(moff[k], room_masks[k]) for k in used], dev)
+        offsets.append(n_cells)
+        n_cells += r * c
+    packed, at = _batch.pack(([occupancy_block] if occupancy_block is not None else occupancy) + [room_masks[k] for k in used], torch.uint8, dev)
+    moff = dict(zip(used, at[len(at) - len(used):]))
 
     uniform = len(set(shapes)) == 1
     want = [(P,) + shapes[0], (P,) + shapes[0], (P, 2) + shapes[0]] if uniform else [(n_cells,), (n_cells,), (2 * n_cells,)]
@@ -150,8 +99,7 @@ def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, 
         if len(out) != 3:
             raise ValueError('out must be three tensors (%s)' % ', '.join(names))
         for t, w, d, name in zip(out, want, dtypes, names):
-            if not isinstance(t, torch.Tensor) or t.dtype != d or t.device != dev or not t.is_contiguous() or \
-                    (tuple(t.shape) != w if uniform else t.numel() < w[0]):
+            if not _batch.out_fits(t, d, dev, w if uniform else None, w[0]):
                 raise ValueError('out: %s must be a contiguous %s tensor on %s of %s' % (
                     name, str(d).replace('torch.', ''), dev, 'shape %s' % (w,) if uniform else 'at least %d elements' % w[0]))
     probs = (OccupancyProblem * P)(*[OccupancyProblem(offsets[p], moff[room_index[p]], offsets[p], shapes[p][0], shapes[p][1], radii[p],
@@ -160,23 +108,16 @@ def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, 
     status = torch.empty(P, dtype=torch.int32, device=dev)
     lib.call('simq_occupancy_maps', ptr(packed), ctypes.c_int64(packed.numel()), probs, P, ptr(d_probs), ptr(out[0]), ptr(out[1]),
              ctypes.c_int64(min(out[0].numel(), out[1].numel())), ptr(out[2]), ctypes.c_int64(out[2].numel()), ptr(status), stream_ptr(dev))
-    st = status.cpu().numpy()
-    if st.any():
-        bad = np.flatnonzero(st)
-        blocked = bad[st[bad] == 1]
-        if blocked.size == bad.size:
+    bad, codes = _batch.bad_problems(status)
+    if bad.size:
+        if (codes == 1).all():
             raise SimqError('simq_occupancy_maps: the configuration space of %d problem(s) has no free cell, their closest cells are '
                             'undefined (problems %s)' % (bad.size, bad[:8].tolist()))
-        raise SimqError('simq_occupancy_maps: %d problem(s) failed (status %s at problems %s)' % (bad.size, st[bad[:8]].tolist(), bad[:8].tolist()))
+        raise SimqError('simq_occupancy_maps: %d problem(s) failed (status %s at problems %s)' % (bad.size, codes[:8].tolist(), bad[:8].tolist()))
     if uniform:
         return OccupancyMaps(*out)
-    flat = [t.view(-1) for t in out]
-    views = ([], [], [])
-    for o, (r, c) in zip(offsets, shapes):
-        views[0].append(flat[0][o:o + r * c].view(r, c))
-        views[1].append(flat[1][o:o + r * c].view(r, c))
-        views[2].append(flat[2][2 * o:2 * o + 2 * r * c].view(2, r, c))
-    return OccupancyMaps(*views)
+    return OccupancyMaps(_batch.views(out[0].view(-1), shapes), _batch.views(out[1].view(-1), shapes),
+                         _batch.views(out[2].view(-1), [(2,) + s for s in shapes]))
 
 
 def configuration_space(occupancy_map, room_mask, radius, thin_radius):

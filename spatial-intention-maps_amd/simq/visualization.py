@@ -13,6 +13,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
 
 WIDTH = 96                       # Mapper.LOCAL_MAP_PIXEL_WIDTH (envs.py:2010)
@@ -42,12 +43,6 @@ def jet_table():
 
 
 _JET = {}                        # device -> the reference's table there (uploaded once)
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise SimqError('simq visualisations need an MI355X (torch.cuda.is_available() is False); no CPU path')
-    return torch.device('cuda', torch.cuda.current_device())
 
 
 def _on_device(x, dev, what, rank):
@@ -88,7 +83,7 @@ def _jet_on(jet, dev):
 def _prepare(states, outputs, jet, alpha, chw, out):
     """The argument tuple of simq_state_output_visualizations, the images it will hold and the device tensors the call reads
     (tools/visualization_rate.py times the library call alone with it)."""
-    dev = _device()
+    dev = _batch.device('visualisations')
     states = _rows(states, dev, 'states', 3)
     outputs = _rows(outputs, dev, 'outputs', 3)
     P = len(states)
@@ -108,14 +103,10 @@ def _prepare(states, outputs, jet, alpha, chw, out):
     uniform = all(sh == shapes[0] for sh in shapes)
     if out is None:
         out = torch.empty(offset, dtype=torch.float32, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or out.numel() < offset:
+    elif not _batch.out_fits(out, torch.float32, dev, at_least=offset):
         raise ValueError('out must be a contiguous float32 tensor of at least %d elements on %s' % (offset, dev))
     flat = out.view(-1)
-    images, at = [], 0
-    for sh in shapes:
-        images.append(flat[at:at + sh[0] * sh[1] * sh[2]].view(sh))
-        at += sh[0] * sh[1] * sh[2]
-    result = flat[:offset].view((P,) + shapes[0]) if uniform else images
+    result = flat[:offset].view((P,) + shapes[0]) if uniform else _batch.views(flat, shapes)
     jet = _jet_on(jet, dev)
     d_probs = torch.empty(ctypes.sizeof(VisualizationProblem) * P, dtype=torch.uint8, device=dev)
     args = (probs, P, ptr(d_probs), ptr(jet), ctypes.c_double(float(alpha)), int(bool(chw)), ptr(out), ctypes.c_int64(out.numel()),
@@ -153,6 +144,6 @@ def state_output_visualization(state, output):
 def state_visualization(state):
     """Drop-in for utils.get_state_visualization (utils.py:103-108): the float32 [96, 96, 3] numpy panel of one state -- the first 96
     columns of the image the kernel draws for it (with an output of zeros)."""
-    dev = _device()
+    dev = _batch.device('visualisations')
     image = state_output_visualizations([state], [torch.zeros((1, WIDTH, WIDTH), dtype=torch.float32, device=dev)])
     return np.ascontiguousarray(image[0, :, :WIDTH].cpu().numpy())

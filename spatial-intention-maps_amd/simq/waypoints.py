@@ -14,8 +14,9 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
-from .grid_paths import GridGraph, _check_grid, _device, _pixel
+from .grid_paths import GridGraph, index_grids, pixel
 from .local_maps import PIXELS_PER_METER, position_to_pixel_indices
 
 MAX_BOX_CELLS = 20000            # SIMQ_GRID_PATH_MAX_BOX_CELLS of include/simq.h
@@ -91,32 +92,12 @@ def prune(grid, dense, simplify):
     return [(int(q[0]), int(q[1])) for q in path[::-1]]
 
 
-def _as_list(maps, what, check=_check_grid):
-    if isinstance(maps, (np.ndarray, torch.Tensor)) and maps.ndim == 3:
-        maps = list(maps)
-    return [check(m, '%s[%d]' % (what, k)) for k, m in enumerate(maps)]
-
-
 def _check_closest(c, what):
     ok = isinstance(c, (np.ndarray, torch.Tensor)) and c.ndim == 3 and c.shape[0] == 2 and \
         (c.dtype == torch.int32 and c.is_contiguous() if isinstance(c, torch.Tensor) else c.dtype == np.int32 and c.flags['C_CONTIGUOUS'])
     if not ok:
         raise ValueError('%s must be a contiguous int32 [2, rows, cols] array or tensor (closest_cspace_indices)' % what)
     return c
-
-
-def _pack(items, used, dtype, dev):
-    """One device buffer holding items[k] for k in used, and {k: element offset} (offsets kept multiples of 16 elements)."""
-    off, total = {}, 0
-    for k in used:
-        off[k] = total
-        n = int(np.prod(items[k].shape))
-        total += (n + 15) // 16 * 16
-    buf = torch.zeros(max(total, 1), dtype=dtype, device=dev)
-    for k in used:
-        t = items[k] if isinstance(items[k], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(items[k]))
-        buf[off[k]:off[k] + t.numel()].copy_(t.reshape(-1))
-    return buf, off
 
 
 def _boxes(grids, used, dev):
@@ -186,23 +167,17 @@ def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, di
 
     The search state lives in LDS over the bounding box of the grid's free cells: a box of more than MAX_BOX_CELLS cells with its
     one-cell halo is refused (SimqError, nothing launched).  A path longer than the first buffer is fetched with one more launch."""
-    grids = _as_list(grids, 'grids')
-    srcs, tgts = [_pixel(s) for s in sources], [_pixel(t) for t in targets]
+    grids, _ = _batch.as_maps(grids, 'grids')
+    srcs, tgts = [pixel(s) for s in sources], [pixel(t) for t in targets]
     if not grids or not srcs:
         raise ValueError('grid_dense_paths needs at least one grid and one source')
     if len(srcs) != len(tgts):
         raise ValueError('%d sources but %d targets' % (len(srcs), len(tgts)))
-    if grid_index is None:
-        if len(grids) != len(srcs):
-            raise ValueError('%d grids but %d sources (grid_index shares grids between problems)' % (len(grids), len(srcs)))
-        grid_index = range(len(srcs))
-    grid_index = [int(k) for k in grid_index]
-    if len(grid_index) != len(srcs) or any(k < 0 or k >= len(grids) for k in grid_index):
-        raise ValueError('grid_index must name one of the %d grids for each of the %d sources' % (len(grids), len(srcs)))
+    grid_index = index_grids(grid_index, len(grids), len(srcs))
     if thin is not None:
-        thin = _as_list(thin, 'thin')
+        thin, _ = _batch.as_maps(thin, 'thin')
     if closest is not None:
-        closest = _as_list(closest, 'closest', _check_closest)
+        closest, _ = _batch.as_maps(closest, 'closest', _check_closest)
     used = sorted(set(grid_index))
     for name, extra in (('thin', thin), ('closest', closest)):
         if extra is not None:
@@ -211,18 +186,22 @@ def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, di
             for k in used:
                 if tuple(extra[k].shape[-2:]) != tuple(grids[k].shape):
                     raise ValueError('%s[%d] is %s but grids[%d] is %s' % (name, k, tuple(extra[k].shape), k, tuple(grids[k].shape)))
-    dev = _device()
+    dev = _batch.device('grid distance images')
 
-    G = len(grids)
-    packed, goff = _pack(list(grids) + (list(thin) if thin is not None else []), used + ([G + k for k in used] if thin is not None else []),
-                         torch.uint8, dev)
-    closest_buf, coff = _pack(closest, used, torch.int32, dev) if closest is not None else (None, {})
+    # the grids the problems use, then their thin maps, in one uint8 buffer; offsets kept multiples of 16 elements (the kernel reads a
+    # grid 16 bytes at a time where it is aligned)
+    packed, offsets = _batch.pack([grids[k] for k in used] + ([thin[k] for k in used] if thin is not None else []), torch.uint8, dev, align=16)
+    goff, toff = dict(zip(used, offsets)), dict(zip(used, offsets[len(used):]))
+    closest_buf, coff = None, {}
+    if closest is not None:
+        closest_buf, offsets = _batch.pack([closest[k] for k in used], torch.int32, dev, align=16)
+        coff = dict(zip(used, offsets))
     boxes = _boxes(grids, used, dev)
     descs = []
     for k, s, t in zip(grid_index, srcs, tgts):
         rows, cols = grids[k].shape
         box = boxes[k]
-        descs.append(dict(grid=goff[k], thin=goff[G + k] if thin is not None else -1, closest=coff.get(k, -1), rows=rows, cols=cols, src=s,
+        descs.append(dict(grid=goff[k], thin=toff.get(k, -1), closest=coff.get(k, -1), rows=rows, cols=cols, src=s,
                           tgt=t, box=box, capacity=max(1, min(box[2] * box[3], 2 * (box[2] + box[3]) + 8))))
     paths, lengths, status, ends, par, dist = _launch(dev, packed, closest_buf, descs, parents, distances)
     _raise_for(status)
@@ -241,21 +220,15 @@ def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, di
             out[p] = host2[o:o + n].copy()
             o += int(lengths[p])
             status[p] = TRACED
-    views = [None, None]
-    for h, flat in enumerate((par, dist)):
-        if flat is not None:
-            views[h], o = [], 0
-            for d in descs:
-                views[h].append(flat[o:o + d['rows'] * d['cols']].view(d['rows'], d['cols']))
-                o += d['rows'] * d['cols']
-    return DensePaths(out, status, ends, views[0], views[1])
+    shapes = [(d['rows'], d['cols']) for d in descs]
+    return DensePaths(out, status, ends, *[None if flat is None else _batch.views(flat, shapes) for flat in (par, dist)])
 
 
 def _raise_for(status, allow_capacity=True):
-    bad = np.flatnonzero((status != TRACED) & (status != STRAIGHT) & ((status != CAPACITY) | (not allow_capacity)))
+    bad, codes = _batch.bad_problems(status, (TRACED, STRAIGHT, CAPACITY) if allow_capacity else (TRACED, STRAIGHT))
     if bad.size:
         raise SimqError('simq_grid_paths: %d problem(s) failed (status %s at problems %s; 2: a free cell outside the declared box or a '
-                        'closest cell outside the grid, 3: path buffer, 4: pop cap)' % (bad.size, status[bad[:8]].tolist(), bad[:8].tolist()))
+                        'closest cell outside the grid, 3: path buffer, 4: pop cap)' % (bad.size, codes[:8].tolist(), bad[:8].tolist()))
 
 
 class WaypointGraph(GridGraph):
@@ -279,7 +252,7 @@ class WaypointGraph(GridGraph):
                 dist, par = self.search(self.grid, source)
             else:
                 if self._dev_grid is None:
-                    self._dev_grid = torch.from_numpy(self.grid).to(_device())
+                    self._dev_grid = torch.from_numpy(self.grid).to(_batch.device('grid distance images'))
                 got = grid_dense_paths([self._dev_grid], [source], [source], parents=True, distances=True)
                 par, dist = got.parents[0].cpu().numpy(), got.distances[0].cpu().numpy()
             self.parents[source] = np.asarray(par, np.int32)
@@ -308,17 +281,12 @@ def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positi
     skimage.measure.approximate_polygon) and pruning run on the host, over the free-cell boxes of the maps that had a problem that was
     not straight -- nothing else of a configuration space is downloaded.  Returns P lists of positions: the two given tuples when the
     line is clear or the path has fewer than two waypoints, otherwise (x, y, 0) tuples with the given tuples at both ends."""
-    maps = _as_list(cspace, 'cspace')
+    maps, _ = _batch.as_maps(cspace, 'cspace')
     P = len(source_positions)
     if len(target_positions) != P or P < 1:
         raise ValueError('%d source positions but %d target positions' % (P, len(target_positions)))
-    if map_index is None:
-        if len(maps) != P:
-            raise ValueError('%d maps but %d positions (map_index shares maps between problems)' % (len(maps), P))
-        map_index = range(P)
-    map_index = [int(k) for k in map_index]
-    if len(map_index) != P or any(k < 0 or k >= len(maps) for k in map_index):
-        raise ValueError('map_index must name one of the %d maps for each of the %d positions' % (len(maps), P))
+    map_index = _batch.problem_index(map_index, len(maps), P, '%d maps but %d positions (map_index shares maps between problems)' % (len(maps), P),
+                                     'map_index must name one of the %d maps for each of the %d positions' % (len(maps), P))
     srcs = [position_to_pixel_indices(s[0], s[1], tuple(maps[k].shape)) for s, k in zip(source_positions, map_index)]
     tgts = [position_to_pixel_indices(t[0], t[1], tuple(maps[k].shape)) for t, k in zip(target_positions, map_index)]
     got = grid_dense_paths(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest)

@@ -349,7 +349,7 @@ def test_python_rejects_bad_input_before_touching_a_device(L, monkeypatch):
         args = dict(dict(paths=[[path]], map_shape=(184, 232), encoding='ramp'), **kw)
         with pytest.raises((ValueError, TypeError)):
             simq.intention_maps(**args)
-    monkeypatch.setattr(im, '_device', lambda: torch.device('cpu'))
+    monkeypatch.setattr(im._batch, 'device', lambda what: torch.device('cpu'))
     with pytest.raises(ValueError, match='out'):
         simq.intention_maps([[path]], (184, 232), 'ramp', out=torch.zeros(1, 184, 231))
     with pytest.raises(ValueError, match='out'):

@@ -278,7 +278,7 @@ def test_python_rejects_bad_input_before_touching_a_device(L, monkeypatch):
     with pytest.raises(L.SimqError, match='MI355X'):
         simq.local_distance_map(good, (0.0, 0.0), 0.0)
     # the input contract (checked with a stand-in device so that the checks are reached)
-    monkeypatch.setattr(lm, '_device', lambda: torch.device('cpu'))
+    monkeypatch.setattr(lm._batch, 'device', lambda what: torch.device('cpu'))
     for bad in (good.astype(np.float64), good.astype(np.uint8), np.zeros(5, np.float32), good.tolist(), torch.zeros(184, 232, dtype=torch.float64)):
         with pytest.raises(ValueError):
             simq.local_state_images([bad], [('map', 0)], [pose])

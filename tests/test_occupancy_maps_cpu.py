@@ -298,7 +298,7 @@ def test_python_rejects_bad_input_before_touching_a_device(L, monkeypatch):
         args = dict(dict(occupancy=[occ], room_masks=[mask], radius=6, thin_radius=3), **kw)
         with pytest.raises(ValueError):
             simq.occupancy_maps(**args)
-    monkeypatch.setattr(om, '_device', lambda: torch.device('cpu'))
+    monkeypatch.setattr(om._batch, 'device', lambda what: torch.device('cpu'))
     good = [torch.zeros(1, 6, 9, dtype=torch.uint8), torch.zeros(1, 6, 9, dtype=torch.uint8), torch.zeros(1, 2, 6, 9, dtype=torch.int32)]
     for k, bad in ((0, torch.zeros(1, 6, 8, dtype=torch.uint8)), (1, torch.zeros(1, 6, 9, dtype=torch.float32)), (2, torch.zeros(1, 6, 9, dtype=torch.int32)),
                    (2, torch.zeros(1, 2, 6, 9, dtype=torch.int64)), (0, torch.zeros(1, 6, 18, dtype=torch.uint8)[:, :, ::2]), (1, np.zeros((1, 6, 9), np.uint8))):
