@@ -144,10 +144,16 @@ typedef struct simq_plan_options {
     /* Round 6: fp32 plans -- which matrix pipe contracts the transform-domain GEMMs of the Winograd layers (forward, dgrad, weight gradient) */
     int gemm_split;               /* 1.  0 = v_mfma_f32_16x16x4_f32 on the fp32 operands (the fp32 FMA chain of rounds 1-5).
                                    * 1 = the bf16 matrix cores through an EXACT three-way split of both fp32 operands (v = v0 + v1 + v2 in bf16
-                                   * pieces, no bit dropped) and the six partial products down to 2^-24 of the product, fp32 accumulate
-                                   * (gemm_split3.hip): fp32 operands, fp32 accumulators, fp32 output, fp32-level round-off (measured against fp64
-                                   * beside form 0, tests/test_gpu_ops.py) at 6/16 of the matrix-pipe time.  Changes the round-off of those
-                                   * contractions (summation order and the dropped sub-ulp terms), nothing else. */
+                                   * pieces cut by truncation, no bit dropped) and SIX of the nine piece products, fp32 accumulate
+                                   * (gemm_split3.hip): fp32 operands, fp32 accumulators, fp32 output, at 6/16 of the matrix-pipe time.  The
+                                   * split is exact; the product is not: the three dropped piece products (a1 b2 + a2 b1 + a2 b2) are bounded
+                                   * by 2^-21 |a b| per product (about 4 fp32 ulp, reached by mantissas 0x00FFFF), carry the product's sign --
+                                   * a bias towards zero, not zero-mean round-off -- and average about 2^-24.6 |a b| on random mantissas.  On
+                                   * randn operands the rms error against fp64 is 0.85 x form 0's (tests/test_gpu_ops.py); the kept terms,
+                                   * the bound and the bias are pinned by tests/test_gpu_split3.py against tests/split3_oracle.py.  Bit-exact
+                                   * statements hold while every piece is at least 2^-126 in magnitude (operands from about 2^-103 up; what
+                                   * happens below: DESIGN.md 4).  An Inf operand yields NaN (Inf - Inf in the split), not +-Inf as form 0.
+                                   * Changes the round-off of those contractions (summation order and the dropped terms), nothing else. */
 } simq_plan_options;
 void simq_plan_options_default(simq_plan_options* options);
 int simq_plan_create_opts(int num_input_channels, int num_output_channels, int precision, const simq_plan_options* options,

@@ -7,13 +7,23 @@
 // kernel already runs at 0.83 of that rate on its marginal flop (profiles/r05_gemm_batched_probe.txt).  The bf16 matrix pipe of the same
 // CU is 16 x faster.  An fp32 value has 24 significant bits, a bf16 value 8, and the two formats share their exponent range, so
 //       v = v0 + v1 + v2,   v0 = trunc_bf16(v),  v1 = trunc_bf16(v - v0),  v2 = v - v0 - v1      (every subtraction exact, v2 a bf16 value)
-// holds EXACTLY for every finite fp32 v (down to 2^-109: below it the last piece underflows to zero, an error below 2^-133), and every
-// product of two pieces is exact in fp32 (8 x 8 significant bits).  a*b = sum_ij a_i*b_j; the three terms with i + j >= 3 are below
-// 2^-24 |a*b| -- half an fp32 ulp of the product, i.e. below what ONE rounding of the fp32 FMA chain loses -- so six bf16 MFMAs
+// holds EXACTLY for every fp32 v of magnitude >= 2^-110 (below it the bits under 2^-133 are lost), and every product of two pieces is exact
+// in fp32 (8 x 8 significant bits).  THE SPLIT IS EXACT, THE PRODUCT IS NOT: a*b = sum_ij a_i*b_j has nine piece products and six bf16 MFMAs
 //       a0b0 + (a0b1 + a1b0) + (a0b2 + a1b1 + a2b0),         smallest terms first, all into the fp32 accumulator of the matrix core,
-// reproduce the fp32 contraction to fp32 round-off (measured against fp64 beside the fp32-MFMA kernel: tests/test_gpu_ops.py,
-// tools/gemm_batched_probe.py) at 6/16 of its matrix-pipe time.  Nothing is stored in reduced precision: operands are read as fp32 and
-// split while they are staged into LDS, the accumulators and the output are fp32.
+// keep the six with i + j <= 2.  The split truncates, so |a1| < 2^-7 |a|, |a2| < 2^-15 |a| and every piece carries a's sign: the three
+// dropped products a1b2 + a2b1 + a2b2 are bounded by (2^-21 + 2^-30) |a*b| per product -- about 4 fp32 ulp of it, reached (0.97 2^-21) by
+// mantissas 0x00FFFF = 1 + 2^-7 - 2^-23 -- and have the product's sign: a one-signed bias towards zero, about 2^-24.6 |a*b| on average over
+// random mantissas, not zero-mean round-off.  Closing it would take round-to-nearest pieces or the two 2^-24-weight products (8/6 of the
+// matrix time).  Against fp64 beside the fp32-MFMA kernel (tests/test_gpu_ops.py, tools/gemm_split_accuracy.py): rms error 0.85 x that
+// kernel's on randn operands, where accumulation round-off dominates; on the adversarial mantissas (K = 512) the kept sum itself is accumulated
+// to 0.066 x the fp32 kernel's rms error, and the dropped terms then show as predicted: mean(y - full) = 1.10 x -mean(dropped), a mean
+// relative error of 1.08 2^-21 (the fp32 kernel: 5.8 2^-21 of two-signed round-off on the same operands).
+// The kept terms, the bound and the bias are pinned against a numpy model of this header (tests/split3_oracle.py, tests/test_gpu_split3.py:
+// operands whose kept products sum exactly come out bit for bit).  Domain of the bit-exact statements: every piece at least 2^-126 in
+// magnitude (operands from 2^-103 up); below that the subnormal pieces are flushed to zero on the device and the contraction
+// degrades towards the leading piece alone (x 2^-120 against w 2^100: 6.0e-5 of the output range instead of 2.2e-7; finite, never more).
+// An Inf operand yields NaN (Inf - Inf in the split), not +-Inf as the fp32 form.  Nothing is stored in reduced precision: operands are read
+// as fp32 and split while they are staged into LDS, the accumulators and the output are fp32; 6/16 of the fp32 kernel's matrix-pipe time.
 //
 // Block: 256 threads = 2 x 2 wave64, block tile 128 x 128, wave tile 64 x 64 = 2 x 2 tiles of v_mfma_f32_32x32x16_bf16; K-step 16.
 // Loader: 4 threads per row x float4 (64 B of a row per K-step, as conv_igemm.hip), two K-steps in flight in registers; a thread splits

@@ -53,21 +53,45 @@ FWD_CASES = [
 ]
 
 
-@pytest.mark.parametrize('case', FWD_CASES, ids=lambda c: 'B%d_H%d_%dto%d_k%d_form%d' % (c[0], c[1], c[2], c[3], c[4], c[6]))
-def test_conv_with_batchnorm_relu_on_load_matches_fp64(L, case):
+def _both_gemm_forms(cases, split):
+    """Every case with the fp32-MFMA form of the transform-domain GEMMs under its id, and the transform-domain cases `split` selects again
+    with the split-bf16 form (simq_launch_opts.gemm_split = 1, what the plans run) as '<id>_split3': the same operands and bars."""
+    out = []
+    for c in cases:
+        i = 'B%d_H%d_%dto%d_k%d_form%d' % (c[0], c[1], c[2], c[3], c[4], c[6])
+        out.append(pytest.param(c, 0, id=i))
+        if c[6] != 0 and split(c):
+            out.append(pytest.param(c, 1, id=i + '_split3'))
+    return out
+
+
+def _assert_gemm_form(L, gemm_split, M, N, K):
+    """One batched GEMM since the reset: gemm_split3_kernel where asked for and eligible (K % 16 == 0, N % 128 == 0, M >= 64), else fp32-MFMA."""
+    ran = L.launch_counts()
+    split = gemm_split == 1 and K % 16 == 0 and N % 128 == 0 and M >= 64
+    assert (ran.get('gemm_split3_batched', 0), ran.get('gemm_f32_batched', 0)) == ((1, 0) if split else (0, 1)), (ran, gemm_split, M, N, K)
+
+
+# (the split form on the 128-channel cases of both Winograd forms and one 512-channel case)
+@pytest.mark.parametrize('case,gemm_split', _both_gemm_forms(FWD_CASES, lambda c: c[3] <= 128 or c[2] == 256))
+def test_conv_with_batchnorm_relu_on_load_matches_fp64(L, case, gemm_split):
     B, H, Cin, Cout, k, pad, form, bias = case
+    opts = L.launch_opts(gemm_split=gemm_split)
     y, sc, sh, w, a = _operands(B, H, Cin, Cout, k, 700 + Cin + Cout + B + form)
     b = torch.randn(Cout, generator=torch.Generator().manual_seed(5)).cuda() if bias else None
     planes = {0: 0, 1: 16, 2: 36}[form]
     T = B * (H // 2) ** 2
     scratch = torch.empty(max(1, planes * Cout * Cin + 16 * T * (Cin + Cout)), device='cuda') if form else None
     out = torch.full((B, H, H, Cout), float('nan'), device='cuda')
+    L.lib.call('simq_launch_counts_reset')
     L.lib.call('simq_conv2d_fwd_bnrelu_in', L.ptr(y), L.ptr(sc), L.ptr(sh), L.ptr(w), L.ptr(b), L.ptr(out), B, H, H, Cin, Cout, k, k, 1, pad,
-               form, L.ptr(scratch), L.stream_ptr())
+               form, L.ptr(scratch), L.stream_ptr(), opts=opts)
+    if form:
+        _assert_gemm_form(L, gemm_split, B * (H // (2 * form)) ** 2, Cout, Cin)
     ref = F.conv2d(a.permute(0, 3, 1, 2), w.double().cpu().permute(0, 3, 1, 2), b.double().cpu() if bias else None, padding=pad).permute(0, 2, 3, 1)
     assert torch.isfinite(out).all()
     err = rel(out, ref)
-    print('\nconv(relu(bn(y))) %d->%d k%d B=%d form %d: %.3g vs fp64' % (Cin, Cout, k, B, form, err))
+    print('\nconv(relu(bn(y))) %d->%d k%d B=%d form %d gemm_split %d: %.3g vs fp64' % (Cin, Cout, k, B, form, gemm_split, err))
     assert err < (2e-5 if form == 2 else 1e-5)
     # ... and it is the unfused pair of launches' result to round-off: the activation materialised by torch, then the plain kernel
     a32 = torch.relu(torch.addcmul(sh, y, sc))
@@ -75,9 +99,11 @@ def test_conv_with_batchnorm_relu_on_load_matches_fp64(L, case):
     if form == 0:
         L.lib.call('simq_conv2d_fwd', L.ptr(a32), L.ptr(w), L.ptr(b), L.ptr(plain), B, H, H, Cin, Cout, k, k, 1, pad, None, L.stream_ptr())
     elif form == 1:
-        L.lib.call('simq_conv2d_fwd_winograd', L.ptr(a32), L.ptr(w), L.ptr(b), L.ptr(plain), B, H, H, Cin, Cout, None, L.ptr(scratch), L.stream_ptr())
+        L.lib.call('simq_conv2d_fwd_winograd', L.ptr(a32), L.ptr(w), L.ptr(b), L.ptr(plain), B, H, H, Cin, Cout, None, L.ptr(scratch), L.stream_ptr(),
+                   opts=opts)
     else:
-        L.lib.call('simq_conv2d_fwd_winograd4', L.ptr(a32), L.ptr(w), L.ptr(b), L.ptr(plain), B, H, H, Cin, Cout, None, L.ptr(scratch), L.stream_ptr())
+        L.lib.call('simq_conv2d_fwd_winograd4', L.ptr(a32), L.ptr(w), L.ptr(b), L.ptr(plain), B, H, H, Cin, Cout, None, L.ptr(scratch), L.stream_ptr(),
+                   opts=opts)
     assert rel(out, plain) < 2e-6          # (torch's addcmul may or may not contract to an fma: the same values to an ulp)
 
 
@@ -93,20 +119,23 @@ WGRAD_CASES = [
 ]
 
 
-@pytest.mark.parametrize('case', WGRAD_CASES, ids=lambda c: 'B%d_H%d_%dto%d_k%d_form%d' % (c[0], c[1], c[2], c[3], c[4], c[6]))
-def test_wgrad_with_batchnorm_relu_on_load_matches_fp64(L, case):
+@pytest.mark.parametrize('case,gemm_split', _both_gemm_forms(WGRAD_CASES, lambda c: True))
+def test_wgrad_with_batchnorm_relu_on_load_matches_fp64(L, case, gemm_split):
     B, H, Cin, Cout, k, pad, form = case
     y, sc, sh, _, a = _operands(B, H, Cin, Cout, k, 900 + Cin + Cout + B + form)
     dy = torch.randn(B, H, H, Cout, generator=torch.Generator().manual_seed(11 + B)).cuda()
     T = B * (H // 2) ** 2
     scratch = torch.empty(36 * Cout * Cin + 16 * T * (Cin + Cout), device='cuda') if form else None
     dw = torch.full((Cout, k, k, Cin), float('nan'), device='cuda')
+    L.lib.call('simq_launch_counts_reset')
     L.lib.call('simq_conv2d_wgrad_bnrelu_in', L.ptr(y), L.ptr(sc), L.ptr(sh), L.ptr(dy), L.ptr(dw), B, H, H, Cin, Cout, k, k, 1, pad, form,
-               L.ptr(scratch), L.stream_ptr())
+               L.ptr(scratch), L.stream_ptr(), opts=L.launch_opts(gemm_split=gemm_split))
+    if form:                               # the contraction runs over the tiles: F(4x4,3x3) where B * 36 is a multiple of 16, else F(2x2,3x3)
+        _assert_gemm_form(L, gemm_split, Cout, Cin, B * (H // 4) ** 2 if (B * (H // 4) ** 2) % 16 == 0 else T)
     ref = torch.nn.grad.conv2d_weight(a.permute(0, 3, 1, 2), (Cout, Cin, k, k), dy.double().cpu().permute(0, 3, 1, 2), padding=pad).permute(0, 2, 3, 1)
     assert torch.isfinite(dw).all()
     err = rel(dw, ref)
-    print('\nwgrad over relu(bn(y)) %d->%d k%d B=%d form %d: %.3g vs fp64' % (Cin, Cout, k, B, form, err))
+    print('\nwgrad over relu(bn(y)) %d->%d k%d B=%d form %d gemm_split %d: %.3g vs fp64' % (Cin, Cout, k, B, form, gemm_split, err))
     assert err < (1e-4 if (form == 1 and B % 4 == 0) else 1e-5)
 
 

@@ -4,6 +4,7 @@ Tolerance: 1e-4 relative (max-abs error over max-abs value) -- BASELINE.json's f
 observed errors are ~1e-6.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -37,6 +38,29 @@ def nhwc(t):     # NCHW cpu -> NHWC cuda
 
 def ohwi(w):     # OIHW cpu -> OHWI cuda
     return dev(w.permute(0, 2, 3, 1))
+
+
+def both_gemm_forms(cases, ids, split_ids):
+    """The per-operator Winograd tests in both forms of their transform-domain GEMMs (simq_launch_opts.gemm_split): every case with the
+    fp32-MFMA form under its id, and the cases named in split_ids again with the split-bf16 form (the plans' default) as '<id>_split3'
+    directly behind it -- the same operands, the same reference, the very same bars."""
+    out = []
+    for c, i in zip(cases, ids):
+        out.append(pytest.param(*c, 0, id=i))
+        if i in split_ids:
+            out.append(pytest.param(*c, 1, id=i + '_split3'))
+    assert set(split_ids) <= set(ids)
+    return out
+
+
+def assert_gemm_form(L, gemm_split, M, N, K, launches=1):
+    """The launch log since the last reset: `launches` batched GEMMs, gemm_split3_kernel where it was asked for and the problem is
+    eligible (K % 16 == 0, N % 128 == 0, M >= 64: gemm_split3_eligible), the fp32-MFMA kernel otherwise -- the fallback rule."""
+    ran = L.launch_counts()
+    split = gemm_split == 1 and K % 16 == 0 and N % 128 == 0 and M >= 64
+    want = (launches, 0) if split else (0, launches)
+    assert (ran.get('gemm_split3_batched', 0), ran.get('gemm_f32_batched', 0)) == want, (ran, gemm_split, M, N, K)
+    return split
 
 
 CONV_CASES = [
@@ -502,12 +526,14 @@ def test_conv_fp32_image_tile_kernel_matches_implicit_gemm(L, B, Cout, bias):
     assert rel(s0[:Cout], s_ref.sum(0)) < 1e-5 and rel(s0[Cout:], (s_ref * s_ref).sum(0)) < 1e-5
 
 
-@pytest.mark.parametrize('B,H,Cin,Cout', [(5, 24, 512, 512), (3, 24, 256, 512), (4, 12, 128, 256), (2, 8, 64, 64), (7, 24, 128, 128)],
-                         ids=['l4', 'l4a', 'l3a_small_map', 'narrow', 'l2'])
-def test_conv_winograd_forward_matches_direct(L, B, H, Cin, Cout):
+@pytest.mark.parametrize('B,H,Cin,Cout,gemm_split', both_gemm_forms(
+    [(5, 24, 512, 512), (3, 24, 256, 512), (4, 12, 128, 256), (2, 8, 64, 64), (7, 24, 128, 128)],
+    ['l4', 'l4a', 'l3a_small_map', 'narrow', 'l2'], ['l4a', 'l3a_small_map', 'narrow', 'l2']))
+def test_conv_winograd_forward_matches_direct(L, B, H, Cin, Cout, gemm_split):
     """conv_winograd.hip (input transform, 16 batched transform-domain GEMMs, output transform + epilogue) against the
     implicit-GEMM kernel and an fp64 convolution: outputs within 1e-5 of the output range (the transforms only add and
-    halve, measured ~7e-7), fused bias + batch statistics identical to round-off."""
+    halve, measured ~7e-7), fused bias + batch statistics identical to round-off.  '*_split3': the GEMMs in the split-bf16 form, the
+    same bars ('narrow': 64 columns and 32 rows are not eligible, the fp32-MFMA kernel must serve)."""
     g = torch.Generator().manual_seed(17 + Cin + Cout + B)
     x = torch.randn(B, H, H, Cin, generator=g).cuda()
     w = (torch.randn(Cout, 3, 3, Cin, generator=g) / (Cin * 9) ** 0.5).cuda()
@@ -518,9 +544,13 @@ def test_conv_winograd_forward_matches_direct(L, B, H, Cin, Cout):
     y0, y1 = torch.empty(B, H, H, Cout, device='cuda'), torch.full((B, H, H, Cout), float('nan'), device='cuda')
     s0, s1 = torch.zeros(2 * Cout, dtype=torch.float64, device='cuda'), torch.zeros(2 * Cout, dtype=torch.float64, device='cuda')
     L.lib.call('simq_conv2d_fwd', L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y0), B, H, H, Cin, Cout, 3, 3, 1, 1, L.ptr(s0), st)
-    L.lib.call('simq_conv2d_fwd_winograd', L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y1), B, H, H, Cin, Cout, L.ptr(s1), L.ptr(scratch), st)
+    L.lib.call('simq_launch_counts_reset')
+    L.lib.call('simq_conv2d_fwd_winograd', L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y1), B, H, H, Cin, Cout, L.ptr(s1), L.ptr(scratch), st,
+               opts=L.launch_opts(gemm_split=gemm_split))
+    assert_gemm_form(L, gemm_split, T, Cout, Cin)
     ref = F.conv2d(x.permute(0, 3, 1, 2).double(), w.permute(0, 3, 1, 2).double(), b.double(), padding=1).permute(0, 2, 3, 1)
     assert torch.isfinite(y1).all()
+    print('\nF(2x2,3x3) forward %dx%d B=%d gemm_split %d: error vs fp64 %.3g (direct kernel %.3g)' % (Cin, Cout, B, gemm_split, rel(y1, ref), rel(y0, ref)))
     assert rel(y1, ref) < 1e-5 and rel(y1, y0) < 1e-5
     assert rel(s1, s0) < 1e-6
     sref = torch.cat([ref.reshape(-1, Cout).sum(0), (ref * ref).reshape(-1, Cout).sum(0)])
@@ -555,15 +585,16 @@ def test_winograd_gemm_plane_per_xcd_walk_is_bit_identical(L, f4, B, H, Cin, Cou
     assert torch.equal(ys[0], ys[1])
 
 
-@pytest.mark.parametrize('B,H,Cin,Cout', [(5, 24, 512, 512), (3, 24, 256, 512), (4, 24, 128, 256), (6, 12, 256, 256), (29, 24, 256, 256),
-                                          (9, 24, 128, 128)],
-                         ids=['l4', 'l4a', 'l3a', 'l3_small_map', 'l3_b29', 'l2'])
-def test_conv_winograd4_forward_matches_direct(L, B, H, Cin, Cout):
+@pytest.mark.parametrize('B,H,Cin,Cout,gemm_split', both_gemm_forms(
+    [(5, 24, 512, 512), (3, 24, 256, 512), (4, 24, 128, 256), (6, 12, 256, 256), (29, 24, 256, 256), (9, 24, 128, 128)],
+    ['l4', 'l4a', 'l3a', 'l3_small_map', 'l3_b29', 'l2'], ['l4a', 'l3a', 'l3_small_map', 'l3_b29', 'l2']))
+def test_conv_winograd4_forward_matches_direct(L, B, H, Cin, Cout, gemm_split):
     """The F(4x4,3x3) form of the no-grad forwards (conv_winograd.hip: 6x6 input transform at stride 4, 36 batched transform-domain
     GEMMs, 4x4 output transform + forward epilogue; interpolation points {0, 1, -1, 1/2, -2, inf}) against the implicit-GEMM kernel and
     an fp64 convolution: its larger transform coefficients cost ~6x the round-off of F(2x2,3x3) -- measured / simulated 3-4e-6 of the
     output range -- held to 2e-5 per layer (the Q-map bar after the eight wide layers is 1e-4); fused bias + batch statistics agree
-    with the direct kernel to the same order."""
+    with the direct kernel to the same order.  '*_split3': the 36 GEMMs in the split-bf16 form, the same bars ('l3_small_map': 54 tiles
+    are fewer than the 64 rows the split form wants, the fp32-MFMA kernel must serve)."""
     g = torch.Generator().manual_seed(19 + Cin + Cout + B)
     x = torch.relu(torch.randn(B, H, H, Cin, generator=g)).cuda()          # post-ReLU activations, as in the network
     w = (torch.randn(Cout, 3, 3, Cin, generator=g) * (2.0 / (Cout * 9)) ** 0.5).cuda()
@@ -574,24 +605,29 @@ def test_conv_winograd4_forward_matches_direct(L, B, H, Cin, Cout):
     y0, y1 = torch.empty(B, H, H, Cout, device='cuda'), torch.full((B, H, H, Cout), float('nan'), device='cuda')
     s0, s1 = torch.zeros(2 * Cout, dtype=torch.float64, device='cuda'), torch.zeros(2 * Cout, dtype=torch.float64, device='cuda')
     L.lib.call('simq_conv2d_fwd', L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y0), B, H, H, Cin, Cout, 3, 3, 1, 1, L.ptr(s0), st)
-    L.lib.call('simq_conv2d_fwd_winograd4', L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y1), B, H, H, Cin, Cout, L.ptr(s1), L.ptr(scratch), st)
+    L.lib.call('simq_launch_counts_reset')
+    L.lib.call('simq_conv2d_fwd_winograd4', L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y1), B, H, H, Cin, Cout, L.ptr(s1), L.ptr(scratch), st,
+               opts=L.launch_opts(gemm_split=gemm_split))
+    assert_gemm_form(L, gemm_split, T4, Cout, Cin)
     ref = F.conv2d(x.permute(0, 3, 1, 2).double(), w.permute(0, 3, 1, 2).double(), b.double(), padding=1).permute(0, 2, 3, 1)
     assert torch.isfinite(y1).all()
-    print('\nF(4x4,3x3) forward %dx%d B=%d: error vs fp64 %.3g (direct kernel %.3g)' % (Cin, Cout, B, rel(y1, ref), rel(y0, ref)))
+    print('\nF(4x4,3x3) forward %dx%d B=%d gemm_split %d: error vs fp64 %.3g (direct kernel %.3g)' % (Cin, Cout, B, gemm_split, rel(y1, ref), rel(y0, ref)))
     assert rel(y1, ref) < 2e-5 and rel(y1, y0) < 2e-5
     assert rel(s1, s0) < 1e-5
     sref = torch.cat([ref.reshape(-1, Cout).sum(0), (ref * ref).reshape(-1, Cout).sum(0)])
     assert rel(s1, sref) < 1e-5
 
 
-@pytest.mark.parametrize('B,H,Cin,Cout', [(5, 24, 512, 512), (3, 24, 256, 512), (6, 12, 256, 256), (8, 24, 512, 512), (4, 24, 256, 256),
-                                          (8, 24, 128, 128), (5, 24, 128, 128)],
-                         ids=['l4', 'l4a', 'l3_small_map', 'l4_f4', 'l3_f4', 'l2_f4', 'l2'])
-def test_conv_winograd_wgrad_matches_direct(L, B, H, Cin, Cout):
+@pytest.mark.parametrize('B,H,Cin,Cout,gemm_split', both_gemm_forms(
+    [(5, 24, 512, 512), (3, 24, 256, 512), (6, 12, 256, 256), (8, 24, 512, 512), (4, 24, 256, 256), (8, 24, 128, 128), (5, 24, 128, 128)],
+    ['l4', 'l4a', 'l3_small_map', 'l4_f4', 'l3_f4', 'l2_f4', 'l2'], ['l4a', 'l3_small_map', 'l3_f4', 'l2_f4', 'l2']))
+def test_conv_winograd_wgrad_matches_direct(L, B, H, Cin, Cout, gemm_split):
     """Transform-domain weight gradient (dy / x transforms, batched contractions over the tiles, G^T dU G) against the
     direct wgrad kernel and fp64.  Tile counts that allow it ('*_f4': batch * 36 a multiple of 16) take the F(4x4,3x3) form,
     whose larger coefficients cost ~10x the round-off (measured 0.6-3e-5 of the gradient's range) -- held to the 1e-4
-    per-kernel bar (a weight gradient is a leaf: the error does not propagate); the others run F(2x2,3x3) (GEMM form, or the pixel-split form when the tile count is not a multiple of 16)."""
+    per-kernel bar (a weight gradient is a leaf: the error does not propagate); the others run F(2x2,3x3) (GEMM form, or the pixel-split form when the tile count is not a multiple of 16).
+    '*_split3': the batched GEMM in the split-bf16 form, the same bars ('l3_small_map': 216 tiles take the pixel-split form, no batched
+    GEMM at all in either setting)."""
     g = torch.Generator().manual_seed(29 + Cin + Cout + B)
     x = torch.randn(B, H, H, Cin, generator=g).cuda()
     dy = torch.randn(B, H, H, Cout, generator=g).cuda()
@@ -600,38 +636,55 @@ def test_conv_winograd_wgrad_matches_direct(L, B, H, Cin, Cout):
     st = L.stream_ptr()
     d0, d1 = torch.empty(Cout, 3, 3, Cin, device='cuda'), torch.full((Cout, 3, 3, Cin), float('nan'), device='cuda')
     L.lib.call('simq_conv2d_wgrad', L.ptr(x), L.ptr(dy), L.ptr(d0), B, H, H, Cin, Cout, 3, 3, 1, 1, st)
-    L.lib.call('simq_conv2d_wgrad_winograd', L.ptr(x), L.ptr(dy), L.ptr(d1), B, H, H, Cin, Cout, L.ptr(scratch), st)
+    L.lib.call('simq_launch_counts_reset')
+    L.lib.call('simq_conv2d_wgrad_winograd', L.ptr(x), L.ptr(dy), L.ptr(d1), B, H, H, Cin, Cout, L.ptr(scratch), st,
+               opts=L.launch_opts(gemm_split=gemm_split))
+    f4 = H % 4 == 0 and (B * (H // 4) ** 2) % 16 == 0
+    assert_gemm_form(L, gemm_split, Cout, Cin, B * (H // 4) ** 2 if f4 else T, launches=1 if f4 or T % 16 == 0 else 0)
     ref = torch.nn.grad.conv2d_weight(x.permute(0, 3, 1, 2).double(), (Cout, Cin, 3, 3), dy.permute(0, 3, 1, 2).double(),
                                       padding=1).permute(0, 2, 3, 1)
     assert torch.isfinite(d1).all()
+    print('\nWinograd wgrad %dx%d B=%d H=%d gemm_split %d: error vs fp64 %.3g (direct kernel %.3g)' % (Cin, Cout, B, H, gemm_split, rel(d1, ref), rel(d0, ref)))
     assert rel(d1, ref) < (1e-4 if B % 4 == 0 else 1e-5) and rel(d0, ref) < 1e-5
 
 
-@pytest.mark.parametrize('B,Cin,Cout,splits', [(32, 256, 256, 0), (32, 256, 256, 2), (32, 256, 256, 4), (32, 128, 256, 4), (16, 256, 512, 2),
-                                                (8, 256, 256, 4), (32, 512, 512, 0), (12, 256, 256, 0)],
-                         ids=['l3_auto', 'l3_s2', 'l3_s4', 'l3a_s4', 'l4a_s2', 'l3_b8_s4_no_room_or_short', 'l4_auto_stays_whole', 'b12_tiles_not_divisible'])
-def test_conv_winograd_wgrad_ksplit(L, B, Cin, Cout, splits):
+@functools.lru_cache(maxsize=1)
+def _ksplit_operands(B, H, Cin, Cout):
+    """(x, dy on the device, the fp64 weight gradient): computed once for the two GEMM forms and the split counts of one shape (the cases
+    of a shape follow each other)."""
+    g = torch.Generator().manual_seed(31 + Cin + Cout + B)
+    x = torch.randn(B, H, H, Cin, generator=g).cuda()
+    dy = torch.randn(B, H, H, Cout, generator=g).cuda()
+    ref = torch.nn.grad.conv2d_weight(x.permute(0, 3, 1, 2).double(), (Cout, Cin, 3, 3), dy.permute(0, 3, 1, 2).double(),
+                                      padding=1).permute(0, 2, 3, 1)
+    return x, dy, ref
+
+
+@pytest.mark.parametrize('B,Cin,Cout,splits,gemm_split', both_gemm_forms(
+    [(32, 256, 256, 0), (32, 256, 256, 2), (32, 256, 256, 4), (32, 128, 256, 4), (16, 256, 512, 2), (8, 256, 256, 4), (32, 512, 512, 0), (12, 256, 256, 0)],
+    ['l3_auto', 'l3_s2', 'l3_s4', 'l3a_s4', 'l4a_s2', 'l3_b8_s4_no_room_or_short', 'l4_auto_stays_whole', 'b12_tiles_not_divisible'],
+    ['l3_auto', 'l3_s2', 'l3_s4', 'l3a_s4', 'l4a_s2', 'l3_b8_s4_no_room_or_short', 'b12_tiles_not_divisible']))
+def test_conv_winograd_wgrad_ksplit(L, B, Cin, Cout, splits, gemm_split):
     """K-split of the F(4x4,3x3) weight-gradient GEMMs (conv_winograd.hip: S chunks of the tile range as 36 S planes, summed in chunk order
     by wino4_dw_kernel): forced and shape-chosen splits against fp64 and against the unsplit form -- same 1e-4 per-kernel bar as the
     unsplit F(4x4,3x3) gradient (the split shortens every accumulation chain), NaN-filled destination and scratch, and a second call that
-    must reproduce the first bit for bit (no atomics)."""
-    g = torch.Generator().manual_seed(31 + Cin + Cout + B)
+    must reproduce the first bit for bit (no atomics).  '*_split3': the 36 S GEMMs in the split-bf16 form, the same bars."""
     H = 24
-    x = torch.randn(B, H, H, Cin, generator=g).cuda()
-    dy = torch.randn(B, H, H, Cout, generator=g).cuda()
+    x, dy, ref = _ksplit_operands(B, H, Cin, Cout)
     T = B * (H // 2) ** 2
     scratch = torch.empty(36 * Cout * Cin + 16 * T * (Cin + Cout), device='cuda')
     st = L.stream_ptr()
-    ref = torch.nn.grad.conv2d_weight(x.permute(0, 3, 1, 2).double(), (Cout, Cin, 3, 3), dy.permute(0, 3, 1, 2).double(),
-                                      padding=1).permute(0, 2, 3, 1)
     out = {}
     for s in (1, splits, splits):
         d = torch.full((Cout, 3, 3, Cin), float('nan'), device='cuda')
         scratch.fill_(float('nan'))
+        L.lib.call('simq_launch_counts_reset')
         L.lib.call('simq_conv2d_wgrad_winograd', L.ptr(x), L.ptr(dy), L.ptr(d), B, H, H, Cin, Cout, L.ptr(scratch), st,
-                   opts=L.launch_opts(wgrad_ksplit=s))
+                   opts=L.launch_opts(wgrad_ksplit=s, gemm_split=gemm_split))
         torch.cuda.synchronize()
+        assert assert_gemm_form(L, gemm_split, Cout, Cin, 16) == (gemm_split == 1)      # (K = the tiles of a chunk: a multiple of 16 in every case here)
         assert torch.isfinite(d).all()
+        print('\nF(4x4,3x3) wgrad %dx%d B=%d ksplit %d gemm_split %d: error vs fp64 %.3g' % (Cin, Cout, B, s, gemm_split, rel(d, ref)))
         assert rel(d, ref) < 1e-4
         out.setdefault(s, []).append(d)
     assert torch.equal(out[splits][0], out[splits][1])
@@ -665,7 +718,7 @@ def test_gemm_f32_batched_is_an_exact_fp32_contraction(L, M, N, K, P):
                          ids=['f4_l4_b32_wide_tile', 'f4_l4_b32_128x128', 'f4_b29_ragged_rows', 'f2_l2_b32', 'wgrad_l4', 'wgrad_l3_ksplit', 'small_odd_planes', 'one_ragged_tile_wide'])
 def test_gemm_split3_reproduces_the_fp32_contraction_at_fp32_roundoff(L, M, N, K, P, tile):
     """Round 6: simq_gemm_f32_batched with gemm_split = 1 (gemm_split3.hip) -- the same contraction on the bf16 matrix cores: both fp32 operands
-    split EXACTLY into three bf16 pieces while they are staged, the six partial products down to 2^-24 of each product, fp32 accumulators,
+    split EXACTLY into three bf16 pieces while they are staged, six of the nine piece products (the dropped three: up to 2^-21 of a product, tests/test_gpu_split3.py), fp32 accumulators,
     fp32 output.  Held to the bars of the fp32-MFMA form (2e-6 of the range against fp64) AND to that form itself: its rms error against
     fp64 may not exceed 1.1 x the fp32-MFMA kernel's on the same operands (measured 0.85 x: the matrix core rounds once per 16 products
     instead of once per product); NaN-filled destination, rows past M never written, both block walks bit-identical; operands with a 2^40
