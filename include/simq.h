@@ -625,6 +625,46 @@ int simq_grid_paths(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* 
                     int64_t path_pairs, int32_t* d_lengths, int32_t* d_endpoints, int32_t* d_parents, int64_t parents_ints, float* d_dist,
                     int64_t dist_floats, int32_t* d_status, void* stream);
 
+/* ---- shortest-path distance queries: the point form of the distance images (envs.py:2506-2511 OccupancyMap.shortest_path_distance,
+ * reached through Mapper.distance_to_receptacle, envs.py:2189-2194, by every partial reward; shortest_paths.pyx:150-158
+ * GridGraph.shortest_path_distance) ------------------------------------------------------------------------------------------------
+ * One problem = one grid [rows][cols] of uint8 (free where != 0), one source pixel and n_targets >= 0 target pixels; one wavefront
+ * per problem, every problem of a call in one launch.  Per problem:
+ *   snap        (closest_offset >= 0) the source, then each target, is replaced by closest[:, i, j]: int32 [2][rows][cols] at
+ *               d_closest + closest_offset, the layout simq_occupancy_maps writes and simq_grid_paths reads
+ *   search      the distances of simq_grid_distance_images from the snapped source -- the same updates, fl32(d[u] + w) accepted when
+ *               strictly smaller, to the same fixed point -- in the problem's working image, fp32 [rows][cols] at d_work + work_offset
+ *   queries     target q of the problem is pair target_offset + q of `targets` (int32 (i, j) pairs) and its distance goes to
+ *               d_out[target_offset + q]: the label of the snapped target, -1 where it is unreachable -- the value
+ *               GridGraph.shortest_path_distance returns, before OccupancyMap divides it by the pixels per metre
+ * images != 0 makes the working images outputs: each then holds what simq_grid_distance_images writes without its epilogue for the
+ * snapped source (-1 where unreachable); with images == 0 their content after the call is unspecified.
+ * `problems` (n descriptors) and `targets` (n_targets_total pairs) are host arrays, validated here before anything is copied or
+ * launched: rows, cols >= 1, rows * cols < SIMQ_GRID_MAX_CELLS; the source and every target inside the grid; every target range
+ * inside `targets`; grid, closest block and working image inside the declared extent of their buffers, d_out of at least
+ * n_targets_total floats; 4-byte alignment of d_closest, d_work, d_out and d_status, 8 of d_descriptors; no two problems sharing a
+ * working image or a target (and so d_out) range; nothing the launch writes -- d_work, d_out, d_status, d_descriptors -- sharing a byte
+ * with any other buffer of the call.  Both arrays are then copied, the descriptors first and the targets behind them, to
+ * d_descriptors (n * sizeof(simq_grid_query_problem) + 8 * n_targets_total bytes) on `stream`.  Several problems may share a grid
+ * and a closest block.  d_closest may be NULL when no problem snaps; targets and d_out when n_targets_total is 0.  d_status[n]
+ * (int32): 0 = ok, 1 = the cap of rows * cols + 1 passes was hit (cannot happen, as for the images), 2 = bad descriptor or a
+ * pixel outside the grid -- given or snapped; the kernel checks again: nothing is written for a bad descriptor or source, and only
+ * that target's distance is left unwritten for a bad target. */
+typedef struct simq_grid_query_problem {
+    int64_t grid_offset;        /* byte offset of the problem's [rows][cols] uint8 grid in d_grids */
+    int64_t closest_offset;     /* int32 offset of its [2][rows][cols] closest cells in d_closest, or -1 */
+    int64_t work_offset;        /* float offset of its [rows][cols] fp32 working image in d_work */
+    int64_t target_offset;      /* pair offset of its first target in `targets`, float offset of its first distance in d_out */
+    int32_t n_targets;
+    int32_t rows, cols;
+    int32_t src_i, src_j;
+    int32_t reserved_;
+} simq_grid_query_problem;
+int simq_grid_distance_queries(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* d_closest, int64_t closest_ints,
+                               const simq_grid_query_problem* problems, int n, const int32_t* targets, int64_t n_targets_total,
+                               void* d_descriptors, float* d_work, int64_t work_floats, int images, float* d_out, int64_t out_floats,
+                               int32_t* d_status, void* stream);
+
 /* ---- local state images (Mapper.get_state's crop / rotation: envs.py:2199-2215 _get_local_map / _get_local_distance_map,
  * 2243-2275 _create_global_overhead_map / _create_global_robot_map, 2368-2375 the nonspatial channels) -----------------------------
  * One problem = one robot's state: d_out[p][96][96][C] fp32 (NHWC, what simq_forward and the replay ring take), every channel of

@@ -37,6 +37,9 @@ _LAZY = {
     'WaypointGraph': ('.waypoints', 'WaypointGraph'),
     'grid_dense_paths': ('.waypoints', 'grid_dense_paths'),
     'shortest_paths': ('.waypoints', 'shortest_paths'),
+    'grid_distance_queries': ('.grid_queries', 'grid_distance_queries'),
+    'shortest_path_distances': ('.grid_queries', 'shortest_path_distances'),
+    'distances_to_receptacle': ('.grid_queries', 'distances_to_receptacle'),
     'local_state_images': ('.local_maps', 'local_state_images'),
     'local_map': ('.local_maps', 'local_map'),
     'local_distance_map': ('.local_maps', 'local_distance_map'),

@@ -1,4 +1,4 @@
-"""What the wrappers of the batched map operators share (grid_paths, waypoints, occupancy, observation, local_maps, intention_drawing,
+"""What the wrappers of the batched map operators share (grid_paths, grid_queries, waypoints, occupancy, observation, local_maps, intention_drawing,
 visualization): the device, the argument checks, the packed upload, the `out` check and the status read-back.  Nothing here knows an
 operator: the helpers check and report, the operators word their own errors."""
 import numpy as np
