@@ -103,9 +103,12 @@ typedef struct simq_plan_options {
                                    * activation / its mask from the saved pre-BN output.  Needs fuse_bn_backward_sums. */
     int deterministic;            /* 0.  1: run-to-run bit-identical results UP TO the rounding of the fp64 reductions (debugging aid, e.g. rank
                                    * divergence in data-parallel runs): every fp32 reduction of the step has a fixed order -- the weight gradients
-                                   * whose pixel reduction is split over blocks leave per-split partial tiles in a slab (64 MB more workspace) that
-                                   * a second launch adds in split order, instead of fp32 atomics; the one-hot head backward walks the transitions
-                                   * in order.  The BatchNorm sums (forward statistics, the backward's [sum dz | sum dz*xhat]) stay fp64 atomics in
+                                   * whose pixel reduction is split over blocks leave per-split partial tiles in a slab that a second launch adds
+                                   * in split order, instead of fp32 atomics (64 MB more workspace, plus a slab of the first convolution's own,
+                                   * 96 x 64 x 49 x num_input_channels floats and at most 64 MB, so that its weight gradient may run beside the
+                                   * last block's); the one-hot head backward still runs one block per transition, each leaves its terms of the
+                                   * last layer's gradients in 512 B of workspace and a one-block launch adds them in transition order.  The
+                                   * BatchNorm sums (forward statistics, the backward's [sum dz | sum dz*xhat]) stay fp64 atomics in
                                    * arbitrary order in either setting: a result changes only if two orders of an fp64 sum round to different fp32
                                    * values (~1e-9 per consumer; never observed: tests/diag/diag_determinism.py, tests/test_gpu_overlap.py compare
                                    * whole steps bit for bit), so "bit-identical" is an observation about those sums, not a guarantee. */
@@ -535,6 +538,9 @@ int simq_conv2d_wgrad_bf16(const float* d_x, const float* d_dy, float* d_dw_ohwi
 int64_t simq_conv2d_wgrad_bf16_slab_bytes(void);
 int simq_conv2d_wgrad_bf16_slab(const float* d_x, const float* d_dy, float* d_dw_ohwi, int batch, int hin, int win, int cin, int cout,
                                 int r, int s, int stride, int pad, int nplanes, void* d_scratch, void* d_slab, void* stream, const simq_launch_opts* opts);
+/* The second launch of the deterministic weight gradients on its own: d_dw[e] = ((d_slab[0][e] + d_slab[1][e]) + d_slab[2][e]) + ... in
+ * fp32, d_slab = [splits][n] floats, d_dw = n floats, overwritten.  No alignment beyond a float's is required of either pointer. */
+int simq_wgrad_slab_sum(const float* d_slab, float* d_dw, int64_t n, int splits, void* stream);
 int simq_upsample2x_fwd(const float* d_in, float* d_out, int batch, int h, int w, int c, void* stream);
 int simq_upsample2x_bwd(const float* d_dout, float* d_din, int batch, int h, int w, int c, void* stream);
 

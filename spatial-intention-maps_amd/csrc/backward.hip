@@ -33,7 +33,8 @@ int bn_bwd(const Ctx& c, const BnL& bn, const float* g, const float* mask, const
                                mask_from_y ? c.aux(bn, 0) : nullptr, mask_from_y ? c.aux(bn, 1) : nullptr);
 }
 
-int conv_wgrad(const Ctx& c, const ConvL& cv, const Act& x, const Act& dy, int hin, const InBn& in = InBn()) {
+// `own_slab`: deterministic plans, the first convolution: the slab of its own (Layout::dslab_stem) instead of the one every other layer shares
+int conv_wgrad(const Ctx& c, const ConvL& cv, const Act& x, const Act& dy, int hin, const InBn& in = InBn(), bool own_slab = false) {
     ConvGeom g = geom(c.p, cv, c.B, hin);
     if (c.mc() && cv.wp_off >= 0) {
         SIMQ_REQUIRE(!in.on(), "conv_wgrad: BatchNorm-on-load exists for fp32 plans only");
@@ -44,6 +45,7 @@ int conv_wgrad(const Ctx& c, const ConvL& cv, const Act& x, const Act& dy, int h
     if (cv.wu_off >= 0 && c.L.wino >= 0 && winograd_wgrad_eligible(g) && c.p->opt.winograd_wgrad &&
         winograd_wgrad_pays(g, c.p->opt.winograd_wgrad_f4 != 0))
         return launch_conv_wgrad_winograd(x.f, dy.f, c.grads + cv.w_off, g, c.f(c.L.wino), c.stream, c.p->opt.winograd_wgrad_f4 != 0, in);
+    if (own_slab && c.dslab_stem()) return launch_conv_wgrad(x.f, dy.f, c.grads + cv.w_off, g, c.stream, in, c.dslab_stem(), stem_det_slab_floats(c.p->cin));
     return launch_conv_wgrad(x.f, dy.f, c.grads + cv.w_off, g, c.stream, in, c.dslab());
 }
 
@@ -135,7 +137,7 @@ int backward_impl(const Ctx& c, const float* d_dq, int phase, const OneHotGrad* 
     if (oh) {   // B non-zeros: conv3 backward + bilinear transpose at those pixels only
         RC(launch_head_onehot_bwd(c.f(L.ah2), c.params + p->h3.w_off, oh->action, oh->q_sa, oh->y, oh->grad_scale, S[1],
                                   c.grads + p->h3.w_off, c.grads + p->h3.b_off, B, p->cout, c.stream,
-                                  c.f(L.yh2), 0, c.aux(p->hb2, 2), c.aux(p->hb2, 3), no_fuse_head ? nullptr : c.red(p->hb2), p->opt.deterministic));
+                                  c.f(L.yh2), 0, c.aux(p->hb2, 2), c.aux(p->hb2, 3), no_fuse_head ? nullptr : c.red(p->hb2), L.hpart >= 0 ? c.f(L.hpart) : nullptr));
     } else {
         RC(launch_upsample2x_fwd(c.f(L.ah2), c.f(L.up2), B, 48, 48, 32, c.stream));   // (the forward pass does not keep it)
         RC(launch_head_conv3_bwd(c.f(L.up2), c.params + p->h3.w_off, d_dq, S[0], c.grads + p->h3.w_off, c.grads + p->h3.b_off, B, 9216, 32, p->cout, c.stream,
@@ -291,9 +293,10 @@ int backward_impl(const Ctx& c, const float* d_dq, int phase, const OneHotGrad* 
     }
     // every weight gradient of the walk so far is behind the join.  Before the stem it is needed only for the temporaries the stem reuses
     // (the first set): when the last block worked on the second set, the stem's backward (pool, BatchNorm, weight gradient: HBM-bound) runs
-    // beside that block's weight gradients and the join moves behind it.  (Deterministic plans share one slab between every weight gradient.)
+    // beside that block's weight gradients and the join moves behind it.  (Deterministic plans: the blocks' weight gradients share one slab, in
+    // side-stream order; the stem's has a slab of its own, Layout::dslab_stem.)
     // (Six alternating pairs of 60 steps: bf16 configs[2] 14 834 -> 14 865 tr/s, fp32 configs[1] +0.2 ... +0.4 %: small, never negative.)
-    const bool late_join = piped && phase != 1 && i_hi > i_lo && ((i_hi - i_lo) & 1) == 1 && !p->opt.deterministic;
+    const bool late_join = piped && phase != 1 && i_hi > i_lo && ((i_hi - i_lo) & 1) == 1;
     if (piped) {
         if (late_join) SIMQ_CHECK_HIP(hipStreamWaitEvent(c.stream, c.ev_wdone[0], 0));
         else RC(join());
@@ -318,7 +321,7 @@ int backward_impl(const Ctx& c, const float* d_dq, int phase, const OneHotGrad* 
     if (stem16)                                      // (T0 = dz is dead behind bn_bwd: it holds the partial-sum slabs)
         RC(launch_stem_wgrad_bf16(x0.f, T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream));
     else
-        RC(conv_wgrad(c, p->stem, x0, T1, 96));
+        RC(conv_wgrad(c, p->stem, x0, T1, 96, InBn(), true));
     if (late_join) RC(join());
     return 0;
 }

@@ -158,7 +158,16 @@ int launch_conv_winograd4(const float* x, const float* U4, float* y, const ConvG
 // det_slab: NULL, or kWgradDetSlabFloats floats of scratch -- the pixel-split blocks then leave their partial tiles there and a second launch
 // adds them in split order (deterministic plans) instead of fp32 atomics into the zeroed dw
 constexpr int64_t kWgradDetSlabFloats = 16 << 20;
-int launch_conv_wgrad(const float* x, const float* dy, float* dw, const ConvGeom& g, hipStream_t stream, const InBn& in = InBn(), float* det_slab = nullptr);
+// ... or a smaller slab of det_slab_floats floats that is known to hold the launch (the split count is still chosen against kWgradDetSlabFloats,
+// so it does not depend on which slab a launch got; a slab that turns out too small is an error, not a smaller split)
+constexpr int kWgradMaxSplits = 96;                  // the most pixel ranges a launch makes
+// the first convolution's own slab (deterministic plans: its weight gradient runs beside the last block's, which use the shared one)
+inline int64_t stem_det_slab_floats(int cin) {
+    const int64_t want = (int64_t)kWgradMaxSplits * 64 * 49 * cin;
+    return want < kWgradDetSlabFloats ? want : kWgradDetSlabFloats;
+}
+int launch_conv_wgrad(const float* x, const float* dy, float* dw, const ConvGeom& g, hipStream_t stream, const InBn& in = InBn(), float* det_slab = nullptr,
+                      int64_t det_slab_floats = kWgradDetSlabFloats);
 int launch_wgrad_slab_sum(const float* slab, float* dw, int64_t n, int splits, hipStream_t stream);   // dw[e] = sum_s slab[s][e], s ascending
 // conv_wgrad.hip: `batch` independent dw_g = dy_g^T * x_g in one launch (dw zeroed by the caller)
 int launch_wgrad_batched(const float* x, const float* dy, float* dw, int M, int N, int K, int batch, hipStream_t stream, const LaunchTune& tune = LaunchTune());
@@ -264,7 +273,9 @@ int launch_head_onehot_bwd(const float* ah2, const float* w3, const int64_t* act
                            float grad_scale, float* ds1, float* dw3, float* db3, int B, int Cout, hipStream_t stream,
                            const float* ypre = nullptr, int ypre_bf16 = 0, const float* mean = nullptr, const float* invstd = nullptr,
                            double* red = nullptr,    // red: fused BN-backward sums of the BatchNorm in front (hb2)
-                           int serial = 0);          // 1: one block walks the transitions in order (deterministic plans)
+                           float* det_part = nullptr);   // deterministic plans: head_onehot_det_part_bytes(B) of scratch -- the blocks leave their
+                                                         // terms of dw3 / db3 / red there, a one-block launch adds them in transition order
+int64_t head_onehot_det_part_bytes(int B);
 int launch_head_conv3_bwd(const float* x, const float* w, const float* dq, float* dx, float* dw, float* dbias,
                           int B, int HW, int Cin, int Cout, hipStream_t stream, float* det_slab = nullptr);   // det_slab: as launch_conv_wgrad
 

@@ -33,6 +33,7 @@ struct WgradArgs {
     unsigned x_bytes, dy_bytes;
     long gx, gdy, gdw;   // batched launch (blockIdx.y = g): element offsets of the g-th x / dy / dw (conv_winograd.hip)
     float* slab;         // NULL, or [splits][Cout][K] partial tiles (deterministic plans: plain stores, summed in split order afterwards)
+    int64_t slab_floats; // what `slab` holds
     const float* xscale; const float* xshift;   // XBN: x is a pre-BatchNorm output, the operand is relu(x * xscale[ci] + xshift[ci]) (common.h InBn)
 };
 
@@ -275,7 +276,7 @@ int run(const WgradArgs& a, hipStream_t stream, const LaunchTune& tune, int batc
     // time ~ ceil(tiles*s / 256) * (reduction steps per block + fixed prologue/atomic-epilogue cost).
     const int rsteps = (p.M + BR - 1) / BR;
     int max_splits = rsteps / 8;                     // keep >= 8 reduction steps per block
-    if (max_splits > 96) max_splits = 96;
+    if (max_splits > kWgradMaxSplits) max_splits = kWgradMaxSplits;
     if (max_splits < 1) max_splits = 1;
     int splits = 1;
     double best = 1e300;
@@ -298,6 +299,8 @@ int run(const WgradArgs& a, hipStream_t stream, const LaunchTune& tune, int batc
     splits = (p.M + rps - 1) / rps;
     p.rows_per_split = rps;
     p.splits = splits;
+    SIMQ_REQUIRE(!p.slab || (int64_t)splits * p.Cout * p.K <= p.slab_floats, "wgrad: %d splits of %ld floats do not fit the slab of %ld floats",
+                 splits, (long)p.Cout * p.K, (long)p.slab_floats);
     // fp32: measured and left OFF by default (LaunchTune::wgrad_xcd_group == 2 forces it on, A-B runs): three alternating bench pairs each on two boxes, 3453 -> 3435 and
     // 3382 -> 3361 tr/s with the grouping, with or without the stagger -- the fp32 launches are short (22-72 us, 18 MB of operands at
     // B = 32) and are not bound by their L2 misses, unlike the bf16 kernel's at B = 128 (conv_wgrad_bf16.hip: 237 -> 63 MB, + 0.5-1 %)
@@ -319,10 +322,31 @@ int run(const WgradArgs& a, hipStream_t stream, const LaunchTune& tune, int batc
     return 0;
 }
 
-__global__ void __launch_bounds__(256) wgrad_slab_sum_kernel(const float* __restrict__ slab, float* __restrict__ dw, size_t n, int splits) {
-    for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        float a = slab[e];
-        for (int s2 = 1; s2 < splits; ++s2) a += slab[(size_t)s2 * n + e];
+// dw[e] = ((slab[0][e] + slab[1][e]) + slab[2][e]) + ... : the split order, one thread per element.  The sum is a chain of dependent
+// adds but its loads depend on nothing: they are issued kSumBatch splits at a time and the adds consume them in order, so a thread has
+// kSumBatch loads in flight instead of one (21-96 splits x 36 864-147 456 elements = 12-25 MB per launch: a streaming read).  One-wave
+// blocks: the smallest n (36 864) still makes 576 of them, more than two per CU.
+constexpr int kSumBatch = 32, kSumThreads = 64;
+
+__global__ void __launch_bounds__(kSumThreads) wgrad_slab_sum_kernel(const float* __restrict__ slab, float* __restrict__ dw, size_t n, int splits) {
+    for (size_t e = blockIdx.x * (size_t)kSumThreads + threadIdx.x; e < n; e += (size_t)gridDim.x * kSumThreads) {
+        const float* src = slab + e;
+        float a = src[0];
+        int s2 = 1;
+        for (; s2 + kSumBatch <= splits; s2 += kSumBatch) {
+            float v[kSumBatch];
+#pragma unroll
+            for (int k = 0; k < kSumBatch; ++k) v[k] = src[(size_t)(s2 + k) * n];
+#pragma unroll
+            for (int k = 0; k < kSumBatch; ++k) a += v[k];
+        }
+        if (s2 < splits) {                           // the ragged end: one more batch, splits past the last read nothing and add nothing
+            float v[kSumBatch];
+#pragma unroll
+            for (int k = 0; k < kSumBatch; ++k) v[k] = s2 + k < splits ? src[(size_t)(s2 + k) * n] : 0.f;
+#pragma unroll
+            for (int k = 0; k < kSumBatch; ++k) if (s2 + k < splits) a += v[k];
+        }
         dw[e] = a;
     }
 }
@@ -330,16 +354,18 @@ __global__ void __launch_bounds__(256) wgrad_slab_sum_kernel(const float* __rest
 }  // namespace
 
 int launch_wgrad_slab_sum(const float* slab, float* dw, int64_t n, int splits, hipStream_t stream) {
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(wgrad_slab_sum_kernel, dim3(blocks), dim3(256), 0, stream, slab, dw, (size_t)n, splits);
+    SIMQ_REQUIRE(slab && dw && n >= 1 && splits >= 1, "wgrad_slab_sum: bad argument (n=%ld, splits=%d)", (long)n, splits);
+    int64_t blocks = (n + kSumThreads - 1) / kSumThreads;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(wgrad_slab_sum_kernel, dim3((unsigned)blocks), dim3(kSumThreads), 0, stream, slab, dw, (size_t)n, splits);
     SIMQ_CHECK_LAUNCH();
     return 0;
 }
 
-int launch_conv_wgrad(const float* x, const float* dy, float* dw, const ConvGeom& g, hipStream_t stream, const InBn& in, float* det_slab) {
+int launch_conv_wgrad(const float* x, const float* dy, float* dw, const ConvGeom& g, hipStream_t stream, const InBn& in, float* det_slab,
+                      int64_t det_slab_floats) {
     WgradArgs a;
-    a.x = x; a.dy = dy; a.dw = dw; a.slab = det_slab;
+    a.x = x; a.dy = dy; a.dw = dw; a.slab = det_slab; a.slab_floats = det_slab_floats;
     a.xscale = in.scale; a.xshift = in.shift;
     SIMQ_REQUIRE(!in.live, "conv_wgrad: BatchNorm-on-load takes the scale / shift the forward pass saved (not a live layer)");
     SIMQ_REQUIRE(!in.scale || g.Cin % 64 == 0, "conv_wgrad: BatchNorm-on-load needs Cin %% 64 == 0 (Cin=%d)", g.Cin);
@@ -379,7 +405,7 @@ int launch_wgrad_batched(const float* x, const float* dy, float* dw, int M, int 
     a.M = M; a.K = K;
     a.tilesI = a.tilesJ = a.rows_per_split = 0;
     a.gx = (long)M * K; a.gdy = (long)M * N; a.gdw = (long)N * K;
-    a.xscale = a.xshift = nullptr; a.slab = nullptr;
+    a.xscale = a.xshift = nullptr; a.slab = nullptr; a.slab_floats = 0;
     const double xb = 4.0 * M * K, yb = 4.0 * M * N;
     SIMQ_REQUIRE(xb < 4294967000.0 && yb < 4294967000.0, "wgrad_batched: operand exceeds the 4 GiB buffer-addressing limit");
     a.x_bytes = (unsigned)xb; a.dy_bytes = (unsigned)yb;

@@ -146,19 +146,29 @@ __global__ void __launch_bounds__(256) head_up_relu_conv3_kernel(const float* __
     }
 }
 
+// Deterministic plans: what a transition adds into dw3 / db3 / red, left by its block as plain stores (`part`) and added in transition
+// order by head_onehot_fold_kernel.  kHeadPartFloats floats per transition: [0] the output channel (-1: the transition adds nothing),
+// [1] g, [32 + ci] g * up, [64 + ci] s0, [96 + ci] s1.
+constexpr int kHeadPartFloats = 128;
+
 __global__ void __launch_bounds__(32) head_onehot_bwd_kernel(const float* __restrict__ ah2, const float* __restrict__ w3,
                                                              const int64_t* __restrict__ action, const float* __restrict__ q_sa,
                                                              const float* __restrict__ y, float grad_scale, float* ds1, float* dw3,
                                                              float* db3, int Cout, const float* __restrict__ ypre, int ypre_bf16,
-                                                             const float* __restrict__ mean, const float* __restrict__ invstd, double* red, int B) {
+                                                             const float* __restrict__ mean, const float* __restrict__ invstd, double* red, int B,
+                                                             float* part) {
     constexpr int W2 = 96, W1 = 48, CIN = 32;
-    // one block per transition (the default), or ONE block that walks the transitions in order (deterministic plans: the B atomic adds
-    // into dw3 / db3 / red then happen in a fixed order)
+    // one block per transition.  part == NULL (the default): the B blocks add into dw3 / db3 / red with atomics, in any order;
+    // part != NULL (deterministic plans): they leave their terms there and the fold adds them in transition order
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
     const int ci = threadIdx.x;
     const int64_t a = action[b];
     const int co = (int)(a / (W2 * W2)), p = (int)(a - (int64_t)co * W2 * W2);
-    if (co >= Cout) continue;
+    float* pt = part ? part + (size_t)b * kHeadPartFloats : nullptr;
+    if (co >= Cout) {
+        if (pt && ci == 0) reinterpret_cast<int*>(pt)[0] = -1;
+        continue;
+    }
     const int oy = p / W2, ox = p - oy * W2;
     const float d = q_sa[b] - y[b];
     const float g = fminf(fmaxf(d, -1.f), 1.f) * grad_scale;
@@ -171,8 +181,13 @@ __global__ void __launch_bounds__(32) head_onehot_bwd_kernel(const float* __rest
     const float* src = ah2 + (size_t)b * W1 * W1 * CIN + ci;
     const float up = ly0 * (lx0 * src[(y0 * W1 + x0) * CIN] + lx1 * src[(y0 * W1 + x1) * CIN]) +
                      ly1 * (lx0 * src[(y1 * W1 + x0) * CIN] + lx1 * src[(y1 * W1 + x1) * CIN]);
-    unsafeAtomicAdd(dw3 + co * CIN + ci, g * up);
-    if (ci == 0) unsafeAtomicAdd(db3 + co, g);
+    if (pt) {
+        pt[32 + ci] = g * up;
+        if (ci == 0) { reinterpret_cast<int*>(pt)[0] = co; pt[1] = g; }
+    } else {
+        unsafeAtomicAdd(dw3 + co * CIN + ci, g * up);
+        if (ci == 0) unsafeAtomicAdd(db3 + co, g);
+    }
     const float dx = g * w3[co * CIN + ci];
     float* base = ds1 + (size_t)b * W1 * W1 * CIN + ci;      // this thread owns channel ci of sample b: plain read-modify-write
     base[(y0 * W1 + x0) * CIN] += ly0 * lx0 * dx;
@@ -197,8 +212,70 @@ __global__ void __launch_bounds__(32) head_onehot_bwd_kernel(const float* __rest
             s1 += dz * ((yv - mu) * is);
         }
     }
-    unsafeAtomicAdd(red + ci, (double)s0);
-    unsafeAtomicAdd(red + CIN + ci, (double)s1);
+    if (pt) {
+        pt[64 + ci] = s0;
+        pt[96 + ci] = s1;
+    } else {
+        unsafeAtomicAdd(red + ci, (double)s0);
+        unsafeAtomicAdd(red + CIN + ci, (double)s1);
+    }
+    }
+}
+
+// One block adds the B transitions' terms onto the current contents of dw3 / db3 / red in the order b = 0 ... B-1: the sums the
+// atomics of one block walking the transitions would leave.  Four groups of 32 threads: thread ci of group 0 owns dw3[.][ci], of group 1
+// red[ci] (sum dz), of group 2 red[32 + ci] (sum dz * xhat); thread 0 of group 3 owns db3.  The adds are a dependent chain, the loads are not: kHeadFoldBatch
+// transitions' terms are loaded at a time, so the fold costs B / kHeadFoldBatch round trips.
+constexpr int kHeadFoldBatch = 16;
+
+__global__ void __launch_bounds__(128) head_onehot_fold_kernel(const float* __restrict__ part, float* dw3, float* db3, double* red, int Cout, int B) {
+    constexpr int CIN = 32;
+    const int ci = threadIdx.x & 31, role = threadIdx.x >> 5;      // 0: dw3, 1: red s0, 2: red s1, 3: db3
+    if ((role == 1 || role == 2) && !red) return;
+    if (role == 3 && ci != 0) return;
+    float acc[MAX_COUT];
+    double dacc = 0.0;
+#pragma unroll
+    for (int c = 0; c < MAX_COUT; ++c) acc[c] = 0.f;
+    if (role == 0) {
+#pragma unroll
+        for (int c = 0; c < MAX_COUT; ++c) if (c < Cout) acc[c] = dw3[c * CIN + ci];
+    } else if (role == 3) {
+#pragma unroll
+        for (int c = 0; c < MAX_COUT; ++c) if (c < Cout) acc[c] = db3[c];
+    } else {
+        dacc = red[(role - 1) * CIN + ci];
+    }
+    const int voff = role == 3 ? 1 : 32 * (role + 1) + ci;         // this thread's term within a transition's record
+    for (int b0 = 0; b0 < B; b0 += kHeadFoldBatch) {
+        int co[kHeadFoldBatch];
+        float v[kHeadFoldBatch];
+#pragma unroll
+        for (int k = 0; k < kHeadFoldBatch; ++k) {
+            const bool in = b0 + k < B;
+            const float* pt = part + (size_t)(in ? b0 + k : b0) * kHeadPartFloats;
+            co[k] = in ? reinterpret_cast<const int*>(pt)[0] : -1;
+            v[k] = pt[voff];                                       // (a skipped transition's terms are unwritten: loaded, never used)
+        }
+#pragma unroll
+        for (int k = 0; k < kHeadFoldBatch; ++k) {
+            if (co[k] < 0) continue;
+            if (role == 1 || role == 2) {
+                dacc += (double)v[k];
+            } else {
+#pragma unroll
+                for (int c = 0; c < MAX_COUT; ++c) if (co[k] == c) acc[c] += v[k];
+            }
+        }
+    }
+    if (role == 0) {
+#pragma unroll
+        for (int c = 0; c < MAX_COUT; ++c) if (c < Cout) dw3[c * CIN + ci] = acc[c];
+    } else if (role == 3) {
+#pragma unroll
+        for (int c = 0; c < MAX_COUT; ++c) if (c < Cout) db3[c] = acc[c];
+    } else {
+        red[(role - 1) * CIN + ci] = dacc;
     }
 }
 
@@ -245,14 +322,21 @@ int launch_head_upsample_q(const float* z, const float* bias, float* q, int B, i
 
 int launch_head_onehot_bwd(const float* ah2, const float* w3, const int64_t* action, const float* q_sa, const float* y,
                            float grad_scale, float* ds1, float* dw3, float* db3, int B, int Cout, hipStream_t stream,
-                           const float* ypre, int ypre_bf16, const float* mean, const float* invstd, double* red, int serial) {
+                           const float* ypre, int ypre_bf16, const float* mean, const float* invstd, double* red, float* det_part) {
     SIMQ_REQUIRE(Cout >= 1 && Cout <= MAX_COUT, "head_onehot_bwd: Cout=%d unsupported", Cout);
+    SIMQ_REQUIRE(B >= 1, "head_onehot_bwd: batch=%d", B);
     SIMQ_CHECK_HIP(hipMemsetAsync(ds1, 0, sizeof(float) * (size_t)B * 48 * 48 * 32, stream));
-    hipLaunchKernelGGL(head_onehot_bwd_kernel, dim3(serial ? 1 : B), dim3(32), 0, stream, ah2, w3, action, q_sa, y, grad_scale, ds1, dw3, db3, Cout,
-                       ypre, ypre_bf16, mean, invstd, red, B);
+    hipLaunchKernelGGL(head_onehot_bwd_kernel, dim3(B), dim3(32), 0, stream, ah2, w3, action, q_sa, y, grad_scale, ds1, dw3, db3, Cout,
+                       ypre, ypre_bf16, mean, invstd, red, B, det_part);
     SIMQ_CHECK_LAUNCH();
+    if (det_part) {
+        hipLaunchKernelGGL(head_onehot_fold_kernel, dim3(1), dim3(128), 0, stream, det_part, dw3, db3, red, Cout, B);
+        SIMQ_CHECK_LAUNCH();
+    }
     return 0;
 }
+
+int64_t head_onehot_det_part_bytes(int B) { return (int64_t)B * kHeadPartFloats * (int64_t)sizeof(float); }
 
 int launch_head_up_relu_conv3(const float* z2, const float* w, float* z, int B, int Cout, hipStream_t stream) {
     SIMQ_REQUIRE(Cout >= 1 && Cout <= MAX_COUT, "head_up_relu_conv3: Cout=%d unsupported", Cout);

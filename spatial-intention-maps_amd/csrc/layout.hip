@@ -78,6 +78,8 @@ Layout make_layout(const simq_plan* p, int B) {
     }
     L.wslab = p->precision == SIMQ_PREC_BF16 ? take(conv_wgrad_bf16_slab_bytes()) : -1;
     L.dslab = p->opt.deterministic ? take(kWgradDetSlabFloats * f) : -1;
+    L.dslab_stem = p->opt.deterministic ? take(stem_det_slab_floats(p->cin) * f) : -1;
+    L.hpart = p->opt.deterministic ? take(head_onehot_det_part_bytes(B)) : -1;
     L.total = off;
     return L;
 }

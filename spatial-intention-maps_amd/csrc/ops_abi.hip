@@ -308,6 +308,11 @@ int simq_conv2d_wgrad_bf16_slab(const float* d_x, const float* d_dy, float* d_dw
     return launch_conv_wgrad_bf16(xp, yp, nplanes, d_dw, g, st, static_cast<float*>(d_slab));
 }
 
+int simq_wgrad_slab_sum(const float* d_slab, float* d_dw, int64_t n, int splits, void* stream) {
+    SIMQ_REQUIRE(d_slab && d_dw && n >= 1 && splits >= 1, "wgrad_slab_sum: bad argument");
+    return launch_wgrad_slab_sum(d_slab, d_dw, n, splits, static_cast<hipStream_t>(stream));
+}
+
 int simq_upsample2x_fwd(const float* d_in, float* d_out, int batch, int h, int w, int c, void* stream) {
     return launch_upsample2x_fwd(d_in, d_out, batch, h, w, c, static_cast<hipStream_t>(stream));
 }

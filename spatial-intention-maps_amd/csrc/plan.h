@@ -121,6 +121,8 @@ struct Layout {
                      // on the side stream while the next block's BatchNorm backwards / dgrads write theirs (-1 otherwise)
     int64_t wslab;   // partial tiles of the image-tile bf16 weight-gradient kernel (plain-bf16 plans: 75.5 MB at any batch), -1 otherwise
     int64_t dslab;   // deterministic plans: per-split partial tiles of the pixel-split weight-gradient kernels (64 MB), -1 otherwise
+    int64_t dslab_stem;   // ... and a slab of the stem's own (stem_det_slab_floats(cin)): its weight gradient runs beside the last block's, -1 otherwise
+    int64_t hpart;   // deterministic plans: per-transition terms of the one-hot head backward (head_onehot_det_part_bytes), -1 otherwise
     int64_t fwd_total;   // bytes a workspace needs when only forward passes use it (no weight-gradient slabs)
     int64_t total;
 };
@@ -201,6 +203,7 @@ struct Ctx {
         return lazy1() || (p->precision == SIMQ_PREC_BF16 && p->opt.bn1_mask_from_preact && planes_only());
     }
     float* dslab() const { return L.dslab >= 0 ? f(L.dslab) : nullptr; }      // deterministic plans: slab of the pixel-split weight gradients
+    float* dslab_stem() const { return L.dslab_stem >= 0 ? f(L.dslab_stem) : nullptr; }
     InBn inbn_saved(const BnL& b) const { InBn in; in.scale = aux(b, 0); in.shift = aux(b, 1); return in; }     // backward pass
     // weight planes of conv cv: plain (OHWI) or flipped/transposed (dgrad)
     void wplanes(const ConvL& cv, bool transposed, const uint16_t* out[2]) const {
