@@ -19,4 +19,11 @@ Pinning: the reference ships no tests / golden vectors for this path
 (SURVEY.md section 4), so the oracle is pinned against the reference itself,
 imported in the build container by ``oracle/gen_golden.py`` (bit-exact
 comparison, then small fixtures are written to ``tests/golden/``).
+
+Tests that take only their seeded cases from here (``oracle.cases``,
+``oracle.fcn.state_from_numpy``, ``oracle.learner.apply_transform``) and
+recompute in fp64 from what the plan itself stored, not from this package's
+forward: ``tests/test_gpu_bf16_points.py`` (teacher-forced walks of the bf16
+plan) and ``tests/test_gpu_fp32_points.py`` (the same for the fp32 plan: three
+forward modes, traced backward, every parameter gradient, B = 5 / 8 / 32).
 """
