@@ -569,6 +569,38 @@ int simq_grid_distance_images(const uint8_t* d_grids, int64_t grids_bytes, const
                               simq_grid_problem* d_problems, float* d_out, int64_t out_floats, float pixels_per_meter,
                               int unreachable_to_max, float scale, int32_t* d_status, void* stream);
 
+/* The same images with the snap of OccupancyMap.shortest_path_image (envs.py:2513-2516, 2522-2523) on the device: the source of a
+ * problem is replaced by closest[:, src_i, src_j] before the search -- int32 [2][rows][cols] at d_closest + closest_offset, the layout
+ * simq_occupancy_maps writes and simq_grid_paths / simq_grid_distance_queries read -- so that a chain occupancy maps -> distance
+ * images needs no pixel on the host.  The search and the epilogue are those of simq_grid_distance_images, bit for bit.
+ * Upstream status: d_upstream (n_upstream int32 words on the device, e.g. the d_status simq_occupancy_maps wrote; NULL with
+ * n_upstream == 0) is read by the kernel, never by the host.  A problem with upstream >= 0 whose word d_upstream[upstream] is nonzero
+ * is not searched and its closest block is not read (the closest cells of a configuration space without a free cell are undefined):
+ * d_status[p] becomes that word as it is and every cell of the image SIMQ_GRID_SNAPPED_FILL.  The caller, who owns d_upstream, tells
+ * a passed-on word from the codes below by looking at both arrays.
+ * `problems`: host array of n descriptors, validated here before anything is copied or launched (rows, cols >= 1, rows * cols <
+ * SIMQ_GRID_MAX_CELLS; the source as given inside the grid; grid, closest block and image inside the declared extent of their
+ * buffers; upstream -1 or below n_upstream; no two images overlapping; nothing the launch writes -- d_out, d_status, d_problems --
+ * sharing a byte with any other buffer of the call; 4-byte alignment of d_closest, d_out, d_upstream and d_status, 8 of d_problems) and
+ * copied to d_problems (n descriptors) on `stream`.  Several problems may share a grid and a closest block.  d_status[n] (int32): 0 =
+ * converged, 1 = the cap of passes was hit (cannot happen, as above), 2 = bad descriptor (the kernel checks again and writes nothing
+ * else), 3 = the snapped pixel lies outside the grid or on a cell that is not free: nothing is searched, the image is filled with
+ * SIMQ_GRID_SNAPPED_FILL and every other problem of the call is unaffected; or the upstream word. */
+typedef struct simq_grid_snapped_problem {
+    int64_t grid_offset;        /* byte offset of the problem's [rows][cols] uint8 grid in d_grids */
+    int64_t closest_offset;     /* int32 offset of its [2][rows][cols] closest cells in d_closest */
+    int64_t out_offset;         /* float offset of its [rows][cols] fp32 image in d_out */
+    int32_t rows, cols;
+    int32_t src_i, src_j;       /* the pixel before the snap */
+    int32_t upstream;           /* index of its word in d_upstream, or -1 */
+    int32_t reserved_;
+} simq_grid_snapped_problem;
+#define SIMQ_GRID_SNAPPED_FILL 0.0f
+int simq_grid_distance_images_snapped(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* d_closest, int64_t closest_ints,
+                                      const simq_grid_snapped_problem* problems, int n, simq_grid_snapped_problem* d_problems,
+                                      float* d_out, int64_t out_floats, float pixels_per_meter, int unreachable_to_max, float scale,
+                                      const int32_t* d_upstream, int n_upstream, int32_t* d_status, void* stream);
+
 /* ---- shortest-path waypoints: SPFA's parents and the dense path (shortest_paths.pyx:69-137 GridGraph._spfa and the walk of
  * GridGraph.shortest_path; the front half of OccupancyMap.shortest_path, envs.py:2477-2490) --------------------------------------
  * One problem = one grid [rows][cols] of uint8 (free where != 0), a source pixel and a target pixel; one wavefront emulates the

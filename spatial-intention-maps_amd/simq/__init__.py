@@ -50,6 +50,8 @@ _LAZY = {
     'camera_geometry': ('.observation', 'camera_geometry'),
     'observation_update': ('.observation', 'observation_update'),
     'observe': ('.observation', 'observe'),
+    'BatchedMapper': ('.mapper', 'BatchedMapper'),
+    'RobotState': ('.mapper', 'RobotState'),
     'state_output_visualizations': ('.visualization', 'state_output_visualizations'),
     'state_output_visualization': ('.visualization', 'state_output_visualization'),
     'state_visualization': ('.visualization', 'state_visualization'),

@@ -163,6 +163,8 @@ _SIGS = {
     'simq_comm_destroy': (c_int, [c_void_p]),
     'simq_grid_distance_images': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_float, c_int, c_float,
                                           c_void_p, c_void_p]),
+    'simq_grid_distance_images_snapped': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_float,
+                                                  c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     'simq_grid_paths': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     'simq_grid_distance_queries': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64,

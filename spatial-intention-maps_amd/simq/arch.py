@@ -5,6 +5,7 @@ interchange (reference: networks.py:7-14, resnet.py:52-91, policies.py:39).
 The device-side layout (flat NHWC/OHWI parameter buffer) comes from the C-ABI
 (`simq_param_tensor_info`); this module only knows reference names and shapes.
 """
+import math
 
 PREFIX = 'module.'
 STATE_WIDTH = 96                       # envs.py:2010 Mapper.LOCAL_MAP_PIXEL_WIDTH
@@ -23,6 +24,27 @@ def get_num_output_channels(robot_type):
 def get_action_space(robot_type):
     """envs.py:374-376."""
     return get_num_output_channels(robot_type) * STATE_WIDTH * STATE_WIDTH
+
+
+# ---- what Mapper / OccupancyMap read of the robot classes and the camera (simq.BatchedMapper) ---------------------------------------
+ROBOT_HALF_WIDTH = 0.03                # envs.py:803 Robot.HALF_WIDTH
+ROBOT_BACKPACK_OFFSET = -0.0135        # envs.py:804 Robot.BACKPACK_OFFSET
+ROBOT_BASE_LENGTH = {                  # envs.py:805 Robot.BASE_LENGTH, 1059 (5 mm blade), 1279 (6 mm offset)
+    'pushing_robot': 0.065 + 0.005, 'lifting_robot': 0.065, 'throwing_robot': 0.065 + 0.006, 'rescue_robot': 0.065,
+}
+LOCAL_MAP_PIXELS_PER_METER = 96.0      # envs.py:2012 Mapper.LOCAL_MAP_PIXELS_PER_METER
+SEG_VALUES = {                         # envs.py:1880-1889 Camera.SEG_VALUES
+    'floor': 1.0 / 8, 'obstacle': 2.0 / 8, 'receptacle': 3.0 / 8, 'cube': 4.0 / 8,
+    'robot_group_1': 5.0 / 8, 'robot_group_2': 6.0 / 8, 'robot_group_3': 7.0 / 8, 'robot_group_4': 8.0 / 8,
+}
+
+
+def get_robot_radius(robot_type):
+    """The class's RADIUS: envs.py:807-808 (Robot), 1060-1061 (PushingRobot), 1280-1281 (ThrowingRobot)."""
+    if robot_type not in ROBOT_BASE_LENGTH:
+        raise Exception(robot_type)
+    end_effector_location = ROBOT_BACKPACK_OFFSET + ROBOT_BASE_LENGTH[robot_type]
+    return math.sqrt(ROBOT_HALF_WIDTH**2 + end_effector_location**2)
 
 
 def _bn(name, c):

@@ -1,0 +1,508 @@
+"""The Mapper of every robot of many environments as one object on the GPU: ``Mapper.update`` and ``Mapper.get_state`` in batches.
+
+The reference gives every robot its own ``Mapper`` (envs.py:2009-2406) and every Mapper its ``OccupancyMap`` (envs.py:2408-2554); after
+each environment step it calls ``update`` and ``get_state`` on them one by one, on the host.  ``BatchedMapper`` stands for all those
+pairs of E environments: a *mapper* m is one (environment, robot) pair, the maps of all M mappers are rows of device tensors this
+object owns, and the two calls run the batched operators of this package as one chain on them:
+
+    update       simq_observation_update  ->  simq_occupancy_maps                                     (envs.py:2053-2065, 2444-2459)
+    get_states   simq_grid_distance_images_snapped  ->  simq_intention_maps  ->  simq_local_state_images     (envs.py:2067-2112)
+
+Each stage is one launch however many mappers are named, reads the tensors of the stage before it where they lie, and leaves its
+status words on the device; the call reads them back once, at its end.  What lets the read-back wait is the upstream status of
+the snapped distance images (include/simq.h): a mapper whose configuration space has no free cell -- its closest cells are undefined
+-- is not searched.  Douglas-Peucker and ``store_new_action`` stay on the host (DESIGN.md sections 13 and 17).
+"""
+import collections
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _batch, arch, grid_paths, intention_drawing, local_maps, observation, occupancy
+from ._lib import SimqError, lib, ptr, stream_ptr
+
+FLAGS = ('use_robot_map', 'use_distance_to_receptacle_map', 'use_shortest_path_to_receptacle_map', 'use_shortest_path_map', 'use_history_map',
+         'use_intention_map', 'use_intention_channels')
+CHANNEL_ENCODINGS = ('spatial', 'nonspatial')
+WITH_CUBE = 'lifting_robot_with_cube'                   # the key of envs.py:2037
+NOT_UPDATED = 4                                        # occupancy status of a mapper that had no update since construction / reset
+
+# What Mapper.get_state reads of one robot (envs.py:2199-2203, 2250-2270, 2303-2317, 2350-2373): get_position(), get_heading(), the
+# class, lift_state (LiftingRobot), is_idle(), target_end_effector_position, controller.get_intention_path() / get_history_path().
+# An idle robot needs no target and no paths; the paths are read only by the encodings that draw them.
+RobotState = collections.namedtuple('RobotState', ('position', 'heading', 'robot_type', 'lift_state', 'idle', 'target', 'intention_path',
+                                                   'history_path'), defaults=(None, False, None, None, None))
+
+
+def round_up_to_even(x):
+    """envs.py:2404-2406."""
+    return 2 * math.ceil(x / 2)
+
+
+def padded_room_shape(room_width, room_length):
+    """The shape of Mapper.create_padded_room_zeros (envs.py:2382-2388)."""
+    return (round_up_to_even(room_width * arch.LOCAL_MAP_PIXELS_PER_METER + math.sqrt(2) * arch.STATE_WIDTH),
+            round_up_to_even(room_length * arch.LOCAL_MAP_PIXELS_PER_METER + math.sqrt(2) * arch.STATE_WIDTH))
+
+
+def room_mask(room_width, room_length):
+    """OccupancyMap._create_room_mask (envs.py:2467-2475)."""
+    mask = np.zeros(padded_room_shape(room_width, room_length), np.uint8)
+    room_length_pixels = round_up_to_even((room_length - 2 * arch.ROBOT_HALF_WIDTH) * arch.LOCAL_MAP_PIXELS_PER_METER)
+    room_width_pixels = round_up_to_even((room_width - 2 * arch.ROBOT_HALF_WIDTH) * arch.LOCAL_MAP_PIXELS_PER_METER)
+    start_i = int(mask.shape[0] / 2 - room_width_pixels / 2)
+    start_j = int(mask.shape[1] / 2 - room_length_pixels / 2)
+    mask[start_i:start_i + room_width_pixels, start_j:start_j + room_length_pixels] = 1
+    return mask
+
+
+def distance_to_receptacle_map(shape, receptacle_position, scale):
+    """Mapper._create_global_distance_to_receptacle_map (envs.py:2277-2285), pixel by pixel in Python floats as there: the position of
+    envs.py:2398-2402, the distance of envs.py:2556-2557, stored as float32, then scaled in place."""
+    rows, cols = shape
+    ppm = arch.LOCAL_MAP_PIXELS_PER_METER
+    global_map = np.zeros(shape, np.float32)
+    for i in range(rows):
+        pos_y = (rows / 2 - (i + 0.5)) / ppm
+        for j in range(cols):
+            pos_x = ((j + 0.5) - cols / 2) / ppm
+            global_map[i, j] = _distance((pos_x, pos_y), receptacle_position)
+    global_map *= scale
+    return global_map
+
+
+def channel_names(flags, intention_channel_encoding='spatial', n_robots=1):
+    """The channels of Mapper.get_state in its order (envs.py:2067-2112) for a dict of use_* flags; the intention channels of the
+    other robots come closest first (envs.py:2350-2354): one per robot ('spatial') or two ('nonspatial')."""
+    names = ['overhead']
+    names += [n for f, n in zip(FLAGS[:6], ('robots', 'distance_to_receptacle', 'shortest_path_to_receptacle', 'shortest_path', 'history',
+                                            'intention')) if flags.get(f)]
+    if flags.get('use_intention_channels'):
+        per = 1 if intention_channel_encoding == 'spatial' else 2
+        names += ['intention_channel_%d' % k for k in range(per * (n_robots - 1))]
+    return names
+
+
+def _distance(p1, p2):
+    return math.sqrt((p2[0] - p1[0])**2 + (p2[1] - p1[1])**2)                              # envs.py:2556-2557
+
+
+def _per_env(value, E, what, scalar):
+    """`value` for each of E environments: one value for all (scalar(value) is true) or a sequence of E."""
+    if scalar(value):
+        return [value] * E
+    values = list(value)
+    if len(values) != E:
+        raise ValueError('%s is one value or one per environment: %d values for %d environments' % (what, len(values), E))
+    return values
+
+
+def _is_number(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+
+class BatchedMapper:
+    """The Mapper + OccupancyMap pairs of every robot of E environments.
+
+    room_width, room_length: env.room_width, env.room_length -- one value, or one per environment.  robot_types: per environment the
+    robots' types in env.robots' order ('pushing_robot', 'lifting_robot', 'throwing_robot', 'rescue_robot'); group_indices: per
+    environment each robot's group_index (omitted: 0).  robot_masks: {robot type: float32 [96, 96] mask} plus
+    'lifting_robot_with_cube' when a lifting robot is present -- Mapper.robot_masks (envs.py:2031-2037), from
+    Mapper._create_robot_mask.  receptacle_position: env.receptacle_position, one (x, y[, z]) or one per environment.  The use_*
+    switches (FLAGS) and the remaining keywords are the environment's attributes of the same names; seg_values: Camera.SEG_VALUES.
+
+    Mapper m = (environment e, robot r) has the index `mapper_index(e, r)`: environments in order, robots in env.robots' order.  The
+    persistent maps live in one device buffer per kind and are exposed as `overhead` fp32 [M, rows, cols]
+    (global_overhead_map_without_robots), `occupancy`, `configuration_space`, `cspace_thin` uint8 [M, rows, cols] and
+    `closest_cspace_indices` int32 [M, 2, rows, cols] when every environment has the same room, otherwise as lists of M views
+    ([rows_m, cols_m], [2, rows_m, cols_m]) into those buffers.  `occupancy_status` int32 [M] holds the status word of each mapper's
+    last configuration space (NOT_UPDATED before the first); `distance_to_receptacle_maps` (use_distance_to_receptacle_map) one
+    fp32 [rows, cols] device map per environment (environments of one room and receptacle share it)."""
+
+    def __init__(self, room_width, room_length, robot_types, robot_masks, group_indices=None, receptacle_position=None, *,
+                 use_robot_map=True, use_distance_to_receptacle_map=False, use_shortest_path_to_receptacle_map=False,
+                 use_shortest_path_map=False, use_history_map=False, use_intention_map=False, use_intention_channels=False,
+                 intention_map_encoding='ramp', intention_map_scale=1.0, intention_map_line_thickness=2, intention_channel_encoding='spatial',
+                 intention_channel_nonspatial_scale=0.1, distance_to_receptacle_map_scale=0.25, shortest_path_map_scale=0.25, seg_values=None):
+        given = locals()
+        self.flags = {f: bool(given[f]) for f in FLAGS}
+        try:
+            self.robot_types = [[str(t) for t in env] for env in robot_types]
+        except TypeError:
+            raise ValueError('robot_types holds, per environment, the list of its robots\' types') from None
+        if not self.robot_types or any(not env for env in self.robot_types):
+            raise ValueError('BatchedMapper needs at least one environment and one robot in each')
+        E = self.num_envs = len(self.robot_types)
+        for env in self.robot_types:
+            for t in env:
+                if t not in arch.ROBOT_BASE_LENGTH:
+                    raise ValueError('robot type %r: choose from %s' % (t, sorted(arch.ROBOT_BASE_LENGTH)))
+        if group_indices is None:
+            group_indices = [[0] * len(env) for env in self.robot_types]
+        self.group_indices = [[int(g) for g in env] for env in group_indices]
+        if [len(env) for env in self.group_indices] != [len(env) for env in self.robot_types]:
+            raise ValueError('group_indices must hold one group index for each robot of robot_types: %s robots, %s group indices'
+                             % ([len(env) for env in self.robot_types], [len(env) for env in self.group_indices]))
+        self.seg_values = dict(arch.SEG_VALUES if seg_values is None else seg_values)
+        for env in self.group_indices:
+            for g in env:
+                if 'robot_group_%d' % (g + 1) not in self.seg_values:
+                    raise ValueError('group index %d has no segmentation value robot_group_%d' % (g, g + 1))
+        if intention_map_encoding not in intention_drawing.ENCODINGS[:4]:
+            raise ValueError('intention_map_encoding %r: choose from %s' % (intention_map_encoding, list(intention_drawing.ENCODINGS[:4])))
+        if intention_channel_encoding not in CHANNEL_ENCODINGS:
+            raise ValueError('intention_channel_encoding %r: choose from %s' % (intention_channel_encoding, list(CHANNEL_ENCODINGS)))
+        self.intention_map_encoding, self.intention_channel_encoding = intention_map_encoding, intention_channel_encoding
+        self.intention_map_scale, self.intention_map_line_thickness = intention_map_scale, int(intention_map_line_thickness)
+        self.intention_channel_nonspatial_scale = intention_channel_nonspatial_scale
+        self.distance_to_receptacle_map_scale, self.shortest_path_map_scale = distance_to_receptacle_map_scale, shortest_path_map_scale
+        self.room_widths = [float(w) for w in _per_env(room_width, E, 'room_width', _is_number)]
+        self.room_lengths = [float(w) for w in _per_env(room_length, E, 'room_length', _is_number)]
+        if self.flags['use_distance_to_receptacle_map'] or self.flags['use_shortest_path_to_receptacle_map']:
+            if receptacle_position is None:                                                # envs.py:2050-2051
+                raise ValueError('use_distance_to_receptacle_map and use_shortest_path_to_receptacle_map need receptacle_position')
+            if any(t == 'rescue_robot' for env in self.robot_types for t in env):         # envs.py:2047-2049
+                raise ValueError('an environment with a rescue robot has no receptacle maps')
+        self.receptacle_positions = [None] * E
+        if receptacle_position is not None:
+            self.receptacle_positions = [tuple(float(x) for x in p) for p in
+                                         _per_env(receptacle_position, E, 'receptacle_position', lambda v: _is_number(v[0]))]
+        if self.flags['use_intention_channels'] and len(set(len(env) for env in self.robot_types)) != 1:
+            raise ValueError('use_intention_channels gives one channel set per other robot: every environment needs the same number of '
+                             'robots, got %s' % [len(env) for env in self.robot_types])
+
+        # the bank of masks: each type present, then the lifting robot carrying a cube (envs.py:2031-2037)
+        names = sorted(set(t for env in self.robot_types for t in env))
+        if 'lifting_robot' in names:
+            names.append(WITH_CUBE)
+        bank = []
+        for name in names:
+            m = robot_masks.get(name) if isinstance(robot_masks, dict) else None
+            if not isinstance(m, np.ndarray) or m.dtype != np.float32 or m.shape != (arch.STATE_WIDTH, arch.STATE_WIDTH):
+                raise ValueError('robot_masks[%r] must be a float32 [96, 96] array (Mapper._create_robot_mask)' % name)
+            bank.append(m)
+        self.mask_index = {name: k for k, name in enumerate(names)}
+        self.env_begin = np.concatenate([[0], np.cumsum([len(env) for env in self.robot_types])]).tolist()
+        M = self.num_mappers = self.env_begin[-1]
+        self.env_of = [e for e, env in enumerate(self.robot_types) for _ in env]
+        self.env_shapes = [padded_room_shape(w, l) for w, l in zip(self.room_widths, self.room_lengths)]
+        self.shapes = [self.env_shapes[e] for e in self.env_of]
+        self.radius = [math.floor(arch.get_robot_radius(t) * arch.LOCAL_MAP_PIXELS_PER_METER) for env in self.robot_types for t in env]   # envs.py:2420
+        self.thin_radius = math.ceil(arch.ROBOT_HALF_WIDTH * arch.LOCAL_MAP_PIXELS_PER_METER)                                            # envs.py:2428
+        self.channels = channel_names(self.flags, intention_channel_encoding, len(self.robot_types[0]))
+        self.num_channels = len(self.channels)
+        self.mask_bank = np.stack(bank)
+
+        # the device tensors come after the argument checks, which need no device; without one the object still checks the arguments
+        # of its calls, and then says so
+        self.device, self.stage_maps = None, {}
+        if torch.cuda.is_available():
+            self._allocate()
+
+    def _allocate(self):
+        dev = self.device = _batch.device('batched mappers')
+        E, M = self.num_envs, self.num_mappers
+        cells = [r * c for r, c in self.shapes]
+        self._at = np.concatenate([[0], np.cumsum(cells)]).tolist()                       # cell offset of mapper m's maps; [M]: all cells
+        total = self._at[M]
+        # occupancy maps and room masks are one uint8 buffer: simq_occupancy_maps reads both from one base, where they lie
+        rooms = {}
+        for e in range(E):
+            key = (self.room_widths[e], self.room_lengths[e])
+            if key not in rooms:
+                rooms[key] = (total + sum(m.size for _, m in rooms.values()), room_mask(*key))
+        self._mask_at = [rooms[(self.room_widths[e], self.room_lengths[e])][0] for e in self.env_of]
+        self._bytes = torch.zeros(total + sum(m.size for _, m in rooms.values()), dtype=torch.uint8, device=dev)
+        for at, m in rooms.values():
+            self._bytes[at:at + m.size].copy_(torch.from_numpy(m.reshape(-1)))
+        self._overhead = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._cspace = torch.zeros(total, dtype=torch.uint8, device=dev)
+        self._thin = torch.zeros(total, dtype=torch.uint8, device=dev)
+        self._closest = torch.zeros(2 * total, dtype=torch.int32, device=dev)
+        self.occupancy_status = torch.full((M,), NOT_UPDATED, dtype=torch.int32, device=dev)
+        self.masks = torch.from_numpy(self.mask_bank).to(dev)
+        self.uniform = len(set(self.shapes)) == 1
+
+        def rows_of(flat, per=()):
+            if self.uniform:
+                return flat[:(2 if per else 1) * total].view((M,) + per + self.shapes[0])
+            return [self._view(flat, m, per) for m in range(M)]
+        self.occupancy = rows_of(self._bytes)
+        self.room_masks = [self._bytes[at:at + r * c].view(r, c) for at, (r, c) in zip(self._mask_at, self.shapes)]
+        self.overhead = rows_of(self._overhead)
+        self.configuration_space, self.cspace_thin = rows_of(self._cspace), rows_of(self._thin)
+        self.closest_cspace_indices = rows_of(self._closest, (2,))
+        self.distance_to_receptacle_maps = None
+        if self.flags['use_distance_to_receptacle_map']:
+            made = {}
+            for e in range(E):
+                key = (self.env_shapes[e], self.receptacle_positions[e])
+                if key not in made:
+                    made[key] = torch.from_numpy(distance_to_receptacle_map(key[0], key[1], self.distance_to_receptacle_map_scale)).to(dev)
+            self.distance_to_receptacle_maps = [made[(self.env_shapes[e], self.receptacle_positions[e])] for e in range(E)]
+
+    # ---- indices ---------------------------------------------------------------------------------------------------------------
+    def mapper_index(self, env, robot):
+        if not (0 <= env < self.num_envs and 0 <= robot < len(self.robot_types[env])):
+            raise ValueError('no robot %d in environment %d' % (robot, env))
+        return self.env_begin[env] + robot
+
+    def _mappers(self, mappers):
+        if mappers is None:
+            return list(range(self.num_mappers))
+        ms = [int(m) for m in mappers]
+        if not ms or any(m < 0 or m >= self.num_mappers for m in ms) or len(set(ms)) != len(ms):
+            raise ValueError('mappers must name distinct mappers in 0 .. %d, got %s' % (self.num_mappers - 1, ms))
+        return ms
+
+    def _named(self, bad, ms):
+        return ', '.join('%d (environment %d, robot %d)' % (ms[p], self.env_of[ms[p]], ms[p] - self.env_begin[self.env_of[ms[p]]]) for p in bad[:8])
+
+    # ---- Mapper.__init__ at an episode start -------------------------------------------------------------------------------------
+    def reset(self, envs=None):
+        """Zero the maps of every mapper of the named environments (all when omitted), as the new Mapper objects of an episode start
+        (envs.py:2025, 2416); every other environment's maps are not touched."""
+        envs = list(range(self.num_envs)) if envs is None else [int(e) for e in envs]
+        for e in envs:
+            if not 0 <= e < self.num_envs:
+                raise ValueError('no environment %d (0 .. %d)' % (e, self.num_envs - 1))
+        if self.device is None:
+            self._allocate()
+        for e in envs:
+            a, b = self.env_begin[e], self.env_begin[e + 1]
+            lo, hi = self._at[a], self._at[b]
+            for flat in (self._overhead, self._bytes, self._cspace, self._thin):
+                flat[lo:hi].zero_()
+            self._closest[2 * lo:2 * hi].zero_()
+            self.occupancy_status[a:b].fill_(NOT_UPDATED)
+
+    # ---- Mapper.update + OccupancyMap.update ---------------------------------------------------------------------------------
+    def update(self, depth, ids, geometries, id_ranges, mappers=None):
+        """Mapper.update (envs.py:2053-2065) with OccupancyMap.update (envs.py:2444-2459) for the named mappers (all when omitted):
+        frame p of `depth` / `ids` is the camera frame of mapper mappers[p]; the four arguments are simq.observation_update's.  The
+        observation scatter writes `overhead` and `occupancy` in place, the second launch `configuration_space`, `cspace_thin` and
+        `closest_cspace_indices`; the status words of both are read back once.  Raises SimqError naming the mappers whose frame held
+        a point that is not finite (their maps are unchanged) or whose configuration space has no free cell (status 1 of
+        simq_occupancy_maps: their closest cells are undefined, and get_states reports them until an update succeeds); every
+        other mapper of the call is updated."""
+        ms = self._mappers(mappers)
+        if self.device is None:
+            self._allocate()
+        P, dev, M = len(ms), self.device, self.num_mappers
+        st_obs = observation._enqueue(depth, ids, geometries, id_ranges, [self._view(self._overhead, m) for m in ms],
+                                      [self._view(self._bytes, m) for m in ms])
+        probs = (occupancy.OccupancyProblem * P)(*[occupancy.OccupancyProblem(self._at[m], self._mask_at[m], self._at[m], self.shapes[m][0],
+                                                                               self.shapes[m][1], self.radius[m], self.thin_radius) for m in ms])
+        d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+        whole = ms == list(range(M))
+        st_occ = self.occupancy_status if whole else torch.empty(P, dtype=torch.int32, device=dev)
+        lib.call('simq_occupancy_maps', ptr(self._bytes), ctypes.c_int64(self._bytes.numel()), probs, P, ptr(d_probs), ptr(self._cspace),
+                 ptr(self._thin), ctypes.c_int64(self._cspace.numel()), ptr(self._closest), ctypes.c_int64(self._closest.numel()), ptr(st_occ),
+                 stream_ptr(dev))
+        if not whole:
+            self.occupancy_status[torch.as_tensor(ms, dtype=torch.int64).to(dev)] = st_occ
+        bad, codes = _batch.bad_problems(torch.cat([st_obs, st_occ]))                       # the one read-back of the call
+        if bad.size:
+            said = []
+            for lo, name, what in ((0, 'simq_observation_update', 'hold a point that is not finite, their maps are unchanged'),
+                                   (P, 'simq_occupancy_maps', 'have a configuration space without a free cell, their closest cells are undefined')):
+                mine = [(int(p) - lo, int(c)) for p, c in zip(bad, codes) if lo <= p < lo + P]
+                first, other = [p for p, c in mine if c == 1], [(p, c) for p, c in mine if c != 1]
+                if first:
+                    said.append('%s: mapper(s) %s %s' % (name, self._named(first, ms), what))
+                if other:
+                    said.append('%s: status %s at mapper(s) %s' % (name, [c for _, c in other][:8], self._named([p for p, _ in other], ms)))
+            raise SimqError('BatchedMapper.update: ' + '; '.join(said))
+
+    def _view(self, flat, m, per=()):
+        k = 2 if per else 1
+        return flat[k * self._at[m]:k * self._at[m + 1]].view(per + self.shapes[m])
+
+    # ---- Mapper.get_state ------------------------------------------------------------------------------------------------------
+    def _robots(self, robots, envs):
+        try:
+            n = len(robots)
+        except TypeError:
+            raise ValueError('robots holds one list of RobotState per environment') from None
+        if n != self.num_envs:
+            raise ValueError('robots holds one list of RobotState per environment: %d lists for %d environments' % (n, self.num_envs))
+        out = {}
+        for e in envs:
+            states = [r if isinstance(r, RobotState) else RobotState(*r) for r in robots[e]]
+            if len(states) != len(self.robot_types[e]):
+                raise ValueError('environment %d has %d robots, got %d robot states' % (e, len(self.robot_types[e]), len(states)))
+            for k, (r, t) in enumerate(zip(states, self.robot_types[e])):
+                if r.robot_type is not None and r.robot_type != t:
+                    raise ValueError('environment %d, robot %d is a %s, got the state of a %s' % (e, k, t, r.robot_type))
+            out[e] = states
+        return out
+
+    def _stamps(self, e, states):
+        """The robots of environment e as the robot map and the overhead map draw them (envs.py:2250-2275)."""
+        stamps = []
+        for r, t, g in zip(states, self.robot_types[e], self.group_indices[e]):
+            own = self.mask_index[t]
+            lifting = t == 'lifting_robot' and r.lift_state == 'lifting'
+            stamps.append(local_maps.RobotStamp(r.position, r.heading, self.mask_index[WITH_CUBE] if lifting else own,
+                                                self.seg_values['robot_group_%d' % (g + 1)],
+                                                0.5 if t == 'lifting_robot' and not lifting else 1.0, own))
+        return stamps
+
+    def _drawn(self, states, own, encoding):
+        """What Mapper._create_global_intention_or_history_map draws for robot `own` of an environment (envs.py:2303-2317)."""
+        out = []
+        for k, r in enumerate(states):
+            if k == own or r.idle:
+                continue
+            path = r.target if encoding == 'circle' else r.history_path if encoding == 'history' else r.intention_path
+            if path is None:
+                raise ValueError('a robot that is not idle needs its %s for the %r encoding' % (
+                    'target' if encoding == 'circle' else 'history_path' if encoding == 'history' else 'intention_path', encoding))
+            out.append(path)
+        return out
+
+    def get_states(self, robots, mappers=None, out=None):
+        """Mapper.get_state() (envs.py:2067-2112) for the named mappers (all when omitted): a float32 [P, 96, 96, C] device tensor,
+        state p that of mapper mappers[p], the channels in `self.channels`' order.  robots: per environment the RobotState of each
+        robot, in env.robots' order (only the environments of the named mappers are read).  out: a contiguous float32 device
+        tensor [P, 96, 96, C] to write into -- a batch buffer, a slice of a replay ring's `states`; every element is written.
+
+        The distance images and the states are one launch each; the drawn maps one launch per room shape among the named mappers
+        (simq_intention_maps draws maps of one shape).  Raises ValueError for a wrong robot count or `out`; SimqError, after the
+        whole chain has run, naming the mappers whose distance images could not be computed (no successful update yet, a
+        configuration space without a free cell): their distance channels come from images of zeros, every other mapper's state is
+        right."""
+        ms = self._mappers(mappers)
+        P, C = len(ms), self.num_channels
+        want = (P, arch.STATE_WIDTH, arch.STATE_WIDTH, C)
+        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == want and out.is_contiguous()):
+            raise ValueError('out must be a contiguous float32 device tensor of shape %s, got %s' % (
+                want, '%s %s' % (out.dtype, tuple(out.shape)) if isinstance(out, torch.Tensor) else type(out).__name__))
+        states = self._robots(robots, sorted(set(self.env_of[m] for m in ms)))
+        f = self.flags
+        own = [(self.env_of[m], m - self.env_begin[self.env_of[m]]) for m in ms]
+        pixel = local_maps.position_to_pixel_indices
+
+        # ---- the host side of every stage first: a wrong argument launches nothing
+        sources, grid = [], []                                   # stage 1: (pixel, mapper) of every distance image
+        if f['use_shortest_path_to_receptacle_map']:
+            sources += [pixel(self.receptacle_positions[e][0], self.receptacle_positions[e][1], self.env_shapes[e]) for e, _ in own]
+            grid += ms
+        if f['use_shortest_path_map']:
+            sources += [pixel(states[e][r].position[0], states[e][r].position[1], self.env_shapes[e]) for e, r in own]
+            grid += ms
+        jobs, order = [], {}                                     # stage 2: (key, problem, paths, encoding) of every drawn map
+        if f['use_history_map']:
+            jobs += [(('history', p), p, self._drawn(states[e], r, 'history'), 'history') for p, (e, r) in enumerate(own)]
+        if f['use_intention_map']:
+            jobs += [(('intention', p), p, self._drawn(states[e], r, self.intention_map_encoding), self.intention_map_encoding)
+                     for p, (e, r) in enumerate(own)]
+        constants = {}
+        if f['use_intention_channels']:
+            for p, (e, r) in enumerate(own):
+                me = states[e][r]
+                dists = [_distance(me.position, other.position) for other in states[e]]
+                order[p] = [int(k) for k in np.argsort(dists) if k != r]                       # envs.py:2350-2358
+                for q, k in enumerate(order[p]):
+                    other = states[e][k]
+                    if not other.idle and other.target is None:
+                        raise ValueError('a robot that is not idle needs its target for the intention channels')
+                    if self.intention_channel_encoding == 'spatial':                          # envs.py:2360-2366
+                        jobs.append((('channel', p, q), p, [] if other.idle else [other.target], 'circle'))
+                        continue
+                    relative_position = (0, 0)                                              # envs.py:2368-2375
+                    if not other.idle:
+                        dist = _distance(me.position, other.target)
+                        theta = me.heading - math.atan2(other.target[1] - me.position[1], other.target[0] - me.position[0])
+                        relative_position = (dist * math.sin(theta), dist * math.cos(theta))
+                    constants[(p, q)] = [float(np.float32(self.intention_channel_nonspatial_scale * coord)) for coord in relative_position]
+        if self.device is None:
+            self._allocate()
+        if out is not None and out.device != self.device:
+            raise ValueError('out must be a contiguous float32 device tensor of shape %s on %s' % (want, self.device))
+
+        # ---- stage 1: the distance images, every source snapped through the closest cells on the device
+        status, images = None, []
+        if sources:
+            grids = [self._view(self._cspace, m) for m in range(self.num_mappers)]
+            closest = [self._view(self._closest, m, (2,)) for m in range(self.num_mappers)]
+            images, status, uniform, shapes, _ = grid_paths._enqueue(
+                grids, sources, arch.LOCAL_MAP_PIXELS_PER_METER, True, self.shortest_path_map_scale, None, grid, closest, grid,
+                self.occupancy_status, grid)
+            images = list(images) if uniform else _batch.views(images.view(-1), shapes)
+
+        # ---- stage 2: history maps, intention maps and the maps behind the spatial intention channels: one launch per room shape
+        drawn = {}
+        for shape in sorted(set(self.shapes[ms[p]] for _, p, _, _ in jobs)):
+            mine = [j for j in jobs if self.shapes[ms[j[1]]] == shape]
+            args, maps, keep = intention_drawing._prepare([j[2] for j in mine], shape, [j[3] for j in mine], self.intention_map_scale,
+                                                          self.intention_map_line_thickness, None)
+            lib.call('simq_intention_maps', *args)
+            del keep
+            drawn.update({j[0]: maps[k] for k, j in enumerate(mine)})
+
+        # ---- stage 3: crop and rotation of every channel into the states
+        maps, index = [], {}
+
+        def use(key, tensor):
+            if key not in index:
+                index[key] = len(maps)
+                maps.append(tensor)
+            return index[key]
+        channels = []
+        for p, (e, r) in enumerate(own):
+            ch, d = [('overhead', use(('overhead', p), self._view(self._overhead, ms[p])))], 0
+            if f['use_robot_map']:
+                ch.append('robots')
+            if f['use_distance_to_receptacle_map']:
+                ch.append(('distance', use(('receptacle', id(self.distance_to_receptacle_maps[e])), self.distance_to_receptacle_maps[e])))
+            for flag in ('use_shortest_path_to_receptacle_map', 'use_shortest_path_map'):
+                if f[flag]:
+                    ch.append(('distance', use(('image', d, p), images[d * P + p])))
+                    d += 1
+            for flag, name in (('use_history_map', 'history'), ('use_intention_map', 'intention')):
+                if f[flag]:
+                    ch.append(('map', use((name, p), drawn[(name, p)])))
+            if f['use_intention_channels']:
+                for q in range(len(order[p])):
+                    if self.intention_channel_encoding == 'spatial':
+                        ch.append(('map', use(('channel', p, q), drawn[('channel', p, q)])))
+                    else:
+                        ch += [('constant', v) for v in constants[(p, q)]]
+            channels.append(ch)
+        stamps = {e: self._stamps(e, s) for e, s in states.items()}
+        poses = [(states[e][r].position, states[e][r].heading) for e, r in own]
+        args, out, keep = local_maps._prepare(maps, channels, poses, [stamps[e] for e, _ in own], self.masks, out, None)
+        lib.call('simq_local_state_images', *args)
+        del keep
+        # what the stages left on the device, until the next call: {('image', 0 or 1, p)}: the distance images in the order of the
+        # flags, {('history', p), ('intention', p), ('channel', p, q)}: the drawn maps (p: position in `mappers`, q: channel)
+        self.stage_maps = {key: maps[k] for key, k in index.items() if key[0] in ('image', 'history', 'intention', 'channel')}
+
+        if status is not None:
+            bad, codes = _batch.bad_problems(status)                                        # the one read-back of the call
+            if bad.size:
+                raise SimqError('BatchedMapper.get_states: no distance images for mapper(s) %s (simq_grid_distance_images_snapped status %s; '
+                                '%d: no update since the last reset, 1: a configuration space without a free cell); their distance '
+                                'channels come from images of zeros'
+                                % (self._named(sorted(set(int(p) % P for p in bad)), ms), codes[:8].tolist(), NOT_UPDATED))
+        return out
+
+    # ---- Mapper.shortest_path and Mapper.distance_to_receptacle on the stored tensors -----------------------------------------
+    def shortest_paths(self, source_positions, target_positions, mappers=None, simplify=None):
+        """Mapper.shortest_path (envs.py:2186-2187) of the named mappers: simq.shortest_paths on this object's tensors."""
+        from .waypoints import shortest_paths
+        return shortest_paths(self.configuration_space, self.cspace_thin, self.closest_cspace_indices, source_positions, target_positions,
+                              self._mappers(mappers), simplify)
+
+    def distances_to_receptacle(self, positions, mappers=None, shortest_path=True):
+        """Mapper.distance_to_receptacle (envs.py:2189-2194) for the named mappers' position lists: simq.distances_to_receptacle on this
+        object's tensors, with the receptacle of each mapper's environment."""
+        from .grid_queries import distances_to_receptacle
+        ms = self._mappers(mappers)
+        if any(self.receptacle_positions[self.env_of[m]] is None for m in ms):
+            raise ValueError('distances_to_receptacle needs the receptacle_position the object was built with')
+        return distances_to_receptacle(self.configuration_space, self.closest_cspace_indices,
+                                       [self.receptacle_positions[self.env_of[m]] for m in ms], positions, ms, shortest_path)

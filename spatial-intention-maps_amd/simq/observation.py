@@ -175,6 +175,15 @@ def _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
     return args, status, (frames, d_probs, overhead_maps, occupancy_maps)
 
 
+def _enqueue(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
+    """observation_update without its status read-back: queues the launch and returns the int32 device tensor it writes.  (The frames
+    and descriptors it uploaded may go as soon as the launch is queued: the allocator hands their memory to work of this stream only.)"""
+    args, status, keep = _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps)
+    lib.call('simq_observation_update', *args)
+    del keep
+    return status
+
+
 def observation_update(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
     """Mapper.update (envs.py:2053-2065) for P camera frames in one launch: both maps of every problem are updated in place on the device.
 
@@ -193,10 +202,8 @@ def observation_update(depth, ids, geometries, id_ranges, overhead_maps, occupan
     Returns (overhead_maps, occupancy_maps) as given.  Raises ValueError for a wrong dtype, rank, contiguity or device, SimqError for
     what the library refuses (two problems naming one map among it; nothing is launched) and for the frames that held a point that is
     not finite: their maps are unchanged, every other problem of the call is updated."""
-    args, status, keep = _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps)
-    lib.call('simq_observation_update', *args)
+    status = _enqueue(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps)
     bad, codes = _batch.bad_problems(status)
-    del keep
     if bad.size:
         if (codes == 1).all():
             raise SimqError('simq_observation_update: %d frame(s) hold a point that is not finite (a depth buffer outside what the near and far '

@@ -44,23 +44,9 @@ def _radii(radius, P, what):
     return [int(v) for v in values]
 
 
-def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, out=None):
-    """The configuration spaces, thin configuration spaces and closest free cells of P occupancy maps in one launch, on the device.
-
-    occupancy: P 2-D uint8 maps (C-contiguous numpy arrays or contiguous uint8 device tensors, read with a device copy), or one
-    [P, rows, cols] array / tensor; a cell is occupied where nonzero (OccupancyMap.occupancy_map).  room_masks: the same for the room
-    masks (OccupancyMap.room_mask: nonzero inside the room).  room_index: P indices into `room_masks` (several problems may share one
-    mask); omitted, problem p uses mask p.  radius: floor(robot.RADIUS * 96) of envs.py:2420, thin_radius: ceil(Robot.HALF_WIDTH * 96)
-    of envs.py:2428 -- ints, or one per problem.
-
-    Returns the named triple (configuration_space, cspace_thin, closest_cspace_indices) of envs.py:2453-2455: uint8 [P, rows, cols]
-    twice and int32 [P, 2, rows, cols] (scipy's return_indices layout) device tensors when every problem has the same shape, otherwise
-    three lists of P views ([rows_p, cols_p] twice, [2, rows_p, cols_p]) into packed buffers.  out: three contiguous device tensors to
-    write into, of those shapes (mixed shapes: uint8 of at least sum(rows_p * cols_p) elements twice and int32 of at least twice as
-    many); every element is written.
-
-    Raises ValueError for a wrong dtype, rank or contiguity, SimqError for what the library refuses (launching nothing) and for the
-    problems whose configuration space has no free cell (their closest cells are undefined)."""
+def _enqueue(occupancy, room_masks, radius, thin_radius, room_index=None, out=None):
+    """occupancy_maps without its status read-back: checks, uploads and queues the launch, and returns (out, status, uniform, shapes)
+    with `out` the three output tensors and `status` the int32 device tensor the launch writes."""
     occupancy, occupancy_block = _batch.as_maps(occupancy, 'occupancy', expects=MAPS)
     room_masks, _ = _batch.as_maps(room_masks, 'room_masks', expects=MAPS)
     P = len(occupancy)
@@ -108,6 +94,27 @@ def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, 
     status = torch.empty(P, dtype=torch.int32, device=dev)
     lib.call('simq_occupancy_maps', ptr(packed), ctypes.c_int64(packed.numel()), probs, P, ptr(d_probs), ptr(out[0]), ptr(out[1]),
              ctypes.c_int64(min(out[0].numel(), out[1].numel())), ptr(out[2]), ctypes.c_int64(out[2].numel()), ptr(status), stream_ptr(dev))
+    return out, status, uniform, shapes
+
+
+def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, out=None):
+    """The configuration spaces, thin configuration spaces and closest free cells of P occupancy maps in one launch, on the device.
+
+    occupancy: P 2-D uint8 maps (C-contiguous numpy arrays or contiguous uint8 device tensors, read with a device copy), or one
+    [P, rows, cols] array / tensor; a cell is occupied where nonzero (OccupancyMap.occupancy_map).  room_masks: the same for the room
+    masks (OccupancyMap.room_mask: nonzero inside the room).  room_index: P indices into `room_masks` (several problems may share one
+    mask); omitted, problem p uses mask p.  radius: floor(robot.RADIUS * 96) of envs.py:2420, thin_radius: ceil(Robot.HALF_WIDTH * 96)
+    of envs.py:2428 -- ints, or one per problem.
+
+    Returns the named triple (configuration_space, cspace_thin, closest_cspace_indices) of envs.py:2453-2455: uint8 [P, rows, cols]
+    twice and int32 [P, 2, rows, cols] (scipy's return_indices layout) device tensors when every problem has the same shape, otherwise
+    three lists of P views ([rows_p, cols_p] twice, [2, rows_p, cols_p]) into packed buffers.  out: three contiguous device tensors to
+    write into, of those shapes (mixed shapes: uint8 of at least sum(rows_p * cols_p) elements twice and int32 of at least twice as
+    many); every element is written.
+
+    Raises ValueError for a wrong dtype, rank or contiguity, SimqError for what the library refuses (launching nothing) and for the
+    problems whose configuration space has no free cell (their closest cells are undefined)."""
+    out, status, uniform, shapes = _enqueue(occupancy, room_masks, radius, thin_radius, room_index, out)
     bad, codes = _batch.bad_problems(status)
     if bad.size:
         if (codes == 1).all():
