@@ -318,6 +318,15 @@ int simq_clip_sgd_step(float* d_params, float* d_grads, float* d_momentum, int64
 int simq_replay_gather(const float* d_ring, int64_t item_floats, const int64_t* d_index, int count,
                        float* d_out, void* stream);
 
+/* ---- replay pool scatter: the inverse of simq_replay_gather, for observations that are already on the device ------------------
+ * d_pool [pool_slots][item_floats] fp32; d_pool[slots[p]] = d_src[p] for p < count.  `slots` is a HOST array: every slot is checked
+ * before anything is copied or launched (0 <= slot < pool_slots, none named twice, no written slot sharing a byte with d_src or
+ * d_desc; 1 <= count <= 65535), then copied to d_desc (at least 8 * count bytes of device scratch, 8-byte aligned) on `stream`.
+ * Any item size: rows move as 16-byte vectors where the two addresses allow it, float by float elsewhere.  A refusal writes
+ * nothing. */
+int simq_replay_scatter(const float* d_src, int64_t item_floats, const int64_t* slots, int count, float* d_pool, int64_t pool_slots,
+                        void* d_desc, int64_t desc_bytes, void* stream);
+
 /* ---- the whole TD step in one call (reference train.train, train.py:108-141, lines 114-135) -------------------------------
  * Policy forward (train-mode BN) on `state`; double DQN: policy forward (train mode, no grad) on `next_state` + argmax, target
  * forward (eval) + gather -- vanilla DQN: target forward + max; scatter into the bootstrap vector, TD target + Huber + dLoss/dQ
@@ -768,6 +777,18 @@ int64_t simq_local_state_desc_bytes(int n_maps, int n_robots, int n, int n_chann
 int simq_local_state_images(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks, const simq_local_robot* robots,
                             int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels,
                             void* d_desc, int64_t desc_bytes, float* d_out, int64_t out_floats, void* stream);
+
+/* simq_local_state_images with a destination per problem: problem p's [96][96][C] image begins at d_pool + slots[p] * 96 * 96 * C
+ * floats (a replay pool whose free slots are not consecutive).  `slots` is a HOST array of n slots, checked with everything else
+ * before anything is copied or launched: 0 <= slot < pool_slots, none named twice, and no WRITTEN slot sharing a byte with a map, the
+ * mask bank or d_desc -- the pool as a whole may hold them (a map kept in another slot of the same allocation is read in place).
+ * The slot table travels behind the descriptors: d_desc takes simq_local_state_slots_desc_bytes(...) bytes.  Every other rule, and
+ * every image, is simq_local_state_images'. */
+int64_t simq_local_state_slots_desc_bytes(int n_maps, int n_robots, int n, int n_channels);
+int simq_local_state_images_slots(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks, const simq_local_robot* robots,
+                                  int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels,
+                                  int n_channels, const int64_t* slots, void* d_desc, int64_t desc_bytes, float* d_pool, int64_t pool_slots,
+                                  void* stream);
 
 /* ---- global intention / history maps (Mapper._create_global_intention_or_history_map, envs.py:2301-2346, and the per-robot spatial
  * maps of Mapper._get_intention_channels, envs.py:2360-2366) ----------------------------------------------------------------------

@@ -65,6 +65,40 @@ inline bool first_conflict(const Buffer* bufs, int n, int* a_out, int* b_out) {
     return false;
 }
 
+// ---- host: slot tables -------------------------------------------------------------------------------------------------------------
+// A call that writes item p to pool + slots[p] * item_bytes (simq_replay_scatter, simq_local_state_images_slots) checks its host table
+// with these two: nothing else of the pool is the call's business, so buffers the launch reads may lie in the pool's other slots.
+
+// `sorted` receives the n slots in ascending order.  0: every slot lies in [0, pool_slots) and none is named twice; 1: *which lies
+// outside the pool; 2: *which is named twice.
+inline int check_slots(const int64_t* slots, int n, int64_t pool_slots, std::vector<int64_t>& sorted, int64_t* which) {
+    for (int p = 0; p < n; ++p)
+        if (slots[p] < 0 || slots[p] >= pool_slots) {
+            *which = slots[p];
+            return 1;
+        }
+    sorted.assign(slots, slots + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < sorted.size(); ++i)
+        if (sorted[i] == sorted[i - 1]) {
+            *which = sorted[i];
+            return 2;
+        }
+    return 0;
+}
+
+// a slot of `sorted` (ascending, each in [0, pool_slots)) whose bytes [pool + slot * item_bytes, + item_bytes) share a byte with
+// [p, p + bytes); -1 when there is none
+inline int64_t written_slot_in(const std::vector<int64_t>& sorted, const void* pool, int64_t item_bytes, int64_t pool_slots, const void* p,
+                               int64_t bytes) {
+    if (bytes <= 0 || !overlaps(pool, pool_slots * item_bytes, p, bytes)) return -1;
+    const uintptr_t base = (uintptr_t)pool, lo = (uintptr_t)p, hi = lo + (uintptr_t)bytes - 1;        // (hi: the last byte)
+    const int64_t first = lo <= base ? 0 : (int64_t)((lo - base) / (uintptr_t)item_bytes);
+    const int64_t last = std::min<int64_t>(pool_slots - 1, (int64_t)((hi - base) / (uintptr_t)item_bytes));
+    const auto it = std::lower_bound(sorted.begin(), sorted.end(), first);
+    return it != sorted.end() && *it <= last ? *it : -1;
+}
+
 // ---- host: the descriptor upload ---------------------------------------------------------------------------------------------------
 
 struct HostBlock {

@@ -294,6 +294,8 @@ int launch_split_last_channel(const float* x, float* head, float* last, int64_t 
 int launch_sigmoid_concat(const float* state, const float* logit, float* out, float* prob, int64_t pixels, int Cs, hipStream_t stream);
 int launch_replay_gather(const float* ring, int64_t item_floats, const int64_t* index, int count, float* out,
                          hipStream_t stream);
+int launch_replay_scatter(const float* src, int64_t item_floats, const int64_t* slots, int count, float* pool, int64_t pool_slots,
+                          void* d_desc, int64_t desc_bytes, hipStream_t stream);
 
 // comm.hip: RCCL all-reduce on the communicator's own stream, ordered behind `producer` / awaited by `consumer`
 int comm_allreduce(simq_comm* c, void* buf, int64_t count, int dtype, hipStream_t producer);

@@ -5,7 +5,7 @@
 //   td_huber                   y = r + g*v ; |q-y| ; smooth_l1_loss ; dLoss/dQ  train.py:126-129 (+ autograd seed)
 //   clip_sgd                   clip_grad_norm_ + optim.SGD(momentum, wd).step  train.py:133-135,186
 //   replay_gather              torch.cat([transform_fn(s) for s in batch.state]).to(device)  train.py:109,112
-#include "common.h"
+#include "batch_abi.h"
 
 namespace simq {
 
@@ -157,6 +157,33 @@ __global__ void replay_gather_kernel(const float* __restrict__ ring, size_t item
         dst[i] = src[i];
 }
 
+// The inverse of replay_gather: source row blockIdx.y goes to pool slot slots[blockIdx.y].  Any item size: a row pair whose two
+// addresses agree modulo 16 bytes moves as float4 between a scalar head (up to the destination's 16-byte boundary) and a scalar tail;
+// a pair that does not agree (items of 4k + r floats put most rows there) moves float by float.  A slot outside the pool is skipped:
+// the host has refused those, this guards a table changed behind its back.
+__global__ void __launch_bounds__(256) replay_scatter_kernel(const float* __restrict__ src, int64_t item, const int64_t* __restrict__ slots,
+                                                             float* __restrict__ pool, int64_t pool_slots) {
+    const int64_t slot = slots[blockIdx.y];
+    if (slot < 0 || slot >= pool_slots) return;
+    const float* s = src + (int64_t)blockIdx.y * item;
+    float* d = pool + slot * item;
+    const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, lanes = (int64_t)gridDim.x * blockDim.x;
+    int64_t head = item, n4 = 0;                                         // floats before the float4 body, float4s of the body
+    if ((((uintptr_t)s ^ (uintptr_t)d) & 15) == 0) {
+        head = (int64_t)((16 - ((uintptr_t)d & 15)) & 15) / 4;
+        if (head > item) head = item;
+        n4 = (item - head) / 4;
+    }
+    const float4* s4 = reinterpret_cast<const float4*>(s + head);
+    float4* d4 = reinterpret_cast<float4*>(d + head);
+    for (int64_t i = lane; i < n4; i += lanes) d4[i] = s4[i];
+    const int64_t body_end = head + n4 * 4, rest = head + (item - body_end);
+    for (int64_t i = lane; i < rest; i += lanes) {                       // the head, then the tail
+        const int64_t at = i < head ? i : body_end + (i - head);
+        d[at] = s[at];
+    }
+}
+
 // ---- intention-prediction head (train.py:143-158, policies.py:97-117) ---------------------------------------------
 // BCEWithLogitsLoss (mean) and its gradient:  l = max(x,0) - x*t + log(1 + exp(-|x|)) ;  dl/dx = (sigmoid(x) - t) / N
 __global__ void __launch_bounds__(256) bce_logits_kernel(const float* __restrict__ x, const float* __restrict__ t, size_t n,
@@ -281,6 +308,41 @@ int launch_replay_gather(const float* ring, int64_t item_floats, const int64_t* 
     if (bx > 16) bx = 16;
     hipLaunchKernelGGL(replay_gather_kernel, dim3(bx, count), dim3(256), 0, stream, ring, item4, index, out);
     SIMQ_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_replay_scatter(const float* src, int64_t item_floats, const int64_t* slots, int count, float* pool, int64_t pool_slots,
+                          void* d_desc, int64_t desc_bytes, hipStream_t stream) {
+    SIMQ_REQUIRE(src && slots && pool && d_desc, "replay_scatter: NULL pointer");
+    SIMQ_REQUIRE(count >= 1 && count <= 65535, "replay_scatter: count = %d (1 .. 65535 rows: one grid row each)", count);
+    SIMQ_REQUIRE(item_floats >= 1 && item_floats <= (1 << 28), "replay_scatter: item_floats = %lld (1 .. 2^28)", (long long)item_floats);
+    const int64_t item_bytes = item_floats * 4;
+    SIMQ_REQUIRE(pool_slots >= 1 && pool_slots <= ((int64_t)1 << 40) / item_bytes, "replay_scatter: pool_slots = %lld (1 .. 2^40 bytes of pool)",
+                 (long long)pool_slots);
+    SIMQ_REQUIRE(((uintptr_t)src & 3) == 0 && ((uintptr_t)pool & 3) == 0 && ((uintptr_t)d_desc & 7) == 0,
+                 "replay_scatter: d_src and d_pool must be 4-byte, d_desc 8-byte aligned");
+    const int64_t need_desc = (int64_t)sizeof(int64_t) * count, src_bytes = item_bytes * count;
+    SIMQ_REQUIRE(desc_bytes >= need_desc, "replay_scatter: d_desc holds %lld bytes, the slot table takes %lld", (long long)desc_bytes,
+                 (long long)need_desc);
+    std::vector<int64_t> sorted;
+    int64_t which = 0;
+    const int bad = check_slots(slots, count, pool_slots, sorted, &which);
+    SIMQ_REQUIRE(bad != 1, "replay_scatter: slot %lld outside the pool of %lld", (long long)which, (long long)pool_slots);
+    SIMQ_REQUIRE(bad != 2, "replay_scatter: slot %lld is named twice", (long long)which);
+    int64_t hit = written_slot_in(sorted, pool, item_bytes, pool_slots, src, src_bytes);
+    SIMQ_REQUIRE(hit == -1, "replay_scatter: slot %lld overlaps d_src", (long long)hit);
+    hit = written_slot_in(sorted, pool, item_bytes, pool_slots, d_desc, need_desc);
+    SIMQ_REQUIRE(hit == -1, "replay_scatter: slot %lld overlaps d_desc", (long long)hit);
+    SIMQ_REQUIRE(!overlaps(src, src_bytes, d_desc, need_desc), "replay_scatter: d_src overlaps d_desc");
+
+    const HostBlock table = {slots, (size_t)need_desc};
+    SIMQ_CHECK_HIP(upload_descriptors(d_desc, &table, 1, nullptr, stream));
+    int bx = (int)((item_floats / 4 + 255) / 256);                       // (as replay_gather: up to 16 blocks of 256 lanes per row)
+    bx = bx < 1 ? 1 : (bx > 16 ? 16 : bx);
+    hipLaunchKernelGGL(replay_scatter_kernel, dim3(bx, count), dim3(256), 0, stream, src, item_floats, static_cast<const int64_t*>(d_desc), pool,
+                       pool_slots);
+    SIMQ_CHECK_LAUNCH();
+    note_launch("replay_scatter");
     return 0;
 }
 

@@ -18,6 +18,7 @@
 #include "../../include/simq.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace simq {
 
@@ -39,6 +40,21 @@ struct Desc {                                     // the packed device copy of o
     const float* masks;
     int C;
 };
+
+struct SlotDesc : Desc {                          // simq_local_state_images_slots: problem p is written to pool slot slots[p]
+    const int64_t* slots;
+    int64_t pool_slots;
+};
+
+// where problem p's [96][96][C] image begins: the dense batch, or the problem's pool slot (NULL: a slot outside the pool -- the host has
+// refused those, this guards a table changed behind its back)
+__device__ __forceinline__ float* image_of(const Desc& d, float* out, unsigned p) {
+    return out + (int64_t)p * kPix * d.C;
+}
+__device__ __forceinline__ float* image_of(const SlotDesc& d, float* pool, unsigned p) {
+    const int64_t slot = d.slots[p];
+    return slot >= 0 && slot < d.pool_slots ? pool + slot * ((int64_t)kPix * d.C) : nullptr;
+}
 
 // input index along both axes of an n x n image for output index (oi, oj) of its rotation; false: outside (the pixel is 0)
 __device__ __forceinline__ bool rotate_index(const simq_local_rotation& t, int n, int oi, int oj, int* i0, int* i1) {
@@ -70,7 +86,9 @@ __device__ __forceinline__ float robot_value(const Desc& d, const simq_local_pro
     return acc;
 }
 
-__global__ void __launch_bounds__(kThreads) local_state_kernel(Desc d, float* __restrict__ out) {
+// D: Desc (out is the [n][96][96][C] batch) or SlotDesc (out is the pool); everything but the image's base is the same code
+template <typename D>
+__global__ void __launch_bounds__(kThreads) local_state_kernel(D d, float* __restrict__ out) {
     __shared__ int gidx[kPix];                    // gi * cols + gj of the local pixel, -1 outside the crop
     __shared__ float wave_min[kWaves];
     __shared__ float chan_min[SIMQ_LOCAL_MAX_CHANNELS];
@@ -110,7 +128,9 @@ __global__ void __launch_bounds__(kThreads) local_state_kernel(Desc d, float* __
         __syncthreads();
     }
 
-    float* o = out + (int64_t)blockIdx.x * kPix * C;
+    float* o = image_of(d, out, blockIdx.x);
+    if constexpr (std::is_same<D, SlotDesc>::value)
+        if (o == nullptr) return;                                        // (uniform over the workgroup)
     const int items = kPix * C;
     for (int it = tid; it < items; it += kThreads) {
         const int pix = it / C, c = it - pix * C;
@@ -141,6 +161,97 @@ bool finite_rotation(const simq_local_rotation& t) {
     return std::isfinite(t.offset[0]) && std::isfinite(t.offset[1]);
 }
 
+
+// The checks both entry points make of their host descriptors, in the order simq_local_state_images has always made them; `who` heads
+// the refusal.  Everything about the output is the entry point's own.
+int check_counts(const char* who, const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks, const simq_local_robot* robots,
+                 int n_robots, int n, int n_channels) {
+    SIMQ_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d (1 .. 2^20 problems)", who, n);
+    SIMQ_REQUIRE(n_channels >= 1 && n_channels <= SIMQ_LOCAL_MAX_CHANNELS, "%s: n_channels = %d (1 .. %d)", who, n_channels,
+                 SIMQ_LOCAL_MAX_CHANNELS);
+    SIMQ_REQUIRE(n_maps >= 0 && n_maps <= (1 << 24) && (n_maps == 0 || maps), "%s: n_maps = %d with maps %s", who, n_maps,
+                 maps ? "given" : "NULL");
+    SIMQ_REQUIRE(n_robots >= 0 && n_robots <= (1 << 24) && (n_robots == 0 || (robots && d_masks && n_masks >= 1)),
+                 "%s: n_robots = %d needs robots and a mask bank (n_masks = %d)", who, n_robots, n_masks);
+    SIMQ_REQUIRE(n_masks >= 0 && n_masks <= (1 << 16), "%s: n_masks = %d (0 .. 2^16)", who, n_masks);
+    return 0;
+}
+
+int check_map(const char* who, const simq_local_map& m, int k) {
+    SIMQ_REQUIRE(m.d_data && ((uintptr_t)m.d_data & 3) == 0, "%s: map %d: NULL or misaligned d_data", who, k);
+    SIMQ_REQUIRE(m.rows >= kCrop && m.cols >= kCrop && (int64_t)m.rows * m.cols < (1 << 28),
+                 "%s: map %d is %d x %d (rows, cols >= %d, rows * cols < 2^28)", who, k, m.rows, m.cols, kCrop);
+    return 0;
+}
+
+int check_tables(const char* who, const simq_local_map* maps, int n_maps, int n_masks, const simq_local_robot* robots, int n_robots,
+                 const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels) {
+    for (int k = 0; k < n_robots; ++k) {
+        const simq_local_robot& r = robots[k];
+        SIMQ_REQUIRE(r.mask >= 0 && r.mask < n_masks && r.seg_mask >= 0 && r.seg_mask < n_masks,
+                     "%s: robot %d: mask %d / seg_mask %d outside the bank of %d", who, k, r.mask, r.seg_mask, n_masks);
+        SIMQ_REQUIRE(r.rot.shape[0] >= kW && r.rot.shape[0] <= kMaxShapeMask && r.rot.shape[1] >= kW && r.rot.shape[1] <= kMaxShapeMask,
+                     "%s: robot %d: rotated mask shape %d x %d outside [%d, %d]", who, k, r.rot.shape[0], r.rot.shape[1], kW, kMaxShapeMask);
+        SIMQ_REQUIRE(finite_rotation(r.rot), "%s: robot %d: rotation is not finite", who, k);
+    }
+    for (int i = 0; i < n; ++i) {
+        const simq_local_problem& p = problems[i];
+        SIMQ_REQUIRE(p.rows >= kCrop && p.cols >= kCrop && (int64_t)p.rows * p.cols < (1 << 28),
+                     "%s: problem %d: maps of %d x %d (rows, cols >= %d, rows * cols < 2^28)", who, i, p.rows, p.cols, kCrop);
+        SIMQ_REQUIRE(p.pixel_i >= kCrop / 2 && p.pixel_i <= p.rows - kCrop / 2 && p.pixel_j >= kCrop / 2 && p.pixel_j <= p.cols - kCrop / 2,
+                     "%s: problem %d: the %d x %d crop around pixel (%d, %d) leaves its %d x %d map", who, i, kCrop, kCrop, p.pixel_i,
+                     p.pixel_j, p.rows, p.cols);
+        SIMQ_REQUIRE(p.rot.shape[0] >= kCrop && p.rot.shape[0] <= kMaxShapeCrop && p.rot.shape[1] >= kCrop && p.rot.shape[1] <= kMaxShapeCrop,
+                     "%s: problem %d: rotated crop shape %d x %d outside [%d, %d]", who, i, p.rot.shape[0], p.rot.shape[1], kCrop,
+                     kMaxShapeCrop);
+        SIMQ_REQUIRE(finite_rotation(p.rot), "%s: problem %d: rotation is not finite", who, i);
+        SIMQ_REQUIRE(p.robot_count >= 0 && p.robot_begin >= 0 && (int64_t)p.robot_begin + p.robot_count <= n_robots,
+                     "%s: problem %d: robots [%d, %d + %d) outside the %d given", who, i, p.robot_begin, p.robot_begin, p.robot_count,
+                     n_robots);
+        for (int k = p.robot_begin; k < p.robot_begin + p.robot_count; ++k) {
+            const simq_local_robot& r = robots[k];
+            const int si = r.pixel_i - r.rot.shape[0] / 2, sj = r.pixel_j - r.rot.shape[1] / 2;
+            SIMQ_REQUIRE(si >= 0 && si + r.rot.shape[0] <= p.rows && sj >= 0 && sj + r.rot.shape[1] <= p.cols,
+                         "%s: problem %d: the stamp of robot %d at pixel (%d, %d) leaves the %d x %d map", who, i, k, r.pixel_i, r.pixel_j,
+                         p.rows, p.cols);
+        }
+        for (int c = 0; c < n_channels; ++c) {
+            const simq_local_channel& ch = channels[(int64_t)i * n_channels + c];
+            SIMQ_REQUIRE(ch.kind >= SIMQ_LOCAL_MAP && ch.kind <= SIMQ_LOCAL_CONSTANT, "%s: problem %d channel %d: kind %d", who, i, c, ch.kind);
+            if (ch.kind == SIMQ_LOCAL_MAP || ch.kind == SIMQ_LOCAL_DISTANCE || ch.kind == SIMQ_LOCAL_OVERHEAD) {
+                SIMQ_REQUIRE(ch.map >= 0 && ch.map < n_maps, "%s: problem %d channel %d: map %d outside the %d given", who, i, c, ch.map,
+                             n_maps);
+                SIMQ_REQUIRE(maps[ch.map].rows == p.rows && maps[ch.map].cols == p.cols,
+                             "%s: problem %d channel %d: map %d is %d x %d, the problem's maps are %d x %d", who, i, c, ch.map,
+                             maps[ch.map].rows, maps[ch.map].cols, p.rows, p.cols);
+            }
+        }
+    }
+    return 0;
+}
+
+// the descriptor tables of one call, packed into d_desc behind each other (`slots`: NULL, or the n pool slots as a fifth block)
+template <typename D>
+int upload_tables(D* d, const simq_local_map* maps, int n_maps, const float* d_masks, const simq_local_robot* robots, int n_robots,
+                  const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels, const int64_t* slots,
+                  void* d_desc, const char** slots_at, hipStream_t s) {
+    const HostBlock parts[5] = {{maps, sizeof(simq_local_map) * (size_t)n_maps},
+                                {robots, sizeof(simq_local_robot) * (size_t)n_robots},
+                                {problems, sizeof(simq_local_problem) * (size_t)n},
+                                {channels, sizeof(simq_local_channel) * (size_t)n * n_channels},
+                                {slots, sizeof(int64_t) * (size_t)n}};
+    const char* at[5];
+    SIMQ_CHECK_HIP(upload_descriptors(d_desc, parts, slots ? 5 : 4, at, s));
+    d->maps = reinterpret_cast<const simq_local_map*>(at[0]);
+    d->robots = reinterpret_cast<const simq_local_robot*>(at[1]);
+    d->probs = reinterpret_cast<const simq_local_problem*>(at[2]);
+    d->chans = reinterpret_cast<const simq_local_channel*>(at[3]);
+    d->masks = d_masks;
+    d->C = n_channels;
+    if (slots) *slots_at = at[4];
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace simq
@@ -157,15 +268,9 @@ extern "C" int simq_local_state_images(const simq_local_map* maps, int n_maps, c
                                        const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
                                        const simq_local_channel* channels, int n_channels, void* d_desc, int64_t desc_bytes, float* d_out,
                                        int64_t out_floats, void* stream) {
+    const char* who = "local_state_images";
     SIMQ_REQUIRE(problems && channels && d_desc && d_out, "local_state_images: NULL pointer");
-    SIMQ_REQUIRE(n >= 1 && n <= (1 << 20), "local_state_images: n = %d (1 .. 2^20 problems)", n);
-    SIMQ_REQUIRE(n_channels >= 1 && n_channels <= SIMQ_LOCAL_MAX_CHANNELS, "local_state_images: n_channels = %d (1 .. %d)", n_channels,
-                 SIMQ_LOCAL_MAX_CHANNELS);
-    SIMQ_REQUIRE(n_maps >= 0 && n_maps <= (1 << 24) && (n_maps == 0 || maps), "local_state_images: n_maps = %d with maps %s", n_maps,
-                 maps ? "given" : "NULL");
-    SIMQ_REQUIRE(n_robots >= 0 && n_robots <= (1 << 24) && (n_robots == 0 || (robots && d_masks && n_masks >= 1)),
-                 "local_state_images: n_robots = %d needs robots and a mask bank (n_masks = %d)", n_robots, n_masks);
-    SIMQ_REQUIRE(n_masks >= 0 && n_masks <= (1 << 16), "local_state_images: n_masks = %d (0 .. 2^16)", n_masks);
+    if (int rc = check_counts(who, maps, n_maps, d_masks, n_masks, robots, n_robots, n, n_channels)) return rc;
     SIMQ_REQUIRE(((uintptr_t)d_desc & 7) == 0 && ((uintptr_t)d_out & 3) == 0, "local_state_images: d_desc must be 8-byte and d_out 4-byte aligned");
     const int64_t need_desc = simq_local_state_desc_bytes(n_maps, n_robots, n, n_channels);
     SIMQ_REQUIRE(desc_bytes >= need_desc, "local_state_images: d_desc holds %lld bytes, the descriptors take %lld", (long long)desc_bytes,
@@ -176,74 +281,69 @@ extern "C" int simq_local_state_images(const simq_local_map* maps, int n_maps, c
     const int64_t out_bytes = need_out * 4;
     SIMQ_REQUIRE(!overlaps(d_out, out_bytes, d_desc, need_desc), "local_state_images: d_out overlaps d_desc");
     for (int k = 0; k < n_maps; ++k) {
-        const simq_local_map& m = maps[k];
-        SIMQ_REQUIRE(m.d_data && ((uintptr_t)m.d_data & 3) == 0, "local_state_images: map %d: NULL or misaligned d_data", k);
-        SIMQ_REQUIRE(m.rows >= kCrop && m.cols >= kCrop && (int64_t)m.rows * m.cols < (1 << 28),
-                     "local_state_images: map %d is %d x %d (rows, cols >= %d, rows * cols < 2^28)", k, m.rows, m.cols, kCrop);
-        SIMQ_REQUIRE(!overlaps(d_out, out_bytes, m.d_data, (int64_t)m.rows * m.cols * 4), "local_state_images: d_out overlaps map %d", k);
+        if (int rc = check_map(who, maps[k], k)) return rc;
+        SIMQ_REQUIRE(!overlaps(d_out, out_bytes, maps[k].d_data, (int64_t)maps[k].rows * maps[k].cols * 4), "local_state_images: d_out overlaps map %d", k);
     }
     if (n_masks > 0 && d_masks)
         SIMQ_REQUIRE(!overlaps(d_out, out_bytes, d_masks, (int64_t)n_masks * kPix * 4), "local_state_images: d_out overlaps the mask bank");
-    for (int k = 0; k < n_robots; ++k) {
-        const simq_local_robot& r = robots[k];
-        SIMQ_REQUIRE(r.mask >= 0 && r.mask < n_masks && r.seg_mask >= 0 && r.seg_mask < n_masks,
-                     "local_state_images: robot %d: mask %d / seg_mask %d outside the bank of %d", k, r.mask, r.seg_mask, n_masks);
-        SIMQ_REQUIRE(r.rot.shape[0] >= kW && r.rot.shape[0] <= kMaxShapeMask && r.rot.shape[1] >= kW && r.rot.shape[1] <= kMaxShapeMask,
-                     "local_state_images: robot %d: rotated mask shape %d x %d outside [%d, %d]", k, r.rot.shape[0], r.rot.shape[1], kW,
-                     kMaxShapeMask);
-        SIMQ_REQUIRE(finite_rotation(r.rot), "local_state_images: robot %d: rotation is not finite", k);
-    }
-    for (int i = 0; i < n; ++i) {
-        const simq_local_problem& p = problems[i];
-        SIMQ_REQUIRE(p.rows >= kCrop && p.cols >= kCrop && (int64_t)p.rows * p.cols < (1 << 28),
-                     "local_state_images: problem %d: maps of %d x %d (rows, cols >= %d, rows * cols < 2^28)", i, p.rows, p.cols, kCrop);
-        SIMQ_REQUIRE(p.pixel_i >= kCrop / 2 && p.pixel_i <= p.rows - kCrop / 2 && p.pixel_j >= kCrop / 2 && p.pixel_j <= p.cols - kCrop / 2,
-                     "local_state_images: problem %d: the %d x %d crop around pixel (%d, %d) leaves its %d x %d map", i, kCrop, kCrop,
-                     p.pixel_i, p.pixel_j, p.rows, p.cols);
-        SIMQ_REQUIRE(p.rot.shape[0] >= kCrop && p.rot.shape[0] <= kMaxShapeCrop && p.rot.shape[1] >= kCrop && p.rot.shape[1] <= kMaxShapeCrop,
-                     "local_state_images: problem %d: rotated crop shape %d x %d outside [%d, %d]", i, p.rot.shape[0], p.rot.shape[1], kCrop,
-                     kMaxShapeCrop);
-        SIMQ_REQUIRE(finite_rotation(p.rot), "local_state_images: problem %d: rotation is not finite", i);
-        SIMQ_REQUIRE(p.robot_count >= 0 && p.robot_begin >= 0 && (int64_t)p.robot_begin + p.robot_count <= n_robots,
-                     "local_state_images: problem %d: robots [%d, %d + %d) outside the %d given", i, p.robot_begin, p.robot_begin,
-                     p.robot_count, n_robots);
-        for (int k = p.robot_begin; k < p.robot_begin + p.robot_count; ++k) {
-            const simq_local_robot& r = robots[k];
-            const int si = r.pixel_i - r.rot.shape[0] / 2, sj = r.pixel_j - r.rot.shape[1] / 2;
-            SIMQ_REQUIRE(si >= 0 && si + r.rot.shape[0] <= p.rows && sj >= 0 && sj + r.rot.shape[1] <= p.cols,
-                         "local_state_images: problem %d: the stamp of robot %d at pixel (%d, %d) leaves the %d x %d map", i, k, r.pixel_i,
-                         r.pixel_j, p.rows, p.cols);
-        }
-        for (int c = 0; c < n_channels; ++c) {
-            const simq_local_channel& ch = channels[(int64_t)i * n_channels + c];
-            SIMQ_REQUIRE(ch.kind >= SIMQ_LOCAL_MAP && ch.kind <= SIMQ_LOCAL_CONSTANT, "local_state_images: problem %d channel %d: kind %d", i, c,
-                         ch.kind);
-            if (ch.kind == SIMQ_LOCAL_MAP || ch.kind == SIMQ_LOCAL_DISTANCE || ch.kind == SIMQ_LOCAL_OVERHEAD) {
-                SIMQ_REQUIRE(ch.map >= 0 && ch.map < n_maps, "local_state_images: problem %d channel %d: map %d outside the %d given", i, c,
-                             ch.map, n_maps);
-                SIMQ_REQUIRE(maps[ch.map].rows == p.rows && maps[ch.map].cols == p.cols,
-                             "local_state_images: problem %d channel %d: map %d is %d x %d, the problem's maps are %d x %d", i, c, ch.map,
-                             maps[ch.map].rows, maps[ch.map].cols, p.rows, p.cols);
-            }
-        }
-    }
+    if (int rc = check_tables(who, maps, n_maps, n_masks, robots, n_robots, problems, n, channels, n_channels)) return rc;
 
-    const HostBlock parts[4] = {{maps, sizeof(simq_local_map) * (size_t)n_maps},
-                                {robots, sizeof(simq_local_robot) * (size_t)n_robots},
-                                {problems, sizeof(simq_local_problem) * (size_t)n},
-                                {channels, sizeof(simq_local_channel) * (size_t)n * n_channels}};
-    const char* at[4];
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SIMQ_CHECK_HIP(upload_descriptors(d_desc, parts, 4, at, s));
     Desc d;
-    d.maps = reinterpret_cast<const simq_local_map*>(at[0]);
-    d.robots = reinterpret_cast<const simq_local_robot*>(at[1]);
-    d.probs = reinterpret_cast<const simq_local_problem*>(at[2]);
-    d.chans = reinterpret_cast<const simq_local_channel*>(at[3]);
-    d.masks = d_masks;
-    d.C = n_channels;
-    local_state_kernel<<<n, kThreads, 0, s>>>(d, d_out);
+    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, nullptr, d_desc, nullptr, s)) return rc;
+    local_state_kernel<Desc><<<n, kThreads, 0, s>>>(d, d_out);
     SIMQ_CHECK_LAUNCH();
     note_launch("local_state");
+    return 0;
+}
+
+extern "C" int64_t simq_local_state_slots_desc_bytes(int n_maps, int n_robots, int n, int n_channels) {
+    const int64_t tables = simq_local_state_desc_bytes(n_maps, n_robots, n, n_channels);
+    return tables < 0 ? -1 : tables + (int64_t)sizeof(int64_t) * n;
+}
+
+extern "C" int simq_local_state_images_slots(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                                             const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                                             const simq_local_channel* channels, int n_channels, const int64_t* slots, void* d_desc,
+                                             int64_t desc_bytes, float* d_pool, int64_t pool_slots, void* stream) {
+    const char* who = "local_state_images_slots";
+    SIMQ_REQUIRE(problems && channels && slots && d_desc && d_pool, "local_state_images_slots: NULL pointer");
+    if (int rc = check_counts(who, maps, n_maps, d_masks, n_masks, robots, n_robots, n, n_channels)) return rc;
+    SIMQ_REQUIRE(pool_slots >= 1 && pool_slots <= ((int64_t)1 << 40) / (kPix * 4), "local_state_images_slots: pool_slots = %lld (1 .. 2^40 bytes of pool)",
+                 (long long)pool_slots);
+    SIMQ_REQUIRE(((uintptr_t)d_desc & 7) == 0 && ((uintptr_t)d_pool & 3) == 0,
+                 "local_state_images_slots: d_desc must be 8-byte and d_pool 4-byte aligned");
+    const int64_t need_desc = simq_local_state_slots_desc_bytes(n_maps, n_robots, n, n_channels);
+    SIMQ_REQUIRE(desc_bytes >= need_desc, "local_state_images_slots: d_desc holds %lld bytes, the descriptors and the slot table take %lld",
+                 (long long)desc_bytes, (long long)need_desc);
+    std::vector<int64_t> sorted;
+    int64_t which = 0;
+    const int bad = check_slots(slots, n, pool_slots, sorted, &which);
+    SIMQ_REQUIRE(bad != 1, "local_state_images_slots: slot %lld outside the pool of %lld", (long long)which, (long long)pool_slots);
+    SIMQ_REQUIRE(bad != 2, "local_state_images_slots: slot %lld is named twice", (long long)which);
+    // the pool as a whole may hold what the launch reads (a map in another slot): only the slots written must be clear of it
+    const int64_t item_bytes = (int64_t)kPix * n_channels * 4;
+    int64_t hit = written_slot_in(sorted, d_pool, item_bytes, pool_slots, d_desc, need_desc);
+    SIMQ_REQUIRE(hit == -1, "local_state_images_slots: slot %lld overlaps d_desc", (long long)hit);
+    for (int k = 0; k < n_maps; ++k) {
+        if (int rc = check_map(who, maps[k], k)) return rc;
+        hit = written_slot_in(sorted, d_pool, item_bytes, pool_slots, maps[k].d_data, (int64_t)maps[k].rows * maps[k].cols * 4);
+        SIMQ_REQUIRE(hit == -1, "local_state_images_slots: slot %lld overlaps map %d", (long long)hit, k);
+    }
+    if (n_masks > 0 && d_masks) {
+        hit = written_slot_in(sorted, d_pool, item_bytes, pool_slots, d_masks, (int64_t)n_masks * kPix * 4);
+        SIMQ_REQUIRE(hit == -1, "local_state_images_slots: slot %lld overlaps the mask bank", (long long)hit);
+    }
+    if (int rc = check_tables(who, maps, n_maps, n_masks, robots, n_robots, problems, n, channels, n_channels)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SlotDesc d;
+    const char* slots_at = nullptr;
+    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, slots, d_desc, &slots_at, s)) return rc;
+    d.slots = reinterpret_cast<const int64_t*>(slots_at);
+    d.pool_slots = pool_slots;
+    local_state_kernel<SlotDesc><<<n, kThreads, 0, s>>>(d, d_pool);
+    SIMQ_CHECK_LAUNCH();
+    note_launch("local_state_slots");
     return 0;
 }

@@ -67,6 +67,11 @@ int simq_replay_gather(const float* d_ring, int64_t item_floats, const int64_t* 
     return launch_replay_gather(d_ring, item_floats, d_index, count, d_out, static_cast<hipStream_t>(stream));
 }
 
+int simq_replay_scatter(const float* d_src, int64_t item_floats, const int64_t* slots, int count, float* d_pool, int64_t pool_slots,
+                        void* d_desc, int64_t desc_bytes, void* stream) {
+    return launch_replay_scatter(d_src, item_floats, slots, count, d_pool, pool_slots, d_desc, desc_bytes, static_cast<hipStream_t>(stream));
+}
+
 int simq_nchw_to_nhwc(const float* d_in, float* d_out, int batch, int channels, int hw, void* stream) {
     return launch_nchw_to_nhwc(d_in, d_out, batch, channels, hw, static_cast<hipStream_t>(stream));
 }

@@ -116,6 +116,7 @@ _SIGS = {
     'simq_split_last_channel': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'simq_sigmoid_concat': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'simq_replay_gather': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    'simq_replay_scatter': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_nchw_to_nhwc': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'simq_nhwc_to_nchw': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'simq_conv2d_fwd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p] + [c_void_p]),
@@ -172,6 +173,9 @@ _SIGS = {
     'simq_local_state_desc_bytes': (c_int64, [c_int, c_int, c_int, c_int]),
     'simq_local_state_images': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64,
                                         c_void_p, c_int64, c_void_p]),
+    'simq_local_state_slots_desc_bytes': (c_int64, [c_int, c_int, c_int, c_int]),
+    'simq_local_state_images_slots': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                              c_int64, c_void_p, c_int64, c_void_p]),
     'simq_intention_desc_bytes': (c_int64, [c_int, c_int]),
     'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,

@@ -58,6 +58,28 @@ def _reference_view(flat, shape):
     return v.permute(0, 3, 1, 2) if len(shape) == 4 else v
 
 
+
+def is_handle(s):
+    """A replay pool handle (learner._PoolObs, which this module cannot import: learner imports it)."""
+    return getattr(s, 'pool', None) is not None and hasattr(s, 'slot')
+
+
+def states_batch(states, device):
+    """A list of HWC states -- ndarrays [96,96,C], device tensors [1,96,96,C], handles of AliasedDeviceReplayBuffer.reserve / adopt --
+    as one contiguous float32 [n,96,96,C] device tensor, every state at its position.  The handles of a pool are read with one
+    simq_replay_gather, behind the writes of their slots; ndarrays are uploaded as they always were."""
+    rows, by_pool = {}, {}
+    for k, s in enumerate(states):
+        if is_handle(s):
+            by_pool.setdefault(id(s.pool), []).append(k)
+    for ks in by_pool.values():
+        got = states[ks[0]].pool.gather_handles([states[k] for k in ks])
+        if len(ks) == len(states):
+            return got
+        rows.update({k: got[r:r + 1] for r, k in enumerate(ks)})
+    return torch.cat([rows[k] if k in rows else s if torch.is_tensor(s) else
+                      torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(device) for k, s in enumerate(states)]).contiguous()
+
 class FCN(torch.nn.Module):
     def __init__(self, num_input_channels=3, num_output_channels=1, device=None, dataparallel_keys=True, precision='fp32', options=None):
         super().__init__()
@@ -429,14 +451,16 @@ class FCN(torch.nn.Module):
         return self.flat_grads, lookup
 
     def infer_argmax_batch(self, states, need_q=False):
-        """Eval-mode forward of several HWC states (numpy [96,96,C] or device tensors [1,96,96,C]) in ONE batch + one
-        argmax launch: the multi-robot form of infer_argmax (batched multi-env inference)."""
+        """Eval-mode forward of several HWC states (numpy [96,96,C], device tensors [1,96,96,C] or replay pool handles, mixed as they
+        come) in ONE batch + one argmax launch: the multi-robot form of infer_argmax (batched multi-env inference)."""
         if self.training:
             raise SimqError('infer_argmax_batch: the net must be in eval mode (policies.py:56)')
         if len(states) == 1:
             a, q = self.infer_argmax(states[0], need_q)
             return [a], [q]
-        if all(not torch.is_tensor(s) for s in states):
+        if any(is_handle(s) for s in states):
+            x = states_batch(states, self.device_)
+        elif all(not torch.is_tensor(s) for s in states):
             x = torch.from_numpy(np.stack([np.ascontiguousarray(s, dtype=np.float32) for s in states])).to(self.device_)
         else:
             x = torch.cat([s if torch.is_tensor(s) else torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(self.device_)
@@ -459,7 +483,7 @@ class FCN(torch.nn.Module):
         if self.training:
             raise SimqError('infer_argmax: the net must be in eval mode (policies.py:56)')
         # a device tensor [1,96,96,C] is taken as is (DQNIntentionPolicy hands over state + predicted map in HBM)
-        x = state_hwc if torch.is_tensor(state_hwc) else \
+        x = state_hwc if torch.is_tensor(state_hwc) else states_batch([state_hwc], self.device_) if is_handle(state_hwc) else \
             torch.from_numpy(np.ascontiguousarray(state_hwc, dtype=np.float32)).unsqueeze(0).to(self.device_)
         q = self.forward_nhwc(x)
         a = self.argmax(q[0])

@@ -19,6 +19,7 @@ All arithmetic goes through libsimq (HIP); there is no torch/CPU fallback.
 import ctypes
 import os
 import random
+import weakref
 from collections import namedtuple
 
 import numpy as np
@@ -215,8 +216,72 @@ class _DeviceObs:
     def copy(self):
         return self.__array__()
 
+    def device_row(self):
+        """The [96,96,C] row of the ring itself, for a reader on the current stream (simq.state_output_visualizations)."""
+        if self.store.is_cuda:
+            sync_uploads(self.store.device)
+        return self.store[self.slot]
+
     def __repr__(self):
         return '_DeviceObs(slot=%d, shape=%s)' % (self.slot, self.shape)
+
+
+class _PoolObs(_DeviceObs):
+    """A handle from AliasedDeviceReplayBuffer.reserve / adopt: one pool slot that belongs to its holder until it is written (by
+    BatchedMapper.get_states(into=), local_state_images(into=), adopt's scatter) and pushed.  It stands where the ndarray stands in the
+    collector's loop -- TransitionTracker hands it on by identity, push() takes it, the policies step on it -- and the slot goes back
+    to the pool when the handle is gone (or discarded) and no transition refers to it."""
+    __slots__ = ('pool', '_gone', '__weakref__')
+
+    def __init__(self, pool, slot):
+        super().__init__(pool.pool, slot)
+        self.pool = pool
+        self._gone = weakref.finalize(self, pool._release, self.slot)
+        self._gone.atexit = False
+
+    @property
+    def alive(self):
+        return self._gone.alive
+
+    def __array__(self, dtype=None, copy=None):
+        if not self.alive:
+            raise SimqError('%r was discarded: its slot may hold another observation by now' % (self,))
+        self.pool.sync_ring()                      # (the slot was written on whichever stream ran the mapper / the scatter)
+        a = self.store[self.slot].cpu().numpy()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+    def device_row(self):
+        if not self.alive:
+            raise SimqError('%r was discarded: its slot may hold another observation by now' % (self,))
+        if self.store.is_cuda:
+            self.pool._order_behind_writes(torch.cuda.current_stream(self.store.device))
+        return self.store[self.slot]
+
+    def __repr__(self):
+        return '_PoolObs(slot=%d, shape=%s%s)' % (self.slot, self.shape, '' if self.alive else ', discarded')
+
+
+def pool_of(handles, count=None, channels=None, what='into'):
+    """The AliasedDeviceReplayBuffer the handles belong to, after the checks every `into=` makes before anything is launched: handles
+    from reserve / adopt that are still held, all of one pool, none twice, `count` of them, the pool's states of `channels` channels."""
+    handles = list(handles)
+    if count is not None and len(handles) != count:
+        raise ValueError('%s: %d handles for %d states' % (what, len(handles), count))
+    if not handles:
+        raise ValueError('%s: no handles' % what)
+    for h in handles:
+        if not isinstance(h, _PoolObs):
+            raise ValueError('%s takes the handles of AliasedDeviceReplayBuffer.reserve, got %s' % (what, type(h).__name__))
+        if not h.alive:
+            raise ValueError('%s: %r' % (what, h))
+    pool = handles[0].pool
+    if any(h.pool is not pool for h in handles):
+        raise ValueError('%s: the handles belong to more than one pool' % what)
+    if len({h.slot for h in handles}) != len(handles):
+        raise ValueError('%s: a handle is named twice' % what)
+    if channels is not None and pool.C != channels:
+        raise ValueError('%s: the pool holds states of %d channels, the states have %d' % (what, pool.C, channels))
+    return pool
 
 
 class _PinnedStaging:
@@ -298,17 +363,104 @@ class DeviceReplayBuffer:
         if self.device.type != 'cuda':
             return
         sync_uploads(self.device)
-        for ev in (getattr(self, '_bulk_event', None), getattr(getattr(self, '_staging', None), 'last_event', None)):
+        for ev in (getattr(self, '_bulk_event', None), getattr(getattr(self, '_staging', None), 'last_event', None)) + tuple(self._write_events.values()):
             if ev is not None:
                 ev.synchronize()
 
+    # ---- slots written on the device (a mapper launch, a scatter, a device-to-device copy) rather than uploaded -------------------
+    # The pushes and gathers of a ring are ordered by the one stream they run on (upload_stream=True) or by the caller's.  A device
+    # write runs on the caller's current stream, whichever that is, so it is ordered by events: before it, that stream waits for the
+    # ring's last gather and uploads (a slot that a transition released is never rewritten under a gather that still reads it, nor
+    # behind an upload that has not landed); after it, an event is kept that the next gather's stream waits for.
+    _write_events = {}             # stream -> the event behind its last device write (class default: a ring without any pays an empty loop)
+    _read_events = {}              # stream -> the event behind its last gather
+
+    def order_write(self):
+        """Call before enqueuing a device write of ring slots on the current stream."""
+        if self.device.type != 'cuda':
+            return
+        cur = torch.cuda.current_stream(self.device)
+        if self.ring_on_upload_stream:
+            cur.wait_stream(_upload_stream(self.device))
+        for ev in (getattr(self, '_bulk_event', None), getattr(self._staging, 'last_event', None)):
+            if ev is not None:
+                cur.wait_event(ev)
+        for events in (self._read_events, self._write_events):
+            for key, ev in events.items():
+                if key != cur.cuda_stream:
+                    cur.wait_event(ev)
+
+    def note_write(self):
+        """Call after enqueuing a device write of ring slots on the current stream: gathers and uploads order themselves behind it."""
+        if self.device.type != 'cuda':
+            return
+        cur = torch.cuda.current_stream(self.device)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        if not self._write_events:
+            self._write_events = {}
+        self._write_events[cur.cuda_stream] = ev
+
+    def _order_behind_writes(self, stream):
+        for key, ev in self._write_events.items():
+            if key != stream.cuda_stream:
+                stream.wait_event(ev)
+
+    def note_read(self):
+        """Call after enqueuing, on the current stream, a read of ring slots in place that the ring did not issue itself."""
+        if self.device.type == 'cuda':
+            self._note_read(torch.cuda.current_stream(self.device))
+
+    def _note_read(self, stream, ev=None):
+        if ev is None:
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        if not self._read_events:
+            self._read_events = {}
+        self._read_events[stream.cuda_stream] = ev
+
+    def _device_obs(self, obs):
+        """None for an observation that goes through the pinned staging ring; a device tensor as the [96,96,C] row to copy (checked:
+        push refuses it before it changes anything)."""
+        if not torch.is_tensor(obs) or not obs.is_cuda:
+            return None
+        row = obs[0] if obs.dim() == 4 and obs.shape[0] == 1 else obs
+        if row.dtype != torch.float32 or tuple(row.shape) != (W, W, self.C) or not row.is_contiguous() or row.device != self.states.device:
+            raise SimqError('push: a device state must be a contiguous float32 [%d,%d,%d] (or [1,%d,%d,%d]) tensor on %s, got %s %s on %s'
+                            % (W, W, self.C, W, W, self.C, self.states.device, obs.dtype, tuple(obs.shape), obs.device))
+        return row
+
+    def _put(self, obs, dst):
+        """One observation into ring row `dst`: an ndarray through the pinned staging ring, a device tensor [96,96,C] / [1,96,96,C] by
+        a device-to-device copy on the stream the ring's uploads run on (no host round trip)."""
+        row = self._device_obs(obs)
+        if row is None:
+            self._staging.upload(obs, dst)
+            return
+        obs = row
+        cur = torch.cuda.current_stream(self.device)
+        if self.ring_on_upload_stream:
+            up = _upload_stream(self.device)
+            up.wait_stream(cur)                                # (the tensor's producer runs on the caller's stream)
+            with torch.cuda.stream(up):
+                dst.copy_(obs, non_blocking=True)
+            obs.record_stream(up)
+            self._staging.last_event = None
+        else:
+            dst.copy_(obs, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._staging.last_event = ev
+
     def push(self, state, action, reward, next_state):
+        self._device_obs(state)
+        self._device_obs(next_state)
         if len(self.buffer) < self.capacity:
             self.buffer.append(None)
         slot = self.position
-        self._staging.upload(state, self.states[slot])
+        self._put(state, self.states[slot])
         if next_state is not None:
-            self._staging.upload(next_state, self.next_states[slot])
+            self._put(next_state, self.next_states[slot])
         self.buffer[slot] = Transition(_DeviceObs(self.states, slot), int(action), float(reward),
                                        _DeviceObs(self.next_states, slot) if next_state is not None else None)
         self.position = (self.position + 1) % self.capacity
@@ -366,6 +518,7 @@ class DeviceReplayBuffer:
                 up.wait_event(self._bulk_event)
             if ev_push is not None:
                 up.wait_event(ev_push)
+            self._order_behind_writes(up)
             with torch.cuda.stream(up):
                 state = torch.empty((B, W, W, self.C), dtype=torch.float32, device=dev)
                 lib.call('simq_replay_gather', ptr(self.states), self.item, ptr(index), B, ptr(state), stream_ptr(dev))
@@ -375,14 +528,18 @@ class DeviceReplayBuffer:
                 ready = torch.cuda.Event()
                 ready.record(up)
             main.wait_event(ready)
+            self._note_read(up, ready)
             for t in (state, next_state, index, nindex):
                 t.record_stream(main)
             return DeviceBatch(state, action, reward, next_state, pos, mask, ready)
+        if self._write_events:
+            self._order_behind_writes(torch.cuda.current_stream(dev))
         state = torch.empty((B, W, W, self.C), dtype=torch.float32, device=dev)
         lib.call('simq_replay_gather', ptr(self.states), self.item, ptr(index), B, ptr(state), st)
         next_state = torch.empty((len(nf), W, W, self.C), dtype=torch.float32, device=dev)
         if nf:
             lib.call('simq_replay_gather', ptr(self.next_states), self.item, ptr(nindex), len(nf), ptr(next_state), st)
+        self._note_read(torch.cuda.current_stream(dev))          # (a device write of a released slot waits for this gather: order_write)
         return DeviceBatch(state, action, reward, next_state, pos, mask)
 
     def sample(self, batch_size):
@@ -423,6 +580,8 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
             raise SimqError('AliasedDeviceReplayBuffer: observation pool exhausted (%d slots); the pushes do not alias '
                             'next_state/state -- construct with pool_slots=2*capacity' % len(self._ref))
         slot = self._free.pop()
+        if self._write_events:                               # (the slot may have been written on the device before it was released)
+            self._order_behind_writes(_upload_stream(self.device) if self.ring_on_upload_stream else torch.cuda.current_stream(self.device))
         self._staging.upload(arr, self.pool[slot])
         self._recent[id(arr)] = (slot, arr)
         self._recent_order.append(id(arr))
@@ -437,15 +596,32 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
                 del self._recent[key]
             self._free.append(slot)
 
+    def _slot_of(self, obs):
+        return obs.slot if isinstance(obs, _PoolObs) else self._upload(obs)
+
+    def _check_pushed(self, obs):
+        """A handle must be a live one of this pool; a device tensor has no slot yet (nothing is changed before these refusals)."""
+        if isinstance(obs, _PoolObs):
+            if obs.pool is not self:
+                raise SimqError('AliasedDeviceReplayBuffer.push: %r is a handle of another pool; copy its state into this one with '
+                                'adopt(states)' % (obs,))
+            if not obs.alive:
+                raise SimqError('AliasedDeviceReplayBuffer.push: %r' % (obs,))
+        elif torch.is_tensor(obs) and obs.is_cuda:
+            raise SimqError('AliasedDeviceReplayBuffer.push takes ndarrays or handles of this pool, not device tensors: make the states '
+                            'slots of the pool with adopt(states) (or write them there: reserve(n) and get_states(into=handles))')
+
     def push(self, state, action, reward, next_state):
+        self._check_pushed(state)
+        self._check_pushed(next_state)
         if len(self.buffer) < self.capacity:
             self.buffer.append(None)
         old = self.buffer[self.position]
-        s_slot = self._upload(state)
+        s_slot = self._slot_of(state)
         self._ref[s_slot] += 1
         n_slot = None
         if next_state is not None:
-            n_slot = self._upload(next_state)
+            n_slot = self._slot_of(next_state)
             self._ref[n_slot] += 1
         if old is not None:                                  # the ring wrapped: the overwritten transition lets go
             self._release(int(old.state))
@@ -461,7 +637,80 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
 
     @property
     def observations_resident(self):
+        """Pool slots in use: referred to by a transition, held by a handle of reserve / adopt, or both."""
         return len(self._ref) - len(self._free)
+
+    # ---- observations that are already on the device: slots handed out before they are written -----------------------------------
+    def reserve(self, n):
+        """n handles, each owning one free pool slot for its holder to write (BatchedMapper.get_states(into=), local_state_images(into=))
+        and push.  The handle counts as one reference to its slot: the slot is free again when the handle is gone -- dropped, or
+        discard()ed -- and no transition refers to it.  Raises SimqError, taking no slot, when fewer than n are free."""
+        n = int(n)
+        if n < 0:
+            raise ValueError('reserve: n = %d' % n)
+        if n > len(self._free):
+            raise SimqError('AliasedDeviceReplayBuffer: observation pool exhausted (%d slots, %d free, %d wanted); handles that are '
+                            'never pushed hold their slots until they are dropped or discard()ed' % (len(self._ref), len(self._free), n))
+        handles = []
+        for _ in range(n):
+            slot = self._free.pop()
+            self._ref[slot] = 1
+            handles.append(_PoolObs(self, slot))
+        return handles
+
+    def discard(self, handles):
+        """Give back the slots of handles that will not be pushed (again): what dropping the last reference to a handle does, made
+        explicit.  Transitions that already refer to a slot keep it."""
+        for h in handles:
+            if not isinstance(h, _PoolObs) or h.pool is not self:
+                raise SimqError('discard takes handles of this pool, got %r' % (h,))
+        for h in handles:
+            h._gone()                                        # (once: weakref.finalize calls _release at most one time)
+
+    def adopt(self, states):
+        """Handles for the n states of a contiguous float32 device tensor [n, 96, 96, C] (a batch that did not come from the mapper:
+        DQNIntentionPolicy's state + predicted map, a tensor another process sent): reserve(n) and one simq_replay_scatter on the
+        current stream.  States the mapper writes need no copy: reserve(n) and get_states(into=handles)."""
+        if not (torch.is_tensor(states) and states.dtype == torch.float32 and states.dim() == 4 and tuple(states.shape[1:]) == (W, W, self.C)
+                and states.is_contiguous() and states.device == self.pool.device and states.shape[0] >= 1):
+            raise SimqError('adopt takes a contiguous float32 tensor [n >= 1, %d, %d, %d] on %s, got %s' % (
+                W, W, self.C, self.pool.device, '%s %s on %s' % (states.dtype, tuple(states.shape), states.device)
+                if torch.is_tensor(states) else type(states).__name__))
+        handles = self.reserve(states.shape[0])
+        try:
+            self.write_slots('simq_replay_scatter', handles, lambda slots, d_desc: (
+                ptr(states), self.item, slots, len(handles), ptr(self.pool), len(self._ref), ptr(d_desc), ctypes.c_int64(d_desc.numel()),
+                stream_ptr(self.device)), 8 * len(handles))
+        except Exception:
+            self.discard(handles)
+            raise
+        return handles
+
+    def gather_handles(self, handles):
+        """The states of handles of this pool as one float32 device tensor [n, 96, 96, C] on the current stream (one
+        simq_replay_gather, behind the writes of the slots): what the policies step on."""
+        for h in handles:
+            if not isinstance(h, _PoolObs) or h.pool is not self or not h.alive:
+                raise SimqError('gather_handles takes live handles of this pool, got %r' % (h,))
+        dev = self.pool.device
+        cur = torch.cuda.current_stream(dev)
+        self._order_behind_writes(cur)
+        index = torch.tensor([h.slot for h in handles], dtype=torch.int64, device=dev)
+        out = torch.empty((len(handles), W, W, self.C), dtype=torch.float32, device=dev)
+        lib.call('simq_replay_gather', ptr(self.pool), self.item, ptr(index), len(handles), ptr(out), stream_ptr(dev))
+        self._note_read(cur)
+        return out
+
+    def write_slots(self, entry, handles, args_of, desc_bytes):
+        """One library call that writes the slots of `handles` on the current stream, inside the ring's stream order: `args_of(slots,
+        d_desc)` gives the arguments of `entry` for the host slot table (int64) and a scratch tensor of desc_bytes bytes."""
+        slots = (ctypes.c_int64 * len(handles))(*[h.slot for h in handles])
+        d_desc = torch.empty(max(int(desc_bytes), 8), dtype=torch.uint8, device=self.device)
+        self.order_write()
+        try:
+            lib.call(entry, *args_of(slots, d_desc))
+        finally:
+            self.note_write()                                # (a call that fails after its launch has still written)
 
 
 class _HardwareQueues:

@@ -114,7 +114,7 @@ def _channel(spec, n_maps):
     return LocalChannel(KINDS[name], k, 0.0, 0), k
 
 
-def local_state_images(maps, channels, poses, robots=None, masks=None, out=None, map_shape=None):
+def local_state_images(maps, channels, poses, robots=None, masks=None, out=None, map_shape=None, into=None):
     """The [P, 96, 96, C] float32 states of P robots in one launch.
 
     maps: a sequence of global maps [rows, cols] float32 -- device tensors are read in place (rows of one [G, rows, cols] tensor
@@ -132,18 +132,47 @@ def local_state_images(maps, channels, poses, robots=None, masks=None, out=None,
     (Mapper.robot_masks), numpy or device tensor.  map_shape: (rows, cols) of the global maps for problems whose channels name no map
     (one pair, or P pairs).
     out: a contiguous float32 device tensor [P, 96, 96, C] to write into -- a slice of a replay ring's `states`, a batch buffer.
+    into: instead of `out`, P handles of one AliasedDeviceReplayBuffer (reserve(P)) whose states have C channels: state p is written
+    into the pool slot of into[p] (simq_local_state_images_slots), inside the pool's stream order, and the handles are returned.
 
     Raises SimqError, launching nothing, when the 136 x 136 crop around a robot or the stamp of a robot leaves its map (the reference
     would silently wrap or clip the slice), and for any other descriptor the library refuses."""
-    args, out, keep = _prepare(maps, channels, poses, robots, masks, out, map_shape)
-    lib.call('simq_local_state_images', *args)
-    del keep                                     # (uploaded maps / masks / descriptors: alive until the launch is queued)
-    return out
+    if into is None:
+        args, out, keep = _prepare(maps, channels, poses, robots, masks, out, map_shape)
+        lib.call('simq_local_state_images', *args)
+        del keep                                 # (uploaded maps / masks / descriptors: alive until the launch is queued)
+        return out
+    if out is not None:
+        raise ValueError('local_state_images: `into` and `out` name two destinations; pass one')
+    poses = list(poses)
+    into, pool = check_into(into, 'local_state_images', len(poses))
+    args, _, keep = _prepare(maps, channels, poses, robots, masks, None, map_shape, into=into)
+    write_into(pool, into, args)
+    del keep
+    return into
 
 
-def _prepare(maps, channels, poses, robots, masks, out, map_shape):
+def check_into(into, what, count=None, channels=None):
+    """(handles, their pool) of an `into=` argument; ValueError for anything but distinct live handles of one pool (and, once the
+    caller knows them, `count` of them for states of `channels` channels)."""
+    from .learner import pool_of
+    into = list(into)
+    return into, pool_of(into, count, channels, '%s(into=)' % what)
+
+
+def write_into(pool, handles, args):
+    """simq_local_state_images_slots for _prepare(into=)'s arguments: the slot table and the scratch come from the pool, which puts the
+    launch into its stream order."""
+    n_maps, n_robots, P, C = args[1], args[5], args[7], args[9]
+    pool.write_slots('simq_local_state_images_slots', handles, lambda slots, d_desc: args[:10] + (
+        slots, ptr(d_desc), ctypes.c_int64(d_desc.numel()), ptr(pool.pool), ctypes.c_int64(pool.pool.shape[0]), stream_ptr(pool.pool.device)),
+        lib.c.simq_local_state_slots_desc_bytes(n_maps, n_robots, P, C))
+
+
+def _prepare(maps, channels, poses, robots, masks, out, map_shape, into=None):
     """The argument tuple of simq_local_state_images for local_state_images' inputs, the output tensor and the device tensors the
-    call reads (tools/local_maps_rate.py times the library call alone with it)."""
+    call reads (tools/local_maps_rate.py times the library call alone with it).  into (checked handles of one pool): no output tensor
+    and no descriptor scratch are made; the first ten arguments are those of simq_local_state_images_slots (write_into)."""
     dev = _batch.device('local state images')
     maps, _ = _batch.as_maps(maps, 'maps', _batch.check_map)      # (numpy maps are uploaded, device tensors read in place)
     poses = list(poses)
@@ -233,6 +262,10 @@ def _prepare(maps, channels, poses, robots, masks, out, map_shape):
         c_probs[p] = LocalProblem(_rotation_struct(90 - math.degrees(heading), CROP), pi, pj, shape[0], shape[1], begin, count)
 
     want = (P, WIDTH, WIDTH, C)
+    if into is not None:
+        check_into(into, 'local_state_images', P, C)
+        return (c_maps if d_maps else None, len(d_maps), ptr(d_masks), n_masks, c_robots if n_robots else None, n_robots, c_probs, P, c_chans,
+                C), None, (d_maps, d_masks)
     if out is None:
         out = torch.empty(want, dtype=torch.float32, device=dev)
     elif not _batch.out_fits(out, torch.float32, dev, want):

@@ -363,11 +363,14 @@ class BatchedMapper:
             out.append(path)
         return out
 
-    def get_states(self, robots, mappers=None, out=None):
+    def get_states(self, robots, mappers=None, out=None, into=None):
         """Mapper.get_state() (envs.py:2067-2112) for the named mappers (all when omitted): a float32 [P, 96, 96, C] device tensor,
         state p that of mapper mappers[p], the channels in `self.channels`' order.  robots: per environment the RobotState of each
         robot, in env.robots' order (only the environments of the named mappers are read).  out: a contiguous float32 device
         tensor [P, 96, 96, C] to write into -- a batch buffer, a slice of a replay ring's `states`; every element is written.
+        into: instead of `out`, P handles of one AliasedDeviceReplayBuffer (ring.reserve(P)) for states of C channels: state p is
+        written where it will be sampled from, the pool slot of into[p], and the handles are returned -- for TransitionTracker,
+        the policies' step_many and ring.push, which all take them where they take an ndarray.
 
         The distance images and the states are one launch each; the drawn maps one launch per room shape among the named mappers
         (simq_intention_maps draws maps of one shape).  Raises ValueError for a wrong robot count or `out`; SimqError, after the
@@ -377,6 +380,11 @@ class BatchedMapper:
         ms = self._mappers(mappers)
         P, C = len(ms), self.num_channels
         want = (P, arch.STATE_WIDTH, arch.STATE_WIDTH, C)
+        pool = None
+        if into is not None:
+            if out is not None:
+                raise ValueError('get_states: `into` and `out` name two destinations; pass one')
+            into, pool = local_maps.check_into(into, 'get_states', P, C)
         if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == want and out.is_contiguous()):
             raise ValueError('out must be a contiguous float32 device tensor of shape %s, got %s' % (
                 want, '%s %s' % (out.dtype, tuple(out.shape)) if isinstance(out, torch.Tensor) else type(out).__name__))
@@ -422,6 +430,8 @@ class BatchedMapper:
             self._allocate()
         if out is not None and out.device != self.device:
             raise ValueError('out must be a contiguous float32 device tensor of shape %s on %s' % (want, self.device))
+        if pool is not None and pool.pool.device != self.device:
+            raise ValueError('get_states(into=): the pool lives on %s, the maps on %s' % (pool.pool.device, self.device))
 
         # ---- stage 1: the distance images, every source snapped through the closest cells on the device
         status, images = None, []
@@ -474,8 +484,12 @@ class BatchedMapper:
             channels.append(ch)
         stamps = {e: self._stamps(e, s) for e, s in states.items()}
         poses = [(states[e][r].position, states[e][r].heading) for e, r in own]
-        args, out, keep = local_maps._prepare(maps, channels, poses, [stamps[e] for e, _ in own], self.masks, out, None)
-        lib.call('simq_local_state_images', *args)
+        args, out, keep = local_maps._prepare(maps, channels, poses, [stamps[e] for e, _ in own], self.masks, out, None, into=into)
+        if pool is None:
+            lib.call('simq_local_state_images', *args)
+        else:
+            local_maps.write_into(pool, into, args)
+            out = into
         del keep
         # what the stages left on the device, until the next call: {('image', 0 or 1, p)}: the distance images in the order of the
         # flags, {('history', p), ('intention', p), ('channel', p, q)}: the drawn maps (p: position in `mappers`, q: channel)

@@ -13,7 +13,7 @@ import torch
 
 from . import arch
 from ._lib import SimqError, lib, ptr, stream_ptr
-from .fcn import FCN
+from .fcn import FCN, is_handle, states_batch
 
 
 class DQNPolicy:
@@ -142,9 +142,11 @@ class DQNIntentionPolicy(DQNPolicy):
                     precision=getattr(self.cfg, 'simq_precision', 'fp32')) for _ in range(self.num_robot_groups)]
 
     def _predict(self, i, s):
-        """One HWC state [96,96,C-1] -> device tensors (state_with_intention [1,96,96,C], sigmoid map [96,96])."""
+        """One HWC state [96,96,C-1] (ndarray, replay pool handle, or a device tensor [1,96,96,C-1]) -> device tensors
+        (state_with_intention [1,96,96,C], sigmoid map [96,96])."""
         net = self.intention_nets[i]
-        x = torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(self.device)
+        x = s if torch.is_tensor(s) else states_batch([s], self.device) if is_handle(s) else \
+            torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(self.device)
         logit = net.forward_nhwc(x)
         C = x.shape[3]
         out = torch.empty((1, arch.STATE_WIDTH, arch.STATE_WIDTH, C + 1), dtype=torch.float32, device=self.device)
@@ -175,7 +177,9 @@ class DQNIntentionPolicy(DQNPolicy):
         if self.train and use_ground_truth_intention:
             return super().step(state, exploration_eps=exploration_eps, debug=debug)
         if self.train:                                                                      # drop the ground-truth map
-            state = [[None if s is None else s[:, :, :-1] for s in g] for g in state]
+            # (a pool handle is read on the device and loses its last channel there; an ndarray on the host, as always)
+            state = [[None if s is None else states_batch([s], self.device)[..., :-1].contiguous() if is_handle(s) else s[:, :, :-1]
+                      for s in g] for g in state]
         state = self.step_intention(state, debug=debug, _device=not debug)
         if debug:
             state, info_intention = state
@@ -204,9 +208,14 @@ class DQNIntentionPolicy(DQNPolicy):
                 net = self.intention_nets[i]
                 net.eval()                                                                 # policies.py:101
                 xs = [states[e][i][j] for e, j in live]
-                if self.train:                                                             # drop the ground-truth map (policies.py:124)
-                    xs = [s[:, :, :-1] for s in xs]
-                x = torch.from_numpy(np.stack([np.ascontiguousarray(s, dtype=np.float32) for s in xs])).to(self.device)
+                if any(is_handle(s) for s in xs):                                          # pool handles: the batch is formed in HBM
+                    x = states_batch(xs, self.device)
+                    if self.train:
+                        x = x[..., :-1].contiguous()
+                else:
+                    if self.train:                                                         # drop the ground-truth map (policies.py:124)
+                        xs = [s[:, :, :-1] for s in xs]
+                    x = torch.from_numpy(np.stack([np.ascontiguousarray(s, dtype=np.float32) for s in xs])).to(self.device)
                 logit = net.forward_nhwc(x)
                 n, C = x.shape[0], x.shape[3]
                 out = torch.empty((n, W, W, C + 1), dtype=torch.float32, device=self.device)

@@ -47,6 +47,8 @@ _JET = {}                        # device -> the reference's table there (upload
 
 def _on_device(x, dev, what, rank):
     """A contiguous float32 tensor on `dev`: a device tensor as it is (read in place), anything on the host uploaded."""
+    if hasattr(x, 'device_row'):                 # an observation of a replay ring (a record's state, a pool handle): its row, in place
+        x = x.device_row()
     if isinstance(x, np.ndarray):
         if x.dtype != np.float32:
             raise ValueError('%s must be float32, got %s' % (what, x.dtype))
@@ -118,7 +120,8 @@ def state_output_visualizations(states, outputs, jet=None, alpha=0.5, chw=False,
     """utils.get_state_output_visualization (utils.py:116-131) of P (state, output) pairs in one launch.
 
     states: a [P, 96, 96, C] float32 tensor / array, or a list of P [96, 96, C] ones (C may differ between them).  Device tensors are
-    read in place -- a batch, ``ring.states[k]`` of a DeviceReplayBuffer -- and must be contiguous; host arrays are uploaded.
+    read in place -- a batch, ``ring.states[k]`` of a DeviceReplayBuffer -- and must be contiguous; host arrays are uploaded.  An item
+    of the list may also be an observation of a replay ring (``record.state``, a handle of ``reserve`` / ``adopt``): its row, in place.
     outputs: a [P, n, 96, 96] float32 tensor / array, or a list of P [n, 96, 96] ones, 1 <= n <= 4: the Q-maps ``FCN.forward_nhwc``
     returned (device, read in place), ``info['output'][i][j]`` of ``policy.step(debug=True)`` (host, uploaded), or the stacked ground
     truth and predicted intention of train.py:300-303.
@@ -132,6 +135,9 @@ def state_output_visualizations(states, outputs, jet=None, alpha=0.5, chw=False,
     args, result, keep = _prepare(states, outputs, jet, alpha, chw, out)
     lib.call('simq_state_output_visualizations', *args)
     del keep                                     # (uploaded inputs / descriptors: alive until the launch is queued)
+    if not isinstance(states, (np.ndarray, torch.Tensor)):
+        for pool in {id(v.pool): v.pool for v in states if getattr(v, 'pool', None) is not None}.values():
+            pool.note_read()                     # (a pool slot read in place: whoever rewrites it once it is released waits for this launch)
     return result
 
 
