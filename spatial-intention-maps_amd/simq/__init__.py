@@ -52,6 +52,7 @@ _LAZY = {
     'observe': ('.observation', 'observe'),
     'BatchedMapper': ('.mapper', 'BatchedMapper'),
     'RobotState': ('.mapper', 'RobotState'),
+    'RobotArrays': ('.mapper', 'RobotArrays'),
     'state_output_visualizations': ('.visualization', 'state_output_visualizations'),
     'state_output_visualization': ('.visualization', 'state_output_visualization'),
     'state_visualization': ('.visualization', 'state_visualization'),

@@ -46,6 +46,7 @@ class SnappedProblem(ctypes.Structure):
 
 
 SNAPPED_FILL = 0.0               # SIMQ_GRID_SNAPPED_FILL of include/simq.h
+SNAPPED_PROBLEM = np.dtype(SnappedProblem)                       # the descriptor table as a numpy structured array
 
 
 def check_closest(c, what='closest'):

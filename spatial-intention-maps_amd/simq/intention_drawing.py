@@ -16,11 +16,12 @@ who lists the problems in the order the channels are wanted.
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _batch
 from ._lib import lib, ptr, stream_ptr
-from .local_maps import position_to_pixel_indices
+from .local_maps import distances, pixel_indices_many, position_to_pixel_indices
 
 ENCODINGS = ('circle', 'ramp', 'binary', 'line', 'history')
 STORE, RAMP = 0, 1
@@ -91,6 +92,81 @@ def segments(robots, map_shape, encoding, scale=1.0):
                 out.append((r0, c0, r1, c1, RAMP, drop_last, 0.0, float(start), float(stop), float(step)))
             path_length += segment_length
     return out
+
+
+SEGMENT, PROBLEM = np.dtype(Segment), np.dtype(Problem)      # the descriptor tables as numpy structured arrays (local_maps.as_ctypes)
+
+
+def _starts(counts):
+    """Where each of consecutive runs of `counts` entries begins."""
+    return np.cumsum(counts) - counts
+
+
+def ragged(begin, count):
+    """The indices begin[k] .. begin[k] + count[k] - 1 of every k, one range behind the other."""
+    count = np.asarray(count, np.int64)
+    return np.repeat(np.asarray(begin, np.int64) - _starts(count), count) + np.arange(int(count.sum()), dtype=np.int64)
+
+
+def circle_segments(targets, rows, cols, scale=1.0):
+    """The SEGMENT table of `segments([target], shape, 'circle', scale)` for every row of targets (float64 [D, 2]): one entry each;
+    rows, cols: the map shape, one int or an int array [D]."""
+    table = np.zeros(len(targets), SEGMENT)
+    i, j = pixel_indices_many(targets[:, 0], targets[:, 1], (rows, cols))
+    table['r0'], table['c0'], table['r1'], table['c1'], table['mode'], table['value'] = i, j, i, j, STORE, scale
+    return table
+
+
+def path_segments(points, lo, hi, rows, cols, encoding, scale=1.0):
+    """The SEGMENT tables of `segments([path], shape, encoding, scale)` for D paths at once, one behind the other, and the number of
+    entries of each: path d is points[lo[d]:hi[d]] (points float64 [N, 2], at least one waypoint per path), its map rows[d] x cols[d]
+    (or one int for all); encoding one of 'ramp', 'binary', 'line', 'history'.  Every segment is computed once, whoever observes it."""
+    if encoding not in ENCODINGS[1:]:
+        raise ValueError('encoding %r: choose from %s' % (encoding, list(ENCODINGS[1:])))
+    lo, hi = np.asarray(lo, np.int64), np.asarray(hi, np.int64)
+    if (hi <= lo).any():
+        raise ValueError('a drawn robot has an empty waypoint list (an idle robot is left out of its problem)')
+    D = len(lo)
+    count = np.ones(D, np.int64) if encoding == 'line' else hi - lo - 1
+    path = np.repeat(np.arange(D), count)
+    k = np.arange(int(count.sum()), dtype=np.int64) - np.repeat(_starts(count), count) + 1            # 1 .. count, as segments() counts
+    if encoding == 'line':
+        source, target = lo[path], hi[path] - 1
+    elif encoding == 'history':                                     # the path reversed (envs.py:2317)
+        source, target = hi[path] - k, hi[path] - 1 - k
+    else:
+        source, target = lo[path] + k - 1, lo[path] + k
+    shape = (rows if np.ndim(rows) == 0 else np.asarray(rows)[path], cols if np.ndim(cols) == 0 else np.asarray(cols)[path])
+    table = np.zeros(len(path), SEGMENT)
+    ends, S = points[np.concatenate([source, target])], len(path)
+    i, j = pixel_indices_many(ends[:, 0], ends[:, 1], shape if np.ndim(rows) == 0 else (np.tile(shape[0], 2), np.tile(shape[1], 2)))
+    table['r0'], table['c0'], table['r1'], table['c1'] = i[:S], j[:S], i[S:], j[S:]
+    table['drop_last'] = k < count[path]
+    if encoding in ('binary', 'line'):
+        table['mode'], table['value'] = STORE, scale
+        return table, count
+    length = scale * distances(ends[S:, 0] - ends[:S, 0], ends[S:, 1] - ends[:S, 1])
+    # the running path_length of segments(): a sum from the left that starts at 0, per path -- np.cumsum along the rows of a table
+    # that holds every path's lengths from column 0 on (the zeros behind a shorter path change nothing before them)
+    run = np.zeros((D, max(int(count.max()), 1) if D else 1))
+    run[path, k - 1] = length
+    run = np.cumsum(run, axis=1)
+    before = np.where(k > 1, run[path, k - 2], 0.0)
+    start, stop = 1 - before, 1 - run[path, k - 1]
+    div = np.maximum(np.abs(i[S:] - i[:S]), np.abs(j[S:] - j[:S]))
+    step = np.zeros(len(path))
+    np.divide(stop - start, div, out=step, where=div > 0)
+    table['mode'], table['start'], table['stop'], table['step'] = RAMP, start, stop, step
+    return table, count
+
+
+def check_drawing(scale, line_thickness):
+    """The two checks _prepare makes of what every map of a call shares."""
+    if int(line_thickness) != line_thickness or not 1 <= line_thickness <= MAX_RADIUS + 1:
+        raise ValueError('line_thickness = %r (a whole number in 1 .. %d)' % (line_thickness, MAX_RADIUS + 1))
+    value = float(scale)
+    if not (math.isfinite(value) and value >= 0) or math.copysign(1.0, value) < 0:
+        raise ValueError('scale = %r (finite, >= 0 and not -0)' % (scale,))
 
 
 def intention_maps(paths, map_shape, encoding, scale=1.0, line_thickness=2, out=None):

@@ -92,6 +92,59 @@ def position_to_pixel_indices(position_x, position_y, image_shape):
     return int(np.clip(pixel_i, 0, image_shape[0] - 1)), int(np.clip(pixel_j, 0, image_shape[1] - 1))
 
 
+# The descriptor tables as numpy structured arrays: numpy derives the field offsets and the item size from the ctypes structures, so a
+# table filled column by column has the bytes of the ctypes array filled entry by entry (tests/test_robot_arrays_cpu.py).
+ROTATION, LOCAL_MAP, LOCAL_ROBOT, LOCAL_PROBLEM, LOCAL_CHANNEL = (np.dtype(t) for t in (Rotation, LocalMap, LocalRobot, LocalProblem, LocalChannel))
+RAD_TO_DEG = 180.0 / math.pi     # math.degrees(x) is x * (180.0 / pi) in C doubles; headings * RAD_TO_DEG is that product elementwise
+
+
+def as_ctypes(table, struct):
+    """The ctypes array (struct * len(table)) over the bytes of a structured numpy table, without a copy: what lib.call takes."""
+    return (struct * len(table)).from_buffer(table)
+
+
+def rotation_many(angles, n):
+    """`rotation(angle, n)` for every angle of a float64 array [K]: (R [K, 2, 2], offset [K, 2], shape [K, 2]), each row the doubles
+    and ints `rotation` gives for that angle.  The sequence is rotation()'s own with every product left to numpy's matmul -- a
+    restatement in plain arithmetic, or np.einsum, rounds differently."""
+    special = _special()
+    angles = np.asarray(angles, np.float64).reshape(-1)
+    c, s = special.cosdg(angles), special.sindg(angles)
+    rot = np.empty((len(angles), 2, 2))
+    rot[:, 0, 0], rot[:, 0, 1], rot[:, 1, 0], rot[:, 1, 1] = c, s, -s, c
+    bounds = rot @ [[0, 0, n, n], [0, n, 0, n]]
+    shape = (np.ptp(bounds, axis=2) + 0.5).astype(int)
+    half = (shape - 1) / 2
+    offset = (n - 1) / 2 - (rot @ half[:, :, None])[:, :, 0]
+    return rot, offset, shape
+
+
+def rotation_table(angles, n):
+    """rotation_many as a ROTATION table [K]."""
+    rot, offset, shape = rotation_many(angles, n)
+    table = np.zeros(len(rot), ROTATION)
+    table['r'], table['offset'], table['shape'] = rot.reshape(-1, 4), offset, shape
+    return table
+
+
+def pixel_indices_many(x, y, shape):
+    """`position_to_pixel_indices` elementwise: int32 arrays (pixel_i, pixel_j) for float64 arrays x, y; shape: (rows, cols), each one
+    int for all positions or an int array with one entry per position.  Product, difference, floor and clip are one ufunc call each, so
+    no two of them contract into a fused multiply-add."""
+    rows, cols = shape
+    scaled_y, scaled_x = np.multiply(y, PIXELS_PER_METER), np.multiply(x, PIXELS_PER_METER)
+    pixel_i = np.floor(np.subtract(rows / 2, scaled_y)).astype(np.int32)
+    pixel_j = np.floor(np.add(cols / 2, scaled_x)).astype(np.int32)
+    # (np.clip on whole numbers, without its per-call set-up)
+    return (np.minimum(np.maximum(pixel_i, 0), rows - 1).astype(np.int32, copy=False),
+            np.minimum(np.maximum(pixel_j, 0), cols - 1).astype(np.int32, copy=False))
+
+
+def distances(dx, dy):
+    """math.sqrt(dx**2 + dy**2) elementwise.  Python's `** 2` is libm's pow, which np.float_power(x, 2.0) matches and x * x does not."""
+    return np.sqrt(np.float_power(dx, 2.0) + np.float_power(dy, 2.0))
+
+
 def _is_spec(x):
     return isinstance(x, str) or (isinstance(x, (tuple, list)) and len(x) >= 1 and isinstance(x[0], str))
 

@@ -14,6 +14,7 @@ the snapped distance images (include/simq.h): a mapper whose configuration space
 -- is not searched.  Douglas-Peucker and ``store_new_action`` stay on the host (DESIGN.md sections 13 and 17).
 """
 import collections
+import collections.abc
 import ctypes
 import math
 
@@ -34,6 +35,290 @@ NOT_UPDATED = 4                                        # occupancy status of a m
 # An idle robot needs no target and no paths; the paths are read only by the encodings that draw them.
 RobotState = collections.namedtuple('RobotState', ('position', 'heading', 'robot_type', 'lift_state', 'idle', 'target', 'intention_path',
                                                    'history_path'), defaults=(None, False, None, None, None))
+
+
+def _array(value, what, dtype, shape):
+    """`value` as it is when it is an ndarray of `dtype` and `shape` (None: any length); nothing is converted."""
+    if not isinstance(value, np.ndarray) or value.dtype != dtype or value.ndim != len(shape) or \
+            any(s is not None and n != s for n, s in zip(value.shape, shape)):
+        raise ValueError('RobotArrays.%s must be a %s array of shape [%s], got %s' % (
+            what, np.dtype(dtype).name, ', '.join('M' if s is None else str(s) for s in shape),
+            '%s %s' % (value.dtype, list(value.shape)) if isinstance(value, np.ndarray) else type(value).__name__))
+    return value
+
+
+class RobotArrays:
+    """What RobotState holds of every robot of a BatchedMapper, as arrays indexed by mapper m = env_begin[e] + robot:
+
+    position float64 [M, 2], heading float64 [M], lifting bool [M] (lift_state == 'lifting'; read for lifting robots only), idle bool [M],
+    target float64 [M, 2] or None, intention_path / history_path: a pair (points float64 [N, 2], offsets int64 [M + 1]) -- the
+    waypoints of mapper m are points[offsets[m]:offsets[m + 1]] -- or None.  lifting and idle may be omitted (nobody lifts, nobody is idle).
+
+    The rows of mappers a call does not read may hold anything; a robot that is not idle and is drawn needs a target without NaN and
+    a path of at least one waypoint where the list form needs them.  An array of another type or shape is refused, not converted:
+    the list form computes on the values as they are given, and a float32 position would take float32 arithmetic there."""
+
+    def __init__(self, position, heading, lifting=None, idle=None, target=None, intention_path=None, history_path=None):
+        self.position = _array(position, 'position', np.float64, (None, 2))
+        M = self.num_mappers = len(position)
+        self.heading = _array(heading, 'heading', np.float64, (M,))
+        self.lifting = np.zeros(M, bool) if lifting is None else _array(lifting, 'lifting', np.bool_, (M,))
+        self.idle = np.zeros(M, bool) if idle is None else _array(idle, 'idle', np.bool_, (M,))
+        self.target = None if target is None else _array(target, 'target', np.float64, (M, 2))
+        self.intention_path = self._path(intention_path, 'intention_path')
+        self.history_path = self._path(history_path, 'history_path')
+
+    def _path(self, path, what):
+        if path is None:
+            return None
+        try:
+            points, offsets = path
+        except (TypeError, ValueError):
+            raise ValueError('RobotArrays.%s is a pair (points, offsets) or None' % what) from None
+        points = _array(points, what + ' points', np.float64, (None, 2))
+        offsets = _array(offsets, what + ' offsets', np.int64, (self.num_mappers + 1,))
+        if offsets[0] != 0 or offsets[-1] != len(points) or (np.diff(offsets) < 0).any():
+            raise ValueError('RobotArrays.%s offsets must rise from 0 to the number of points (%d) without falling, got %s%s'
+                             % (what, len(points), offsets[:8].tolist(), ' ...' if len(offsets) > 8 else ''))
+        return points, offsets
+
+    @classmethod
+    def from_states(cls, mapper, robots):
+        """The list form of `mapper.get_states` as arrays: robots holds per environment the RobotState of each robot, or None for an
+        environment no call will read (its rows are NaN).  Coordinates and headings are taken as Python floats or np.float64 only.  A
+        robot without a target gets a row of NaN, a robot without a path an empty one; a field no robot has is None."""
+        M = mapper.num_mappers
+        states = mapper._robots(robots, [e for e in range(min(len(robots), mapper.num_envs)) if robots[e] is not None])
+
+        def number(v, what):
+            if type(v) not in (float, np.float64):
+                raise ValueError('RobotArrays.from_states takes Python floats and np.float64, got %s as %s' % (type(v).__name__, what))
+            return v
+        position, heading = np.full((M, 2), np.nan), np.full(M, np.nan)
+        lifting, idle, target = np.zeros(M, bool), np.zeros(M, bool), np.full((M, 2), np.nan)
+        paths = {'intention_path': [[] for _ in range(M)], 'history_path': [[] for _ in range(M)]}
+        given = set()
+        for e, env in states.items():
+            for k, r in enumerate(env):
+                m = mapper.env_begin[e] + k
+                position[m] = number(r.position[0], 'position'), number(r.position[1], 'position')
+                heading[m] = number(r.heading, 'heading')
+                lifting[m], idle[m] = r.lift_state == 'lifting', bool(r.idle)
+                if r.target is not None:
+                    target[m] = number(r.target[0], 'target'), number(r.target[1], 'target')
+                    given.add('target')
+                for name, rows in paths.items():
+                    if getattr(r, name) is not None:
+                        rows[m] = [(number(w[0], name), number(w[1], name)) for w in getattr(r, name)]
+                        given.add(name)
+
+        def packed(rows):
+            offsets = np.concatenate([[0], np.cumsum([len(row) for row in rows])]).astype(np.int64)
+            return np.array([w for row in rows for w in row], np.float64).reshape(-1, 2), offsets
+        return cls(position, heading, lifting, idle, target if 'target' in given else None,
+                   *[packed(paths[name]) if name in given else None for name in ('intention_path', 'history_path')])
+
+
+class _StageMaps(collections.abc.Mapping):
+    """BatchedMapper.stage_maps after an array-form call: the same keys and tensors as the dict of the list form, each view formed
+    when it is asked for.  where: {key: (buffer name, index)}; buffers: {name: tensor [n, rows, cols], or (flat tensor, offsets, shapes)}."""
+
+    def __init__(self, where, buffers):
+        self._where, self._buffers = where, buffers
+
+    def __getitem__(self, key):
+        name, k = self._where[key]
+        held = self._buffers[name]
+        if isinstance(held, tuple):
+            flat, offsets, shapes = held
+            return flat[offsets[k]:offsets[k] + shapes[k][0] * shapes[k][1]].view(shapes[k])
+        return held[k]
+
+    def __iter__(self):
+        return iter(self._where)
+
+    def __len__(self):
+        return len(self._where)
+
+
+def closest_order(positions, me, own):
+    """The other robots of P environments of R robots from the closest to the furthest, as envs.py:2350-2358 orders them: int [P, R - 1]
+    for positions float64 [P, R, 2], the observers' positions me [P, 2] and their indices own [P].  np.argsort sorts each row as it
+    sorts the list of the list form, so robots at equal distances fall as they do there."""
+    order = np.argsort(local_maps.distances(positions[:, :, 0] - me[:, None, 0], positions[:, :, 1] - me[:, None, 1]))
+    return order[order != np.asarray(own)[:, None]].reshape(len(order), -1)
+
+
+class _Plan:
+    """What get_states' array form needs of one `mappers` tuple and of the object, but of no call: index arrays, and the descriptor
+    tables with every field filled that no robot's state changes (a call copies a table and fills the rest).  The order of robots,
+    maps, problems and channels is the one the list form arrives at through local_maps._prepare and intention_drawing._prepare."""
+
+    def __init__(self, bm, ms):
+        self.stage_keys = {}                                         # BatchedMapper.stage_maps' key: (buffer, index in it)
+        self._index(bm, ms)
+        self._described_robots(bm)
+        slots = self._map_slots(bm)
+        self._stage1(bm, slots)
+        self._stage2(bm, slots)
+        self._stage3(bm, slots)
+        self._fixed = None
+
+    def _index(self, bm, ms):
+        """Of every named mapper p its environment, its robot, its room shape and where its maps lie; the pairs (p, another robot of
+        p's environment), p by p in env.robots' order: whom p's maps draw."""
+        starts, f = intention_drawing._starts, bm.flags
+        self.ms = np.asarray(ms, np.int64)
+        P = self.P = len(ms)
+        self.env_begin = env_begin = np.asarray(bm.env_begin, np.int64)
+        self.env = env = np.asarray(bm.env_of, np.int64)[self.ms]
+        self.robot = self.ms - env_begin[env]
+        self.rows_of, self.cols_of = (np.asarray([s[k] for s in bm.shapes], np.int32) for k in (0, 1))
+        self.rows, self.cols = self.rows_of[self.ms], self.cols_of[self.ms]
+        cells = self.rows_of.astype(np.int64) * self.cols_of
+        self._at = np.concatenate([starts(cells), [cells.sum()]])     # cell offset of every mapper's maps (BatchedMapper._at)
+        others = env_begin[env + 1] - env_begin[env] - 1
+        self.pair_p = np.repeat(np.arange(P), others)
+        rank = np.arange(int(others.sum())) - np.repeat(starts(others), others)
+        self.others = env_begin[env][self.pair_p] + rank + (rank >= self.robot[self.pair_p])
+        self.R = self.env_rows = None
+        if f['use_intention_channels']:
+            self.R = len(bm.robot_types[0])
+            self.env_rows = env_begin[env][:, None] + np.arange(self.R)
+        self.spatial = f['use_intention_channels'] and bm.intention_channel_encoding == 'spatial'
+
+    def _described_robots(self, bm):
+        """The robots as stage 3 has them described -- every environment once, in the order in which `ms` comes to it -- and the
+        problems of stage 3 with each one's range of them."""
+        env, env_begin = self.env, self.env_begin
+        first = list(dict.fromkeys(env.tolist()))
+        begin = dict(zip(first, intention_drawing._starts(np.asarray([len(bm.robot_types[e]) for e in first], np.int64)).tolist()))
+        self.robots = np.concatenate([np.arange(env_begin[e], env_begin[e + 1]) for e in first])
+        self.robot_rows, self.robot_cols = self.rows_of[self.robots], self.cols_of[self.robots]
+        robot_begin = np.asarray([begin[e] for e in env.tolist()], np.int64)
+        self.own_row = robot_begin + self.robot
+        types = [t for e in first for t in bm.robot_types[e]]
+        self.stamps = np.zeros(len(self.robots), local_maps.LOCAL_ROBOT)
+        self.stamps['seg_mask'] = [bm.mask_index[t] for t in types]
+        self.stamps['seg_value'] = [bm.seg_values['robot_group_%d' % (g + 1)] for e in first for g in bm.group_indices[e]]
+        self.lifters = np.asarray([t == 'lifting_robot' for t in types])
+        self.cube_mask = bm.mask_index.get(WITH_CUBE, 0)
+        self.problems = np.zeros(self.P, local_maps.LOCAL_PROBLEM)
+        self.problems['rows'], self.problems['cols'], self.problems['robot_begin'] = self.rows, self.cols, robot_begin
+        self.problems['robot_count'] = env_begin[env + 1] - env_begin[env]
+
+    def _map_slots(self, bm):
+        """The maps of stage 3 in the order of their first use: p by p its overhead map, the receptacle map where p is the first to use
+        it, its distance images, its drawn maps.  Returns where in that table each kind lies: {'overhead', 'receptacle', 'history',
+        'intention': [P], 'images': nd arrays [P], 'channels': [P, nq]}, None for a kind the configuration does not have."""
+        f, P = bm.flags, self.P
+        nd = int(f['use_shortest_path_to_receptacle_map']) + int(f['use_shortest_path_map'])
+        nq = self.R - 1 if self.spatial else 0
+        new = np.zeros(P, np.int64)
+        first_user = np.zeros(P, np.int64)
+        if f['use_distance_to_receptacle_map']:
+            seen = {}
+            for p, e in enumerate(self.env.tolist()):
+                first_user[p] = seen.setdefault((bm.env_shapes[e], bm.receptacle_positions[e]), p)
+            new = (first_user == np.arange(P)).astype(np.int64)
+        per = 1 + nd + int(f['use_history_map']) + int(f['use_intention_map']) + nq
+        base = intention_drawing._starts(per + new)
+        after = base + 1 + new
+        drawn = after + nd
+        slots = {'overhead': base, 'receptacle': base[first_user] + 1 if f['use_distance_to_receptacle_map'] else None,
+                 'images': [after + d for d in range(nd)], 'history': drawn if f['use_history_map'] else None,
+                 'intention': drawn + int(f['use_history_map']) if f['use_intention_map'] else None,
+                 'channels': (drawn + int(f['use_history_map']) + int(f['use_intention_map']))[:, None] + np.arange(nq)}
+        self.overhead_maps, self.receptacle_maps = base, base[first_user] + 1
+        self.n_maps = int((per + new).sum())
+        self.map_rows, self.map_cols = np.zeros(self.n_maps, np.int32), np.zeros(self.n_maps, np.int32)
+        for where in [slots[k] for k in ('overhead', 'receptacle', 'history', 'intention') if slots[k] is not None] + slots['images'] + \
+                [slots['channels'][:, q] for q in range(nq)]:
+            self.map_rows[where], self.map_cols[where] = self.rows, self.cols
+        return slots
+
+    def _stage1(self, bm, slots):
+        """Stage 1: the problems, receptacle-sourced then robot-sourced, each over `ms`, but for the robot pixels."""
+        f, P, at, rows, cols = bm.flags, self.P, self._at, self.rows, self.cols
+        nd = len(slots['images'])
+        self.grid = None
+        if not nd:
+            return
+        lo, hi = int(self.ms.min()), int(self.ms.max())
+        self.grid_lo, self.grid_cells = int(at[lo]), int(at[hi + 1] - at[lo])
+        g = self.grid = np.zeros(nd * P, grid_paths.SNAPPED_PROBLEM)
+        g['grid_offset'] = np.tile(at[self.ms] - at[lo], nd)
+        g['closest_offset'] = 2 * g['grid_offset']
+        g['rows'], g['cols'], g['upstream'] = np.tile(rows, nd), np.tile(cols, nd), np.tile(self.ms, nd)
+        self.image_at = intention_drawing._starts(g['rows'].astype(np.int64) * g['cols'])
+        g['out_offset'] = self.image_at
+        self.grid_want = (int((g['rows'].astype(np.int64) * g['cols']).sum()),)
+        if f['use_shortest_path_to_receptacle_map']:
+            at_receptacle = np.asarray([bm.receptacle_positions[e][:2] for e in self.env.tolist()], np.float64)
+            g['src_i'][:P], g['src_j'][:P] = local_maps.pixel_indices_many(at_receptacle[:, 0], at_receptacle[:, 1], (rows, cols))
+        self.image_maps = np.concatenate(slots['images'])
+        self.image_shapes = [(int(r), int(c)) for r, c in zip(g['rows'], g['cols'])]
+        self.stage_keys.update({('image', d, p): ('image', d * P + p) for d in range(nd) for p in range(P)})
+
+    def _stage2(self, bm, slots):
+        """Stage 2: per room shape the problems -- history maps, intention maps, the maps behind the spatial channels -- over the p of
+        that shape; `pairs`: their rows of `others`; `problem`: for every (problem, drawn robot) its problem; `maps`: where their maps go."""
+        nq = slots['channels'].shape[1]
+        self.jobs = []
+        if slots['history'] is None and slots['intention'] is None and not self.spatial:
+            return
+        for shape in sorted(set(bm.shapes[m] for m in self.ms.tolist())):
+            sel = np.flatnonzero((self.rows == shape[0]) & (self.cols == shape[1]))
+            pairs = np.flatnonzero(np.isin(self.pair_p, sel))
+            of_pair = np.searchsorted(sel, self.pair_p[pairs])
+            problem, maps, n = [], [], 0
+            for name in ('history', 'intention'):
+                if slots[name] is not None:
+                    problem.append(n + of_pair)
+                    maps.append(slots[name][sel])
+                    self.stage_keys.update({(name, int(p)): (shape, n + k) for k, p in enumerate(sel)})
+                    n += len(sel)
+            if self.spatial:
+                problem.append(n + np.arange(len(sel) * nq))
+                maps.append(slots['channels'][sel].reshape(-1))
+                self.stage_keys.update({('channel', int(p), q): (shape, n + k * nq + q) for k, p in enumerate(sel) for q in range(nq)})
+                n += len(sel) * nq
+            self.jobs.append((shape, {'p': sel, 'pairs': pairs, 'problem': np.concatenate(problem), 'n': n, 'maps': np.concatenate(maps)}))
+
+    def _stage3(self, bm, slots):
+        """Stage 3: the channels in get_state's order, with every field but the constants of the nonspatial encoding."""
+        f, C = bm.flags, bm.num_channels
+        columns = [('overhead', slots['overhead'])]
+        if f['use_robot_map']:
+            columns.append(('robots', 0))
+        if slots['receptacle'] is not None:
+            columns.append(('distance', slots['receptacle']))
+        columns += [('distance', where) for where in slots['images']]
+        columns += [('map', slots[name]) for name in ('history', 'intention') if slots[name] is not None]
+        if self.spatial:
+            columns += [('map', slots['channels'][:, q]) for q in range(slots['channels'].shape[1])]
+        elif f['use_intention_channels']:
+            columns += [('constant', 0)] * (2 * (self.R - 1))
+        assert len(columns) == C, (len(columns), bm.channels)
+        table = np.zeros((self.P, C), local_maps.LOCAL_CHANNEL)
+        for c, (kind, where) in enumerate(columns):
+            table['kind'][:, c], table['map'][:, c] = local_maps.KINDS[kind], where
+        self.constant_at = np.flatnonzero(table['kind'].reshape(-1) == local_maps.KINDS['constant'])
+        self.channels = table.reshape(-1)
+
+    def on_device(self, bm):
+        """The part that holds addresses of the object's tensors: the table of stage 3's maps with every map that outlives a call,
+        and where the grids and closest blocks of stage 1 begin."""
+        if self._fixed is None:
+            maps = np.zeros(self.n_maps, local_maps.LOCAL_MAP)
+            maps['rows'], maps['cols'] = self.map_rows, self.map_cols
+            maps['d_data'][self.overhead_maps] = bm._overhead.data_ptr() + 4 * self._at[self.ms]
+            if bm.distance_to_receptacle_maps is not None:
+                maps['d_data'][self.receptacle_maps] = [bm.distance_to_receptacle_maps[e].data_ptr() for e in self.env.tolist()]
+            self._fixed = {'maps': maps}
+            if self.grid is not None:
+                self._fixed.update(grids=bm._cspace.data_ptr() + self.grid_lo, closest=bm._closest.data_ptr() + 8 * self.grid_lo)
+        return self._fixed
 
 
 def round_up_to_even(x):
@@ -194,6 +479,7 @@ class BatchedMapper:
         self.channels = channel_names(self.flags, intention_channel_encoding, len(self.robot_types[0]))
         self.num_channels = len(self.channels)
         self.mask_bank = np.stack(bank)
+        self._plans = {}                                   # what get_states' array form needs of a `mappers` tuple, made once
 
         # the device tensors come after the argument checks, which need no device; without one the object still checks the arguments
         # of its calls, and then says so
@@ -366,7 +652,8 @@ class BatchedMapper:
     def get_states(self, robots, mappers=None, out=None, into=None):
         """Mapper.get_state() (envs.py:2067-2112) for the named mappers (all when omitted): a float32 [P, 96, 96, C] device tensor,
         state p that of mapper mappers[p], the channels in `self.channels`' order.  robots: per environment the RobotState of each
-        robot, in env.robots' order (only the environments of the named mappers are read).  out: a contiguous float32 device
+        robot, in env.robots' order (only the environments of the named mappers are read), or one RobotArrays with the same robots as
+        arrays: the same calls and states, the descriptors built without Python per state.  out: a contiguous float32 device
         tensor [P, 96, 96, C] to write into -- a batch buffer, a slice of a replay ring's `states`; every element is written.
         into: instead of `out`, P handles of one AliasedDeviceReplayBuffer (ring.reserve(P)) for states of C channels: state p is
         written where it will be sampled from, the pool slot of into[p], and the handles are returned -- for TransitionTracker,
@@ -388,6 +675,8 @@ class BatchedMapper:
         if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == want and out.is_contiguous()):
             raise ValueError('out must be a contiguous float32 device tensor of shape %s, got %s' % (
                 want, '%s %s' % (out.dtype, tuple(out.shape)) if isinstance(out, torch.Tensor) else type(out).__name__))
+        if isinstance(robots, RobotArrays):
+            return self._get_states_arrays(robots, ms, out, into, pool, want)
         states = self._robots(robots, sorted(set(self.env_of[m] for m in ms)))
         f = self.flags
         own = [(self.env_of[m], m - self.env_begin[self.env_of[m]]) for m in ms]
@@ -494,6 +783,184 @@ class BatchedMapper:
         # what the stages left on the device, until the next call: {('image', 0 or 1, p)}: the distance images in the order of the
         # flags, {('history', p), ('intention', p), ('channel', p, q)}: the drawn maps (p: position in `mappers`, q: channel)
         self.stage_maps = {key: maps[k] for key, k in index.items() if key[0] in ('image', 'history', 'intention', 'channel')}
+
+        if status is not None:
+            bad, codes = _batch.bad_problems(status)                                        # the one read-back of the call
+            if bad.size:
+                raise SimqError('BatchedMapper.get_states: no distance images for mapper(s) %s (simq_grid_distance_images_snapped status %s; '
+                                '%d: no update since the last reset, 1: a configuration space without a free cell); their distance '
+                                'channels come from images of zeros'
+                                % (self._named(sorted(set(int(p) % P for p in bad)), ms), codes[:8].tolist(), NOT_UPDATED))
+        return out
+
+    # ---- get_states from a RobotArrays: the same three calls with the descriptor tables built as arrays -------------------------
+    def _plan(self, ms):
+        """What the array form needs of the tuple `ms` and not of a call's robots (_Plan), made once per tuple.  The eight tuples used last are
+        kept (the dict is in order of last use); a tuple that is not among them pays for a new plan -- DESIGN.md section 19 has the cost."""
+        key = tuple(ms)
+        plan = self._plans.pop(key, None)
+        if plan is None:
+            if len(self._plans) >= 8:
+                del self._plans[next(iter(self._plans))]
+            plan = _Plan(self, ms)
+        self._plans[key] = plan
+        return plan
+
+    def _get_states_arrays(self, ra, ms, out, into, pool, want):
+        """get_states for `robots` a RobotArrays, after the checks of `mappers`, `out` and `into`: the calls of the list form with equal
+        arguments and descriptor bytes (tests/test_gpu_robot_arrays.py), formed without a Python loop over the states."""
+        if ra.num_mappers != self.num_mappers:
+            raise ValueError('the RobotArrays hold %d mappers, the object has %d' % (ra.num_mappers, self.num_mappers))
+        f, P, C = self.flags, len(ms), self.num_channels
+        plan = self._plan(ms)
+        pixels = local_maps.pixel_indices_many
+        spatial = f['use_intention_channels'] and self.intention_channel_encoding == 'spatial'
+
+        # ---- the host side of every stage first: a wrong argument launches nothing
+        robot_i, robot_j = pixels(ra.position[plan.robots, 0], ra.position[plan.robots, 1], (plan.robot_rows, plan.robot_cols))
+        degrees = ra.heading[plan.robots] * local_maps.RAD_TO_DEG
+        own_i, own_j = robot_i[plan.own_row], robot_j[plan.own_row]
+        idle = ra.idle[plan.others]                                  # of the pairs (p, another robot of p's environment), p by p
+        busy = plan.others[~idle]
+        for flag, name, encoding in (('use_history_map', 'history_path', 'history'),
+                                     ('use_intention_map', 'target' if self.intention_map_encoding == 'circle' else 'intention_path',
+                                      self.intention_map_encoding)):
+            held = getattr(ra, name)
+            if f[flag] and busy.size and (held is None or (np.isnan(held[busy]).any() if name == 'target' else
+                                                           (held[1][busy + 1] == held[1][busy]).any())):
+                raise ValueError('a robot that is not idle needs its %s for the %r encoding' % (name, encoding))
+        order = constants = None
+        if f['use_intention_channels']:
+            R = plan.R
+            mine = ra.position[plan.env_rows]                        # [P, R, 2]: the robots of p's environment
+            me = ra.position[plan.ms]
+            order = closest_order(mine, me, plan.robot)
+            ranked = (plan.env_rows[:, :1] + order).reshape(-1)      # the mapper behind channel (p, q)
+            ranked_busy = ~ra.idle[ranked]
+            if ranked_busy.any() and (ra.target is None or np.isnan(ra.target[ranked[ranked_busy]]).any()):
+                raise ValueError('a robot that is not idle needs its target for the intention channels')
+            if not spatial:                                          # envs.py:2368-2375, in Python floats as there
+                scale, constants = self.intention_channel_nonspatial_scale, []
+                targets = ra.target[ranked].tolist() if ra.target is not None else None
+                for k, (p, is_busy) in enumerate(zip(np.repeat(np.arange(P), R - 1).tolist(), ranked_busy.tolist())):
+                    relative_position = (0, 0)
+                    if is_busy:
+                        (x, y), heading, target = me[p].tolist(), float(ra.heading[ms[p]]), targets[k]
+                        dist = math.sqrt((target[0] - x)**2 + (target[1] - y)**2)
+                        theta = heading - math.atan2(target[1] - y, target[0] - x)
+                        relative_position = (dist * math.sin(theta), dist * math.cos(theta))
+                    constants += [scale * coord for coord in relative_position]
+                constants = np.asarray(constants, np.float64).astype(np.float32)
+
+        # stage 1: (pixel, mapper) of every distance image
+        c_grid = None
+        if plan.grid is not None:
+            c_grid = plan.grid.copy()
+            if f['use_shortest_path_map']:
+                c_grid['src_i'][-P:], c_grid['src_j'][-P:] = own_i, own_j
+
+        # stage 2: every drawn robot's segments once per encoding, then each problem's rows by index
+        launches = []
+        if plan.jobs:
+            intention_drawing.check_drawing(self.intention_map_scale, self.intention_map_line_thickness)
+            drawn = np.unique(busy)
+            tables, begin, count, at = [], {}, {}, 0
+            for flag, encoding in (('use_history_map', 'history'), ('use_intention_map', self.intention_map_encoding), (spatial, 'circle')):
+                if encoding in begin or not (flag is True or f.get(flag)):
+                    continue
+                rows, cols = plan.rows_of[drawn], plan.cols_of[drawn]
+                if not drawn.size:
+                    table, n = np.zeros(0, intention_drawing.SEGMENT), np.zeros(0, np.int64)
+                elif encoding == 'circle':
+                    table, n = intention_drawing.circle_segments(ra.target[drawn], rows, cols, self.intention_map_scale), np.ones(len(drawn), np.int64)
+                else:
+                    points, offsets = ra.history_path if encoding == 'history' else ra.intention_path
+                    table, n = intention_drawing.path_segments(points, offsets[drawn], offsets[drawn + 1], rows, cols, encoding,
+                                                               self.intention_map_scale)
+                begin[encoding], count[encoding] = np.zeros(self.num_mappers, np.int64), np.zeros(self.num_mappers, np.int64)
+                begin[encoding][drawn], count[encoding][drawn] = at + intention_drawing._starts(n), n
+                tables.append(table)
+                at += len(table)
+            tables = np.concatenate([t.view(np.uint8) for t in tables]).view(intention_drawing.SEGMENT)    # (bytes: no promotion of the fields)
+            for shape, sel in plan.jobs:
+                who = []                                             # the robots each problem draws, problem by problem
+                for flag, encoding in (('use_history_map', 'history'), ('use_intention_map', self.intention_map_encoding)):
+                    if f[flag]:
+                        who.append((encoding, plan.others[sel['pairs']]))
+                if spatial:
+                    who.append(('circle', ranked.reshape(P, -1)[sel['p']].reshape(-1)))
+                first = np.concatenate([begin[e][m] for e, m in who])
+                n = np.concatenate([count[e][m] for e, m in who])
+                c_segs = tables[intention_drawing.ragged(first, n)]
+                c_probs = np.zeros(sel['n'], intention_drawing.PROBLEM)
+                c_probs['seg_count'] = np.bincount(sel['problem'], weights=n, minlength=sel['n'])
+                c_probs['seg_begin'] = intention_drawing._starts(c_probs['seg_count'])
+                launches.append((shape, c_segs, c_probs))
+
+        # stage 3: the robots as they are stamped, the problems, the channel values of this call
+        c_robots = plan.stamps.copy()
+        c_robots['rot'] = local_maps.rotation_table(degrees - 90, local_maps.WIDTH)
+        c_robots['pixel_i'], c_robots['pixel_j'] = robot_i, robot_j
+        lifting = plan.lifters & ra.lifting[plan.robots]
+        c_robots['mask'] = np.where(lifting, plan.cube_mask, c_robots['seg_mask'])
+        c_robots['map_value'] = np.where(plan.lifters & ~lifting, 0.5, 1.0)
+        c_probs3 = plan.problems.copy()
+        c_probs3['rot'] = local_maps.rotation_table(90 - degrees[plan.own_row], local_maps.CROP)
+        c_probs3['pixel_i'], c_probs3['pixel_j'] = own_i, own_j
+        c_chans = plan.channels
+        if constants is not None:
+            c_chans = c_chans.copy()
+            c_chans['value'][plan.constant_at] = constants
+
+        if self.device is None:
+            self._allocate()
+        dev = self.device
+        if out is not None and out.device != dev:
+            raise ValueError('out must be a contiguous float32 device tensor of shape %s on %s' % (want, dev))
+        if pool is not None and pool.pool.device != dev:
+            raise ValueError('get_states(into=): the pool lives on %s, the maps on %s' % (pool.pool.device, dev))
+        fixed = plan.on_device(self)
+        c_maps = fixed['maps'].copy()
+        buffers, as_ctypes = {}, local_maps.as_ctypes
+
+        # ---- stage 1
+        status = None
+        if c_grid is not None:
+            images = torch.empty(plan.grid_want, dtype=torch.float32, device=dev)
+            d_probs = torch.empty(c_grid.nbytes, dtype=torch.uint8, device=dev)
+            status = torch.empty(len(c_grid), dtype=torch.int32, device=dev)
+            lib.call('simq_grid_distance_images_snapped', ctypes.c_void_p(fixed['grids']), ctypes.c_int64(plan.grid_cells),
+                     ctypes.c_void_p(fixed['closest']), ctypes.c_int64(2 * plan.grid_cells), as_ctypes(c_grid, grid_paths.SnappedProblem),
+                     len(c_grid), ptr(d_probs), ptr(images), ctypes.c_int64(images.numel()), ctypes.c_float(float(arch.LOCAL_MAP_PIXELS_PER_METER)),
+                     1, ctypes.c_float(float(self.shortest_path_map_scale)), ptr(self.occupancy_status), self.occupancy_status.numel(),
+                     ptr(status), stream_ptr(dev))
+            c_maps['d_data'][plan.image_maps] = images.data_ptr() + 4 * plan.image_at
+            buffers['image'] = (images.view(-1), plan.image_at.tolist(), plan.image_shapes)
+
+        # ---- stage 2: one launch per room shape
+        for (shape, c_segs, c_probs), (_, sel) in zip(launches, plan.jobs):
+            maps = torch.empty((len(c_probs),) + shape, dtype=torch.float32, device=dev)
+            d_desc = torch.empty(max(int(lib.c.simq_intention_desc_bytes(len(c_segs), len(c_probs))), 8), dtype=torch.uint8, device=dev)
+            lib.call('simq_intention_maps', as_ctypes(c_segs, intention_drawing.Segment) if len(c_segs) else None, len(c_segs),
+                     as_ctypes(c_probs, intention_drawing.Problem), len(c_probs), shape[0], shape[1], self.intention_map_line_thickness - 1,
+                     ptr(d_desc), ctypes.c_int64(d_desc.numel()), ptr(maps), ctypes.c_int64(maps.numel()), stream_ptr(dev))
+            c_maps['d_data'][sel['maps']] = maps.data_ptr() + 4 * shape[0] * shape[1] * np.arange(len(c_probs), dtype=np.int64)
+            buffers[shape] = maps
+
+        # ---- stage 3
+        n_maps, n_robots = len(c_maps), len(c_robots)
+        args = (as_ctypes(c_maps, local_maps.LocalMap), n_maps, ptr(self.masks), self.masks.shape[0], as_ctypes(c_robots, local_maps.LocalRobot),
+                n_robots, as_ctypes(c_probs3, local_maps.LocalProblem), P, as_ctypes(c_chans, local_maps.LocalChannel), C)
+        if pool is None:
+            if out is None:
+                out = torch.empty(want, dtype=torch.float32, device=dev)
+            d_desc = torch.empty(max(int(lib.c.simq_local_state_desc_bytes(n_maps, n_robots, P, C)), 8), dtype=torch.uint8, device=dev)
+            lib.call('simq_local_state_images', *args, ptr(d_desc), ctypes.c_int64(d_desc.numel()), ptr(out), ctypes.c_int64(out.numel()),
+                     stream_ptr(dev))
+        else:
+            local_maps.write_into(pool, into, args)
+            out = into
+        self.stage_maps = _StageMaps(plan.stage_keys, buffers)
 
         if status is not None:
             bad, codes = _batch.bad_problems(status)                                        # the one read-back of the call

@@ -3,20 +3,23 @@
     python tools/collect_rate.py [--reps 10] [--sizes 1,8,64,256] [--room 184x232]
 
 A collection step is what a worker that owns E environments does between two environment steps: `BatchedMapper.get_states` for the M
-deciding robots, `DQNPolicy.step_many` on their states, and the `push` of the M transitions that `TransitionTracker` completes.  Two
+deciding robots, `DQNPolicy.step_many` on their states, and the `push` of the M transitions that `TransitionTracker` completes.  Three
 forms of it run in one process, on the same commit, in alternating repetitions:
   host     get_states -> .cpu().numpy() -> the ndarrays through the tracker, step_many and push (every state crosses the bus twice:
            down after the mapper, up again at push -- and once more for the policy's batch)
   handles  per robot group `h = ring.reserve(P)`, get_states(into=h), the handles through the tracker, step_many and push: the states
            are written where they are sampled from and never leave the device.  One get_states call per robot
            group, because a call writes into one pool and every group has its ring.
+  arrays   the handles form with the robots handed to get_states as a simq.RobotArrays instead of lists of
+           RobotState; the arrays of a round exist before the clock starts, the RobotArrays is made from them inside it
 Workload: a recorded episode (tests/golden/mapper_*.npz), the full channel set with spatial intention channels (9 channels),
 environments of three robots in two robot groups replicated until M = 1, 8, 64, 256 robots decide.  `update` runs once before the
 clock; the maps do not change between the steps, the robots' poses follow the recorded rounds.  Per M and form:
   host_ms    a host clock around the step, the device synchronised at both ends
   event_ms   the time between a HIP event recorded on the stream before the step's first call and one after its last
-both the median over `reps` steps after two warm-up steps.  Before anything is timed the two forms are checked against each other: the
-same actions under one seed, and the pool rows of the handles equal to the host states bit for bit.
+both the median over `reps` steps after two warm-up steps, host_ms with its minimum and maximum over those steps.  Before anything is
+timed the forms are checked against each other: the same actions under one seed, and the pool rows of the handles equal to the host
+states bit for bit.
 """
 import argparse
 import json
@@ -35,6 +38,9 @@ sys.path.insert(0, os.path.join(ROOT, 'spatial-intention-maps_amd'))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import mapper_oracle as oracle  # noqa: E402
+
+
+FORMS = ('host', 'handles', 'arrays')
 
 
 class Worker:
@@ -58,8 +64,12 @@ class Worker:
                        [IdRanges(*f['ranges']) for f in frames])
         capacity = max(64, 2 * M)
         self.rings = {form: [simq.AliasedDeviceReplayBuffer(capacity, self.C, pool_slots=2 * capacity + M + 16) for _ in self.groups]
-                      for form in ('host', 'handles')}
-        self.trackers = {'host': None, 'handles': None}
+                      for form in FORMS}
+        self.trackers = {form: None for form in FORMS}
+        self.arrays = []                                              # the robots of every recorded round as arrays, made once
+        for t in range(len(fx['rounds'])):
+            ra = simq.RobotArrays.from_states(self.bm, self.robot_states(t))
+            self.arrays.append((ra.position, ra.heading, ra.lifting, ra.idle, ra.target, ra.intention_path, ra.history_path))
         self.rng = np.random.RandomState(7)
 
     def robot_states(self, t):
@@ -75,18 +85,19 @@ class Worker:
         host = self.bm.get_states(self.robot_states(t), mappers=self.deciding).cpu().numpy()
         return self.nested({m: host[p] for p, m in enumerate(self.deciding)})
 
-    def states_handles(self, t):
-        robots, of_mapper = self.robot_states(t), {}
+    def states_handles(self, t, form='handles'):
+        of_mapper = {}
+        robots = self.robot_states(t) if form == 'handles' else self.simq.RobotArrays(*self.arrays[t % len(self.arrays)])
         for i, g in enumerate(self.groups):
             mine = [m for m in self.deciding if self.fx['groups'][m % 3] == g]
             if mine:
-                handles = self.bm.get_states(robots, mappers=mine, into=self.rings['handles'][i].reserve(len(mine)))
+                handles = self.bm.get_states(robots, mappers=mine, into=self.rings[form][i].reserve(len(mine)))
                 of_mapper.update(zip(mine, handles))
         return self.nested(of_mapper)
 
     def step(self, form, t, eps=0.1):
         """get_states, step_many, push of the completed transitions; returns (states, actions)."""
-        states = (self.states_host if form == 'host' else self.states_handles)(t)
+        states = self.states_host(t) if form == 'host' else self.states_handles(t, form)
         actions = self.policy.step_many(states, exploration_eps=eps)
         if self.trackers[form] is None:                               # the first step of an episode completes no transition
             self.trackers[form] = [self.simq.TransitionTracker(st) for st in states]
@@ -127,15 +138,16 @@ def main():
         for t in (0, 1):
             random.seed(100 + t)
             host_states, host_actions = w.step('host', t)
-            random.seed(100 + t)
-            pool_states, pool_actions = w.step('handles', t)
-            assert pool_actions == host_actions, (M, t)
-            for a, b in zip((s for st in host_states for g in st for s in g), (s for st in pool_states for g in st for s in g)):
-                assert (a is None) == (b is None) and (a is None or np.array_equal(a.view(np.int32), np.asarray(b).view(np.int32))), (M, t)
-        assert [len(r) for r in w.rings['host']] == [len(r) for r in w.rings['handles']] and sum(len(r) for r in w.rings['host']) == M
-        times = {'host': ([], []), 'handles': ([], [])}
+            for form in FORMS[1:]:
+                random.seed(100 + t)
+                pool_states, pool_actions = w.step(form, t)
+                assert pool_actions == host_actions, (M, t, form)
+                for a, b in zip((s for st in host_states for g in st for s in g), (s for st in pool_states for g in st for s in g)):
+                    assert (a is None) == (b is None) and (a is None or np.array_equal(a.view(np.int32), np.asarray(b).view(np.int32))), (M, t, form)
+        assert all([len(r) for r in w.rings['host']] == [len(r) for r in w.rings[form]] for form in FORMS) and sum(len(r) for r in w.rings['host']) == M
+        times = {form: ([], []) for form in FORMS}
         for t in range(2, 4 + args.reps):                             # two warm-up steps, then `reps`; the forms alternate
-            for form in ('host', 'handles'):
+            for form in FORMS:
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -147,11 +159,12 @@ def main():
                 if t >= 4:
                     times[form][0].append(dt)
                     times[form][1].append(a.elapsed_time(b))
-        for ring in w.rings['host'] + w.rings['handles']:
-            ring.sync_ring()
-        result['sizes'][str(M)] = {form: {'host_ms': round(float(np.median(h)), 3), 'event_ms': round(float(np.median(e)), 3)}
-                                   for form, (h, e) in times.items()}
-        result['sizes'][str(M)]['resident'] = {form: [r.observations_resident for r in w.rings[form]] for form in ('host', 'handles')}
+        for form in FORMS:
+            for ring in w.rings[form]:
+                ring.sync_ring()
+        result['sizes'][str(M)] = {form: {'host_ms': round(float(np.median(h)), 3), 'host_ms_min': round(min(h), 3), 'host_ms_max': round(max(h), 3),
+                                          'event_ms': round(float(np.median(e)), 3)} for form, (h, e) in times.items()}
+        result['sizes'][str(M)]['resident'] = {form: [r.observations_resident for r in w.rings[form]] for form in FORMS}
         del w
     print(json.dumps(result))
 

@@ -1,26 +1,36 @@
 """Rate of simq.BatchedMapper on the GPU, beside the same work through the hand-written chain of the public functions: one JSON line.
 
-    python tools/mapper_rate.py [--reps 10] [--sizes 1,8,64,256] [--reference-ms-per-state MS]
+    python tools/mapper_rate.py [--reps 10] [--sizes 1,8,64,256] [--reference-ms-per-state MS] [--profile]
 
 Workload: the two recorded episodes (tests/golden/mapper_*.npz, rooms 184 x 232 and 232 x 232), the full channel set with spatial
 intention channels (9 channels), environments of three robots replicated until M = 1, 8, 64, 256 mappers are named; every repetition is
-one environment step: `update` with a fresh frame per mapper, then `get_states`.  Per room and M, for the object and for the chain
-(tests/mapper_chain.py: observation_update, occupancy_maps, a host-side snap, grid_distance_images, intention_maps three times,
-local_state_images):
+one environment step: `update` with a fresh frame per mapper, then `get_states`.  Per room and M, for the object with the robots as
+lists of RobotState (`object`), for the same object with the robots as a simq.RobotArrays (`arrays`: the arrays of a round exist before
+the clock starts, as they do for a caller who steps his environments in arrays; the RobotArrays is made from them inside it) and for
+the chain (tests/mapper_chain.py: observation_update, occupancy_maps, a host-side snap, grid_distance_images, intention_maps three
+times, local_state_images), the three alternating step by step in one process:
   host_ms      a host clock around update + get_states, each of which ends in its status read-back, so the device has finished;
                the inputs of the step (frames as numpy arrays, robot states) are formed inside the clock, as a caller forms them
   update_host_ms   the part of it up to the end of update: forming the inputs, the upload of M depth and id frames, two launches
   library_ms   the sum of the device time between a HIP event before and one after every library call of the step (the calls are
                wrapped for the measurement, the events are read after the step): the descriptor upload each entry makes on the
                launch stream and its kernel, without what the host does between the calls
-both the median over `reps` steps after two warm-up steps.  `launches`: library launches per step.  The states of the first step are
+  states_host_ms   host_ms without update_host_ms: get_states alone
+all medians over `reps` steps after two warm-up steps; host_ms_min / host_ms_max: the spread of host_ms over those steps.  `launches`:
+library launches per step.  `new_tuple`: after the steps, `reps` times one get_states of the array form with the object's plans dropped
+before it (`states_host_ms`: a `mappers` tuple met for the first time) and at once the same call again (`same_tuple_again_ms`), host
+clock, median and minimum / maximum -- the timed steps above all use one tuple, so none of them builds a plan.  --profile prints no timings but, per M, a cProfile breakdown by function of one get_states in the list
+form and of one in the array form (room 184 x 232, after two warm-up calls; cProfile's own overhead inflates Python-heavy code).  The states of the first step are
 checked against the golden (M <= 3) before anything is timed.  The reference Mapper's host time per state is what
 tools/gen_mapper_golden.py prints (it needs the reference checkout); --reference-ms-per-state repeats that figure in the line
 (`reference_host_ms_per_state`, null when not given): it is not measured here.
 """
 import argparse
+import cProfile
+import io
 import json
 import os
+import pstats
 import sys
 import time
 
@@ -70,6 +80,7 @@ def main():
     ap.add_argument('--sizes', default='1,8,64,256')
     ap.add_argument('--reference-ms-per-state', type=float, default=None,
                     help='the host time per state tools/gen_mapper_golden.py printed for the reference Mapper, repeated in the line')
+    ap.add_argument('--profile', action='store_true', help='print a cProfile breakdown of one get_states per form and M instead of the timings')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('mapper_rate.py needs a GPU')
@@ -93,6 +104,8 @@ def main():
                                     **flags, **rest)
             chain = Chain(simq, fx['room_width'], fx['room_length'], [fx['types']] * E, fx['masks'], fx['mask_names'], fx['receptacle_position'])
 
+            arrays = {}                                              # the robots of a round as arrays, made once: what an array caller holds
+
             def step_inputs(t):
                 rnd = rounds[t % len(rounds)]
                 f = [rnd['frames'][m % 3] for m in ms]
@@ -100,6 +113,10 @@ def main():
                 states = [[simq.RobotState(r['position'], r['heading'], r['type'], r['lift_state'], r['idle'], r['target'], r['intention_path'],
                                            r['history_path']) for r in rnd['robots']]] * E
                 return frames, states, [rnd['robots']] * E
+
+            for t in range(len(rounds)):
+                ra = simq.RobotArrays.from_states(bm, step_inputs(t)[1])
+                arrays[t] = (ra.position, ra.heading, ra.lifting, ra.idle, ra.target, ra.intention_path, ra.history_path)
 
             split = []                                               # host clock after the update of the last step (it ends in a read-back)
 
@@ -109,22 +126,42 @@ def main():
                 split.append(time.perf_counter())
                 return bm.get_states(states, mappers=ms)
 
+            def arrays_step(t):
+                frames, _, _ = step_inputs(t)
+                bm.update(*frames, mappers=ms)
+                split.append(time.perf_counter())
+                return bm.get_states(simq.RobotArrays(*arrays[t % len(rounds)]), mappers=ms)
+
             def chain_step(t):
                 frames, _, envs = step_inputs(t)
                 chain.update(*frames, mappers=ms)
                 split.append(time.perf_counter())
                 return chain.get_states(cfg, envs, mappers=ms)['states']
 
-            # the first step against the golden, and the two ways against each other
-            a, b = object_step(0), chain_step(0)
-            assert torch.equal(a, b), (fname, M)
+            # the first step against the golden, and the three ways against each other
+            a, b, c = object_step(0), chain_step(0), arrays_step(0)
+            assert torch.equal(a, b) and torch.equal(a, c), (fname, M)
             want = np.stack([oracle.expected_state(cfg, rounds[0]['images'], m % 3, 3) for m in ms])
             assert np.array_equal(a.cpu().numpy().view(np.int32), want.view(np.int32)), (fname, M)
-            row = {}
-            for name, step in (('object', object_step), ('chain', chain_step)):
-                host, library, update, launches = [], [], [], 0
-                with LibraryClock(_lib.lib) as clock:
-                    for t in range(1, 3 + args.reps):
+            if args.profile:
+                if fname.startswith('mapper_184'):
+                    for form, robots in (('list form', step_inputs(1)[1]), ('array form', simq.RobotArrays(*arrays[1]))):
+                        for _ in range(2):
+                            bm.get_states(robots, mappers=ms)
+                        prof = cProfile.Profile()
+                        prof.enable()
+                        bm.get_states(robots, mappers=ms)
+                        prof.disable()
+                        text = io.StringIO()
+                        pstats.Stats(prof, stream=text).sort_stats('tottime').print_stats(14)
+                        print('---- M = %d, %s: one get_states by function (tottime)' % (M, form))
+                        print('\n'.join(line for line in text.getvalue().splitlines() if line.strip())[:6000])
+                continue
+            forms = (('object', object_step), ('arrays', arrays_step), ('chain', chain_step))
+            taken = {name: ([], [], [], []) for name, _ in forms}
+            with LibraryClock(_lib.lib) as clock:
+                for t in range(1, 3 + args.reps):
+                    for name, step in forms:                         # the forms alternate step by step
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
                         step(t)
@@ -132,15 +169,36 @@ def main():
                         dt = 1e3 * (time.perf_counter() - t0)
                         ms_lib, launches = clock.take()
                         if t >= 3:
+                            host, library, update, counts = taken[name]
                             host.append(dt)
                             library.append(ms_lib)
                             update.append(1e3 * (split[-1] - t0))
-                row[name] = {'host_ms': round(float(np.median(host)), 3), 'update_host_ms': round(float(np.median(update)), 3),
-                             'library_ms': round(float(np.median(library)), 3), 'launches': launches,
+                            counts.append(launches)
+            # the array form with a `mappers` tuple the object has no plan for, beside the same call again: what a caller pays whose
+            # tuple changes from step to step (the object keeps the plans of eight tuples; here they are dropped before the call)
+            robots, miss, hit = simq.RobotArrays(*arrays[0]), [], []
+            for _ in range(args.reps):
+                for times in (miss, hit):
+                    if times is miss:
+                        bm._plans.clear()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    bm.get_states(robots, mappers=ms)
+                    torch.cuda.synchronize()
+                    times.append(1e3 * (time.perf_counter() - t0))
+            row = {'new_tuple': {'states_host_ms': round(float(np.median(miss)), 3), 'states_host_ms_min': round(min(miss), 3),
+                                 'states_host_ms_max': round(max(miss), 3), 'same_tuple_again_ms': round(float(np.median(hit)), 3),
+                                 'same_tuple_again_ms_min': round(min(hit), 3), 'same_tuple_again_ms_max': round(max(hit), 3)}}
+            for name, (host, library, update, counts) in taken.items():
+                row[name] = {'host_ms': round(float(np.median(host)), 3), 'host_ms_min': round(min(host), 3), 'host_ms_max': round(max(host), 3),
+                             'update_host_ms': round(float(np.median(update)), 3),
+                             'states_host_ms': round(float(np.median(np.asarray(host) - np.asarray(update))), 3),
+                             'library_ms': round(float(np.median(library)), 3), 'launches': counts[-1],
                              'host_ms_per_state': round(float(np.median(host)) / M, 4)}
             rows[str(M)] = row
         result['rooms'][fname[len('mapper_'):-4]] = rows
-    print(json.dumps(result))
+    if not args.profile:
+        print(json.dumps(result))
 
 
 if __name__ == '__main__':
