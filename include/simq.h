@@ -473,6 +473,26 @@ int simq_conv2d_fwd_winograd(const float* d_x, const float* d_w_ohwi, const floa
 int simq_conv2d_fwd_winograd4(const float* d_x, const float* d_w_ohwi, const float* d_bias, float* d_y,
                               int batch, int hin, int win, int cin, int cout,
                               double* d_stats /* NULL or [2*cout] zeroed */, float* d_scratch, void* stream, const simq_launch_opts* opts);
+/* The OUTPUT TRANSFORM of that form on its own (per-kernel tests, tools/): y = A^T m A per 4x4 output tile from the transform-domain
+ * products d_mt [36][T4][channels], T4 = batch*(h/4)*(w/4), followed by the whole convolution epilogue, every part optional (NULL / 0):
+ *   v = y + bias[n] ; (stats[n] += v, stats[channels+n] += v*v) ; v = v*scale[n] + shift[n] ; v += addend[pixel][n] ; relu ; store ;
+ *   with bnr_red1 (a dgrad's fused BatchNorm-backward sums):  dz = mask > 0 ? v : 0, the mask being bnr_mask (fp32), else bnr_mask16
+ *   (bf16 bits), else recomputed as bnr_y1*bnr_mscale[n] + bnr_mshift[n] > 0 ;  bnr_red1[n] += dz,
+ *   bnr_red1[channels+n] += dz*(bnr_y1 - bnr_mean1[n])*bnr_invstd1[n] ; and the same against (bnr_y2, bnr_mean2, bnr_invstd2) into bnr_red2.
+ * Activation-shaped tensors are fp32 [batch][h][w][channels]; the fp64 sums [2*channels] are added into (zero them first).
+ * form 1: the two-phase kernel the plans launch (a tile's epilogue loads issued back to back, then its arithmetic, then its stores);
+ * form 0: the one-pixel-at-a-time kernel it replaced, kept as the oracle -- same operations in the same order, bit-identical y and,
+ * on data whose fp64 sums are exact, bit-identical sums.  h, w multiples of 4; channels / 4 divides 256. */
+typedef struct simq_wino4f_epilogue {
+    int struct_bytes;               /* sizeof(simq_wino4f_epilogue): a struct of another version is refused */
+    int relu;
+    const float* bias; double* stats; const float* scale; const float* shift; const float* addend;
+    const float* bnr_mask; const uint16_t* bnr_mask16; const float* bnr_mscale; const float* bnr_mshift;
+    const float* bnr_y1; const float* bnr_mean1; const float* bnr_invstd1; double* bnr_red1;
+    const float* bnr_y2; const float* bnr_mean2; const float* bnr_invstd2; double* bnr_red2;
+} simq_wino4f_epilogue;
+int simq_wino4f_output(const float* d_mt, float* d_y, int batch, int h, int w, int channels, const simq_wino4f_epilogue* epilogue,
+                       int form, void* stream);
 /* The plan's elementwise BatchNorm pass, on its own (per-kernel parity tests): train-mode nn.BatchNorm2d + residual + ReLU
  * (resnet.py:35-36,42-45) with the batch statistics GIVEN as [sum | sum of squares] over `rows` (what the producing convolution's
  * epilogue leaves):  out = [relu]( (y - mean) * invstd * gamma + beta  [+ res] ).

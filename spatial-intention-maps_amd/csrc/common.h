@@ -155,6 +155,9 @@ int launch_conv_winograd(const float* x, const float* U, float* y, const ConvGeo
 bool winograd_f4_forward(const ConvGeom& g, int min_tiles);
 int launch_conv_winograd4(const float* x, const float* U4, float* y, const ConvGeom& g, const ConvEpilogue& e, float* scratch,
                           hipStream_t stream, const InBn& in = InBn());
+// ... and its output transform alone, Mt [36][B*(H/4)*(W/4)][C] -> y + epilogue.  form 1: the two-phase kernel the plans launch; 0: the
+// one-pixel-at-a-time kernel it replaced (the oracle of tests/test_gpu_wino4f_output.py)
+int launch_wino4f_output(const float* Mt, float* y, const ConvEpilogue& e, int B, int H, int W, int C, int form, hipStream_t stream);
 // det_slab: NULL, or kWgradDetSlabFloats floats of scratch -- the pixel-split blocks then leave their partial tiles there and a second launch
 // adds them in split order (deterministic plans) instead of fp32 atomics into the zeroed dw
 constexpr int64_t kWgradDetSlabFloats = 16 << 20;

@@ -435,6 +435,193 @@ __global__ void __launch_bounds__(256) wino4f_output_kernel(const float* __restr
     }
 }
 
+// The two-phase form of the kernel above (round 8): what the plans launch; the kernel above stays as the oracle of the per-kernel test
+// (simq_wino4f_output, form 0).  Same launch geometry, same thread -> (tile, 4 channels) ownership, the same operations in the same
+// order on every value and on every accumulator -- only the order of the MEMORY operations differs.  Loads and stores share one counter
+// on this part, so the pixel-by-pixel "epilogue loads, compute, store" order of the kernel above makes every pixel's wait for its loads
+// a wait for the previous pixel's store as well.  Here a tile is
+//   phase A   the 36 loads, A^T m A, + bias: sixteen results parked in registers (a[][] is dead by then, so they cost nothing on top
+//             of the transform's own peak)
+//   phase B   per group of ROWS tile rows: every epilogue load of the group back to back, then the arithmetic in (i, j) order, then
+//             the stores, issued behind the NEXT group's loads -- no use of a load waits for a store.
+// Which tensors the epilogue reads is a template parameter: an array element that is "loaded or not" by a run-time flag would put a
+// branch and a full wait around every load.  A pixel's address is a uniform base (tensor + pixel (i, j) of the tile) plus ONE 32-bit
+// byte offset per thread and tile, shared by every tensor: no 64-bit address registers per pixel and tensor (the launcher sends tensors
+// of 4 GiB and more to the kernel above).
+//   ADD   residual / upstream-gradient addend          BNR   0 no fused BatchNorm-backward sums, 1 fp32 mask tensor, 2 bf16 mask plane,
+//   Y2    second BatchNorm (bnr_y2)                           3 mask recomputed from bnr_y1
+//   STATS train-mode batch statistics.  Only the instantiations that leave sums (STATS or BNR) hold the 16 KB of `red`
+//   ABL   timing ablations, ablation build only: 1 fold but no atomics, 2 no sums at all, 4 no epilogue loads
+template <bool ADD, int BNR, bool Y2>
+constexpr int w4f_out_rows() {
+    // registers of one pixel's epilogue loads: 4 per fp32 tensor, 2 for the bf16 mask; the parked results take 64, the per-channel
+    // constants and sums up to 52: as many tile rows per group as keep the group's loads within 96 registers (two waves per SIMD = 256)
+    const int per_pixel = (ADD ? 4 : 0) + (BNR ? 4 : 0) + (BNR == 1 ? 4 : BNR == 2 ? 2 : 0) + (Y2 ? 4 : 0);
+    return per_pixel * 16 <= 96 ? 4 : per_pixel * 8 <= 96 ? 2 : 1;
+}
+
+template <bool ADD, int BNR, bool Y2, bool STATS, int ABL>
+__global__ void __launch_bounds__(256, 2) wino4f_output2_kernel(const float* __restrict__ Mt, const EpiArgs p, int B, int H, int W, int C, int T, int lanes) {
+    static_assert(BNR >= 0 && BNR <= 3 && (BNR != 0 || !Y2) && !(STATS && BNR != 0), "wino4f_output2_kernel: form");
+    constexpr bool LDS = STATS || BNR != 0;
+    constexpr int ROWS = w4f_out_rows<ADD, BNR, Y2>();
+    constexpr bool LOADS = !(ABL & 4);
+    const int tpb = 256 / lanes;
+    const int cl = threadIdx.x % lanes, tl = threadIdx.x / lanes;
+    const int th = H >> 2, tw = W >> 2;
+    const size_t gstride = (size_t)T * C;
+    const int n = (blockIdx.y * lanes + cl) * 4;
+    constexpr bool bnr = BNR != 0, bnr2 = Y2;
+    const bool relu = p.relu != 0;
+    floatx4 bias = {0.f, 0.f, 0.f, 0.f}, sc = {1.f, 1.f, 1.f, 1.f}, sh = bias, mu1 = bias, is1 = bias, mu2 = bias, is2 = bias, msc = bias, msh = bias;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (p.bias) bias[c] = p.bias[n + c];
+        if (p.scale) { sc[c] = p.scale[n + c]; sh[c] = p.shift[n + c]; }
+        if (bnr) { mu1[c] = p.bnr_mean1[n + c]; is1[c] = p.bnr_invstd1[n + c]; }
+        if (BNR == 3 && p.bnr_mscale) { msc[c] = p.bnr_mscale[n + c]; msh[c] = p.bnr_mshift[n + c]; }
+        if (bnr2) { mu2[c] = p.bnr_mean2[n + c]; is2[c] = p.bnr_invstd2[n + c]; }
+    }
+    floatx4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
+    for (int t = blockIdx.x * tpb + tl; t < T; t += gridDim.x * tpb) {
+        const int b = t / (th * tw), r = t - b * (th * tw);
+        const int ty = r / tw, tx = r - ty * tw;
+        const float* src = Mt + (size_t)t * C + n;
+        floatx4 v[4][4];
+        {                                            // phase A
+            floatx4 mt[6][6];                        // all 36 planes in flight at once: the launch is latency-bound (two waves per SIMD)
+#pragma unroll
+            for (int g = 0; g < 36; ++g) mt[g % 6][g / 6] = *reinterpret_cast<const floatx4*>(src + g * gstride);
+            __builtin_amdgcn_sched_barrier(0);
+            floatx4 a[4][6];                         // A^T m, column by column of m
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                floatx4 m[6], y[4];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) m[i] = mt[j][i];
+                w4f_at(m, y);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a[i][j] = y[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                floatx4 y[4];
+                w4f_at(a[i], y);                     // (A^T m) A, row by row
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[i][j] = y[j] + bias;
+            }
+        }
+        // pixel (i, j) of the tile: (uniform) tensor + ((i * W + j) * C) elements, + o00 bytes of fp32 elements
+        const unsigned o00 = (unsigned)((((size_t)(b * H + 4 * ty) * W + 4 * tx) * C + n) * sizeof(float));
+        auto f4 = [&](const float* base, int i, int j) {
+            return reinterpret_cast<const floatx4*>(reinterpret_cast<const char*>(base + ((size_t)i * W + j) * C) + o00);
+        };
+        floatx4 ad[4][4], y1[4][4], mk[4][4], y2[4][4];      // (a group's rows are live from its loads to its arithmetic only)
+        ushort4 mk16[4][4];
+        auto load_rows = [&](int i0) {               // every epilogue load of rows i0 .. i0 + ROWS - 1, back to back
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = i0; i < i0 + ROWS; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (LOADS) {
+                        if constexpr (ADD) ad[i][j] = *f4(p.addend, i, j);
+                        if constexpr (bnr) y1[i][j] = *f4(p.bnr_y1, i, j);
+                        if constexpr (BNR == 1) mk[i][j] = *f4(p.bnr_mask, i, j);
+                        if constexpr (BNR == 2)
+                            mk16[i][j] = *reinterpret_cast<const ushort4*>(reinterpret_cast<const char*>(p.bnr_mask16 + ((size_t)i * W + j) * C) + (o00 >> 1));
+                        if constexpr (bnr2) y2[i][j] = *f4(p.bnr_y2, i, j);
+                    } else {                         // (timing ablation: stand-ins that keep the arithmetic live)
+                        ad[i][j] = y1[i][j] = mk[i][j] = y2[i][j] = v[i][j];
+                        mk16[i][j] = make_ushort4(1, 1, 1, 1);
+                    }
+                }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // phase B.  (The first group's loads are not hoisted into phase A: the transform's 36 loads are its register peak.)  A group's
+        // stores are issued BEHIND the next group's loads: the counter retires in issue order, so the wait for those loads does not
+        // include the stores, and no use of a load waits for a store.
+        load_rows(0);
+#pragma unroll
+        for (int i0 = 0; i0 < 4; i0 += ROWS) {
+#pragma unroll
+            for (int i = i0; i < i0 + ROWS; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    floatx4 v_ = v[i][j];
+                    if constexpr (STATS && !(ABL & 2)) { s0 += v_; s1 += v_ * v_; }
+                    v_ = v_ * sc + sh;
+                    if constexpr (ADD) v_ += ad[i][j];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v_[c] = relu ? fmaxf(v_[c], 0.f) : v_[c];      // (a select, not a branch per pixel)
+                    v[i][j] = v_;
+                    if constexpr (bnr) {
+                        floatx4 dz;
+                        if constexpr (BNR == 1) {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) dz[c] = mk[i][j][c] > 0.f ? v_[c] : 0.f;
+                        } else if constexpr (BNR == 2) {
+                            const ushort4 m16 = mk16[i][j];
+                            dz[0] = (short)m16.x > 0 ? v_[0] : 0.f; dz[1] = (short)m16.y > 0 ? v_[1] : 0.f;
+                            dz[2] = (short)m16.z > 0 ? v_[2] : 0.f; dz[3] = (short)m16.w > 0 ? v_[3] : 0.f;
+                        } else {                     // the activation was never stored: its sign from the pre-BN output (common.h InBn)
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) dz[c] = __builtin_fmaf(y1[i][j][c], msc[c], msh[c]) > 0.f ? v_[c] : 0.f;
+                        }
+                        if constexpr (!(ABL & 2)) {
+                            s0 += dz;
+                            s1 += dz * ((y1[i][j] - mu1) * is1);
+                            if constexpr (bnr2) {
+                                s2 += dz;
+                                s3 += dz * ((y2[i][j] - mu2) * is2);
+                            }
+                        } else {
+                            asm volatile("" :: "v"(dz[0]), "v"(dz[1]), "v"(dz[2]), "v"(dz[3]));
+                        }
+                    }
+                }
+            if (i0 + ROWS < 4) load_rows(i0 + ROWS);
+            else __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = i0; i < i0 + ROWS; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *const_cast<floatx4*>(f4(p.y, i, j)) = v[i][j];
+        }
+    }
+    if constexpr (LDS && !(ABL & 2)) {
+        __shared__ float red[4][256][4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            red[0][threadIdx.x][c] = s0[c]; red[1][threadIdx.x][c] = s1[c];
+            red[2][threadIdx.x][c] = s2[c]; red[3][threadIdx.x][c] = s3[c];
+        }
+        __syncthreads();
+        // The fp64 stage does not depend on the order in which the blocks arrive ONLY because it adds fp32 partials of a few dozen values
+        // each: a sum of a few thousand such partials is exact in fp64 unless their magnitudes span more than ~2^29, so every order of the
+        // atomics below gives the same bits in practice (and exactly the same on data of bounded range, which the per-kernel test uses).
+        for (int lc = threadIdx.x; lc < 4 * lanes; lc += 256) {      // channel lc of the slice lives in lane lc / 4, component lc % 4 of every tile lane group
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            for (int k = 0; k < tpb; ++k) {
+                const int src = k * lanes + (lc >> 2);
+                a0 += (double)red[0][src][lc & 3]; a1 += (double)red[1][src][lc & 3];
+                a2 += (double)red[2][src][lc & 3]; a3 += (double)red[3][src][lc & 3];
+            }
+            if constexpr (ABL & 1) {
+                asm volatile("" :: "v"(a0), "v"(a1), "v"(a2), "v"(a3));
+            } else {
+                const int ch = blockIdx.y * lanes * 4 + lc;
+                double* dst = STATS ? p.stats : p.bnr_red1;
+                unsafeAtomicAdd(dst + ch, a0);
+                unsafeAtomicAdd(dst + C + ch, a1);
+                if (bnr2) {
+                    unsafeAtomicAdd(p.bnr_red2 + ch, a2);
+                    unsafeAtomicAdd(p.bnr_red2 + C + ch, a3);
+                }
+            }
+        }
+    }
+}
+
 // ---- weight gradient in the transform domain --------------------------------------------------------------------------
 //   Y = A^T Mt A  =>  dMt = A dY A^T ;   Mt[g] = V[g] U[g]^T  =>  dU[g] = dMt[g]^T V[g] ;   U = G w G^T  =>  dw = G^T dU G
 // dMt[g][t][c] = (A dY A^T)[g / 4][g % 4],  A = [[1,0],[1,1],[1,-1],[0,-1]]
@@ -799,22 +986,67 @@ int launch_conv_winograd4(const float* x, const float* U4, float* y, const ConvG
     else hipLaunchKernelGGL(wino4f_input_kernel<false>, dim3(bin), dim3(256), 0, stream, x, V, g.B, g.Hin, g.Win, g.Cin, T4, in);
     SIMQ_CHECK_LAUNCH();
     if (int rc = launch_gemm_batched(V, U4, Mt, T4, g.Cout, g.Cin, 36, stream, g.tune)) return rc;
+    return launch_wino4f_output(Mt, y, e, g.B, g.Hin, g.Win, g.Cout, 1, stream);
+}
+
+// one instantiation of the two-phase kernel per set of tensors the epilogue reads (every set the one-pixel-at-a-time kernel accepts)
+template <int ABL>
+static void launch_wino4f_output2(dim3 grid, hipStream_t stream, const float* Mt, const EpiArgs& ea, int B, int H, int W, int C, int T4, int lanes) {
+    const bool add = ea.addend != nullptr, y2 = ea.bnr_red1 && ea.bnr_red2, stats = ea.stats != nullptr;
+    const int bnr = !ea.bnr_red1 ? 0 : ea.bnr_mask ? 1 : ea.bnr_mask16 ? 2 : 3;
+#define SIMQ_W4F_OUT2(ADD, BNR, Y2, STATS)                                                                                                      \
+    if (add == ADD && bnr == BNR && y2 == Y2 && stats == STATS) {                                                                                 \
+        hipLaunchKernelGGL((wino4f_output2_kernel<ADD, BNR, Y2, STATS, ABL>), grid, dim3(256), 0, stream, Mt, ea, B, H, W, C, T4, lanes);       \
+        return;                                                                                                                                 \
+    }
+#define SIMQ_W4F_OUT2_ADD(ADD)                                                                                                                  \
+    SIMQ_W4F_OUT2(ADD, 0, false, false); SIMQ_W4F_OUT2(ADD, 0, false, true);                                                                    \
+    SIMQ_W4F_OUT2(ADD, 1, false, false); SIMQ_W4F_OUT2(ADD, 1, true, false); SIMQ_W4F_OUT2(ADD, 2, false, false); SIMQ_W4F_OUT2(ADD, 2, true, false); \
+    SIMQ_W4F_OUT2(ADD, 3, false, false); SIMQ_W4F_OUT2(ADD, 3, true, false)
+    SIMQ_W4F_OUT2_ADD(false);
+    SIMQ_W4F_OUT2_ADD(true);
+#undef SIMQ_W4F_OUT2_ADD
+#undef SIMQ_W4F_OUT2
+}
+
+// The output transform of launch_conv_winograd4 on its own (Mt [36][T4][C] -> y [B][H][W][C] + epilogue).  form 1: the two-phase kernel
+// (what the plans launch); form 0: the one-pixel-at-a-time kernel of rounds 2-7, kept as the oracle of the per-kernel test.  In the
+// ablation build form 1 + 16 * a selects timing ablation a of the two-phase kernel (its ABL parameter).
+int launch_wino4f_output(const float* Mt, float* y, const ConvEpilogue& e, int B, int H, int W, int C, int form, hipStream_t stream) {
+    SIMQ_REQUIRE(Mt && y && B >= 1 && H >= 4 && W >= 4 && H % 4 == 0 && W % 4 == 0 && C >= 4 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0,
+                 "wino4f_output: geometry not supported (map %% 4, C / 4 divides 256)");
+    SIMQ_REQUIRE(!e.y_bf16 && !(e.addend && e.addend_bf16) && !(e.bnr_red1 && e.bnr_y_bf16), "wino4f_output: fp32 tensors only");
+    SIMQ_REQUIRE(!e.bnr_red1 || (e.bnr_y1 && e.bnr_mean1 && e.bnr_invstd1), "wino4f_output: bnr_red1 without bnr_y1 / bnr_mean1 / bnr_invstd1");
+    SIMQ_REQUIRE(!(e.bnr_red1 && e.bnr_red2) || (e.bnr_y2 && e.bnr_mean2 && e.bnr_invstd2), "wino4f_output: bnr_red2 without bnr_y2 / bnr_mean2 / bnr_invstd2");
+    SIMQ_REQUIRE(!e.scale == !e.shift && !e.bnr_mscale == !e.bnr_mshift, "wino4f_output: scale / shift come in pairs");
+    const int T4 = B * (H / 4) * (W / 4);
     // Round 6.  A launch that leaves BatchNorm sums (train-mode statistics; the dgrads' fused backward sums) ends with 2-4 fp64 atomics per
     // channel and block, and its blocks all finish together: 576 blocks x 1024 sums onto 64 cache lines serialise (~6 ns each) into tens of
     // microseconds -- the 512-channel launches took 32-95 us where the bare transform takes 19.  So such a launch cuts the channels into slices
     // of `lanes` quads (blockIdx.y) and gives a block MORE TILES of fewer channels: the same blocks and bytes, 1 / (C / 4 / lanes) of the
     // atomics per block (256-byte instead of 2-KB runs per tile and plane: still whole DRAM bursts).
     static const int slice_quads = SIMQ_TUNE_INT("SIMQ_W4F_OUT_SLICE_QUADS", 16);      // (ablation build: 0 = whole channel range per block, rounds 2-5)
-    int lanes_out = g.Cout / 4;
+    int lanes_out = C / 4;
     if ((e.stats || e.bnr_red1) && slice_quads > 0 && lanes_out > slice_quads && lanes_out % slice_quads == 0) lanes_out = slice_quads;
-    const int tpb_o = 256 / lanes_out, slices = (g.Cout / 4) / lanes_out;
+    const int tpb_o = 256 / lanes_out, slices = (C / 4) / lanes_out;
     int bout = (T4 + tpb_o - 1) / tpb_o;
     // F(4x4,3x3) has a quarter of the tiles: at 512 channels a block is two tiles and B = 32 gives 576 blocks -- capped at 512, sixty-four
     // blocks did two grid-stride trips while the rest did one (the launch took the time of two).  Up to 1024 blocks, equal trips each.
     bout = balanced_grid(bout, ((e.stats || e.bnr_red1) ? 1024 : 4096) / slices);
     const EpiArgs ea = make_epi(y, e);
     note_launch("winograd_f4");
-    hipLaunchKernelGGL(wino4f_output_kernel, dim3(bout, slices), dim3(256), 0, stream, Mt, ea, g.B, g.Hin, g.Win, g.Cout, T4, lanes_out);
+    const dim3 grid(bout, slices);
+    // the two-phase kernel addresses a tensor with 32-bit byte offsets, and keeps batch statistics and BatchNorm-backward sums (which no
+    // convolution leaves at once: they would share s0 / s1) in separate instantiations: anything else goes to the general kernel
+    if (form == 1 && ((double)B * H * W * C * sizeof(float) >= 4294967296.0 || (e.stats && e.bnr_red1))) form = 0;
+    if (form == 0) hipLaunchKernelGGL(wino4f_output_kernel, grid, dim3(256), 0, stream, Mt, ea, B, H, W, C, T4, lanes_out);
+    else if (form == 1) launch_wino4f_output2<0>(grid, stream, Mt, ea, B, H, W, C, T4, lanes_out);
+#ifdef SIMQ_ABLATIONS
+    else if (form == 1 + 16 * 1) launch_wino4f_output2<1>(grid, stream, Mt, ea, B, H, W, C, T4, lanes_out);
+    else if (form == 1 + 16 * 2) launch_wino4f_output2<2>(grid, stream, Mt, ea, B, H, W, C, T4, lanes_out);
+    else if (form == 1 + 16 * 4) launch_wino4f_output2<4>(grid, stream, Mt, ea, B, H, W, C, T4, lanes_out);
+#endif
+    else SIMQ_REQUIRE(false, "wino4f_output: form %d (0: one pixel at a time, 1: two-phase)", form);
     SIMQ_CHECK_LAUNCH();
     return 0;
 }

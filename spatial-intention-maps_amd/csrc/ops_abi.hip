@@ -229,6 +229,19 @@ int simq_conv2d_fwd_winograd4(const float* d_x, const float* d_w, const float* d
     return launch_conv_winograd4(d_x, d_scratch, d_y, g, e, d_scratch + (size_t)36 * cout * cin, st);
 }
 
+int simq_wino4f_output(const float* d_mt, float* d_y, int batch, int h, int w, int channels, const simq_wino4f_epilogue* ep, int form, void* stream) {
+    SIMQ_REQUIRE(d_mt && d_y && ep, "wino4f_output: NULL argument");
+    SIMQ_REQUIRE(ep->struct_bytes == (int)sizeof(simq_wino4f_epilogue), "simq_wino4f_epilogue.struct_bytes = %d, this library's struct has %d",
+                 ep->struct_bytes, (int)sizeof(simq_wino4f_epilogue));
+    SIMQ_REQUIRE(batch >= 1 && h >= 4 && w >= 4 && channels >= 4 && (double)batch * h * w * channels < 2147483648.0, "wino4f_output: bad shape");
+    ConvEpilogue e;
+    e.bias = ep->bias; e.stats = ep->stats; e.scale = ep->scale; e.shift = ep->shift; e.addend = ep->addend; e.relu = ep->relu;
+    e.bnr_mask = ep->bnr_mask; e.bnr_mask16 = ep->bnr_mask16; e.bnr_mscale = ep->bnr_mscale; e.bnr_mshift = ep->bnr_mshift;
+    e.bnr_y1 = ep->bnr_y1; e.bnr_mean1 = ep->bnr_mean1; e.bnr_invstd1 = ep->bnr_invstd1; e.bnr_red1 = ep->bnr_red1;
+    e.bnr_y2 = ep->bnr_y2; e.bnr_mean2 = ep->bnr_mean2; e.bnr_invstd2 = ep->bnr_invstd2; e.bnr_red2 = ep->bnr_red2;
+    return launch_wino4f_output(d_mt, d_y, e, batch, h, w, channels, form, static_cast<hipStream_t>(stream));
+}
+
 int simq_conv2d_wgrad_winograd(const float* d_x, const float* d_dy, float* d_dw, int batch, int hin, int win, int cin, int cout,
                                float* d_scratch, void* stream, const simq_launch_opts* opts) {
     SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_winograd: bad argument");

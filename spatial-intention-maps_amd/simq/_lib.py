@@ -56,6 +56,13 @@ class LaunchOpts(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ('struct_bytes', 'force_bm', 'force_bn', 'tail_split', 'plane_xcd', 'wgrad_xcd_group', 'wgrad_ksplit', 'gemm_split')]
 
 
+class Wino4fEpilogue(ctypes.Structure):
+    """simq_wino4f_epilogue of include/simq.h (the epilogue of the standalone F(4x4,3x3) output transform)."""
+    _fields_ = [('struct_bytes', c_int), ('relu', c_int)] + [(n, c_void_p) for n in (
+        'bias', 'stats', 'scale', 'shift', 'addend', 'bnr_mask', 'bnr_mask16', 'bnr_mscale', 'bnr_mshift',
+        'bnr_y1', 'bnr_mean1', 'bnr_invstd1', 'bnr_red1', 'bnr_y2', 'bnr_mean2', 'bnr_invstd2', 'bnr_red2')]
+
+
 class TrainArgs(ctypes.Structure):
     """simq_train_args of include/simq.h (the whole TD step in one library call)."""
     _fields_ = [('plan', c_void_p),
@@ -138,6 +145,7 @@ _SIGS = {
     'simq_conv2d_wgrad_winograd': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p] + [c_void_p]),
     'simq_conv2d_fwd_winograd': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p] + [c_void_p]),
     'simq_conv2d_fwd_winograd4': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p] + [c_void_p]),
+    'simq_wino4f_output': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     'simq_bn_relu_apply': (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'simq_bn_relu_backward': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 8 + [c_int64, c_int, c_int, c_void_p]),
     'simq_conv2d_fwd_bnrelu_in': (c_int, [c_void_p] * 6 + [c_int] * 10 + [c_void_p, c_void_p] + [c_void_p]),
@@ -209,6 +217,20 @@ def launch_opts(tile=None, **fields):
             raise SimqError('unknown launch option %r (fields of simq_launch_opts: %s)' % (k, ', '.join(n for n, _ in LaunchOpts._fields_[1:])))
         setattr(o, k, int(v))
     return o
+
+def wino4f_output(mt, y, form=1, relu=False, **tensors):
+    """simq_wino4f_output on torch tensors: mt [36][T4][C] -> y [B][H][W][C] (written in place); tensors: the pointer fields of
+    simq_wino4f_epilogue by name (bias=..., stats=..., bnr_y1=..., ...); form 1 = the kernel the plans launch, 0 = the oracle."""
+    e = Wino4fEpilogue()
+    e.struct_bytes, e.relu = ctypes.sizeof(Wino4fEpilogue), int(bool(relu))
+    for k, t in tensors.items():
+        if k in ('struct_bytes', 'relu') or not hasattr(e, k):
+            raise SimqError('unknown field %r of simq_wino4f_epilogue' % k)
+        setattr(e, k, None if t is None else t.data_ptr())
+    B, H, W, C = y.shape
+    check(_c.simq_wino4f_output(ptr(mt), ptr(y), B, H, W, C, ctypes.byref(e), int(form), stream_ptr(y.device)), 'simq_wino4f_output')
+    return y
+
 
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_c, _name)      # AttributeError here == header / library mismatch
