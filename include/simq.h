@@ -692,6 +692,58 @@ int simq_grid_paths(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* 
                     int64_t path_pairs, int32_t* d_lengths, int32_t* d_endpoints, int32_t* d_parents, int64_t parents_ints, float* d_dist,
                     int64_t dist_floats, int32_t* d_status, void* stream);
 
+/* ---- waypoints from dense paths: exact simplification and pruning (shortest_paths.pyx:139-154, the back half of
+ * GridGraph.shortest_path: skimage.measure.approximate_polygon, then the waypoints a clear line makes unnecessary) ---------------
+ * One problem = one dense path c[0 .. n) of integer pixels (r, c), n >= 1, target first, where simq_grid_paths left it (problem p
+ * reads pair path_offset of d_paths, d_lengths[p] and d_path_status[p]), its uint8 grid in d_grids and an integer tolerance t in
+ * [1, 255] (the reference uses 1).  One wavefront per problem, every problem of a call in one launch on `stream`, so the search
+ * and this stage queue back to back with no read-back between them.
+ *
+ * The rule.  approximate_polygon evaluates its comparisons in float64 through arctan2 / sin / cos, and on integer pixels those
+ * comparisons meet exact ties whose outcome is rounding noise.  Every one of them is a comparison of rationals, decided here in
+ * int64: the result equals the float algorithm wherever that does not depend on rounding, and is defined where it does.
+ *   simplify  1. keep[0] = keep[n - 1] = true.
+ *             2. A segment (s, e) with e > s + 1 is evaluated once, starting with (0, n - 1).
+ *             3. With dr = r_e - r_s, dc = c_e - c_s, L = dr^2 + dc^2, every interior point k gets a squared distance as a fraction:
+ *                a0 = (r_k - r_s) dr + (c_k - c_s) dc, a1 = -(r_k - r_e) dr - (c_k - c_e) dc; if a0 > 0 and a1 > 0 it is
+ *                ((r_k - r_s) dc - (c_k - c_s) dr)^2 / L (perpendicular), otherwise min(|c_k - c_s|^2, |c_k - c_e|^2) / 1 (the
+ *                nearer end point).
+ *             4. m is the maximum, compared by cross-multiplication; the segment is split iff m > t^2 (strict).
+ *             5. It is split at the first k that attains m: keep[k] = true, and (s, k) and (k, e) are evaluated in turn.
+ *             6. A segment's verdict depends on its end points only, so the kept set does not depend on the order of evaluation (the
+ *                kernel keeps no stack: it resolves the first unresolved gap between consecutive kept points).
+ *   prune     sparse = the kept points in path order; path = [sparse[0]]; for k = 1 .. len(sparse) - 2, sparse[k] is kept iff the
+ *             skimage.draw.line (the rule of simq_intention_maps below) from path[-1] to sparse[k + 1] crosses a cell of the grid
+ *             that is not 1 (the reference's uint8 (1 - grid[rr, cc]).sum() > 0); sparse[-1] is appended when len(sparse) > 1.
+ *   output    reversed: int32 (i, j) pairs, source first, at pair way_offset of d_ways, at most way_capacity pairs; d_counts[p].
+ * Magnitudes.  Every coordinate must lie inside its grid, whose sides are at most 2^15, so |cross| < 2^31, cross^2 < 2^62,
+ * L < 2^31, e^2 L < 2^62 and t^2 L < 2^47: all in int64.  Coordinates are data on the device, so it is the kernel that refuses
+ * them (status 2); the host refuses rows or cols above 2^15.  A path of more than SIMQ_GRID_WAYPOINTS_MAX_PATH points is status 2
+ * as well (the kept flags are a bit mask in LDS; simq_grid_paths writes at most SIMQ_GRID_PATH_MAX_BOX_CELLS + 1).
+ * Work is bounded by n: at most n - 2 splits and n - 1 verdicts, at most n - 2 lines of at most max(rows, cols) cells.
+ * `problems`: host array of n descriptors, validated here before anything is copied or launched (rows, cols in [1, 2^15], rows *
+ * cols < SIMQ_GRID_MAX_CELLS; tolerance in [1, 255]; way_capacity >= 1; the grid, the first pair of the path and the waypoint range
+ * inside the declared extent of their buffers; no two problems' waypoint ranges overlapping; d_ways, d_counts, d_status and
+ * d_problems disjoint from each other and from the inputs; 8-byte alignment of d_paths, d_ways and d_problems, 4 of the other int32
+ * buffers) and copied to d_problems (n descriptors) on `stream`.  Several problems may share a grid.
+ * d_status[n] (int32): 0 = ok; 1 = nothing to do: d_path_status[p] was 1 (straight line, d_counts[p] = 0) or 3 (the dense path was
+ * cut short by its capacity, d_counts[p] = -1); 2 = bad descriptor, length, path status or coordinate (the kernel checks again and
+ * writes nothing else); 3 = way_capacity too small: d_counts[p] holds the needed count and nothing is written past the capacity;
+ * 4 = a loop passed its bound (cannot happen). */
+typedef struct simq_grid_waypoint_problem {
+    int64_t grid_offset;        /* byte offset of the problem's [rows][cols] uint8 grid in d_grids */
+    int64_t path_offset;        /* pair offset of its dense path in d_paths */
+    int64_t way_offset;         /* pair offset of its waypoints in d_ways */
+    int32_t rows, cols;
+    int32_t way_capacity;       /* pairs */
+    int32_t tolerance;          /* 1 .. 255 */
+} simq_grid_waypoint_problem;
+#define SIMQ_GRID_WAYPOINTS_MAX_PATH 20480
+int simq_grid_waypoints(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* d_paths, int64_t path_pairs,
+                        const int32_t* d_lengths, const int32_t* d_path_status, const simq_grid_waypoint_problem* problems, int n,
+                        simq_grid_waypoint_problem* d_problems, int32_t* d_ways, int64_t way_pairs, int32_t* d_counts,
+                        int32_t* d_status, void* stream);
+
 /* ---- shortest-path distance queries: the point form of the distance images (envs.py:2506-2511 OccupancyMap.shortest_path_distance,
  * reached through Mapper.distance_to_receptacle, envs.py:2189-2194, by every partial reward; shortest_paths.pyx:150-158
  * GridGraph.shortest_path_distance) ------------------------------------------------------------------------------------------------

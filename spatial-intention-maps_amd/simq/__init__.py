@@ -37,6 +37,8 @@ _LAZY = {
     'WaypointGraph': ('.waypoints', 'WaypointGraph'),
     'grid_dense_paths': ('.waypoints', 'grid_dense_paths'),
     'shortest_paths': ('.waypoints', 'shortest_paths'),
+    'grid_waypoints': ('.waypoints', 'grid_waypoints'),
+    'approximate_polygon_exact': ('.waypoints', 'approximate_polygon_exact'),
     'grid_distance_queries': ('.grid_queries', 'grid_distance_queries'),
     'shortest_path_distances': ('.grid_queries', 'shortest_path_distances'),
     'distances_to_receptacle': ('.grid_queries', 'distances_to_receptacle'),

@@ -973,7 +973,8 @@ class BatchedMapper:
 
     # ---- Mapper.shortest_path and Mapper.distance_to_receptacle on the stored tensors -----------------------------------------
     def shortest_paths(self, source_positions, target_positions, mappers=None, simplify=None):
-        """Mapper.shortest_path (envs.py:2186-2187) of the named mappers: simq.shortest_paths on this object's tensors."""
+        """Mapper.shortest_path (envs.py:2186-2187) of the named mappers: simq.shortest_paths on this object's tensors (simplify: None for
+        scikit-image, 'exact' for the integer rule on the device behind the search, or a callable(coords, tolerance))."""
         from .waypoints import shortest_paths
         return shortest_paths(self.configuration_space, self.cspace_thin, self.closest_cspace_indices, source_positions, target_positions,
                               self._mappers(mappers), simplify)

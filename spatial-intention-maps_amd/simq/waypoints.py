@@ -5,8 +5,10 @@ simplifies that dense path with ``skimage.measure.approximate_polygon`` and drop
 ``OccupancyMap.shortest_path`` (envs.py:2477-2504) puts a straight-line test and the snap to the closest free cells in front and the
 conversion to positions behind.  SPFA's parents depend on the order of its queue, so ``simq_grid_paths`` (csrc/grid_waypoints.hip)
 emulates the search itself, one problem per wavefront, and returns parents, distances and dense paths that equal the reference's bit
-for bit.  The simplification stays on the host: it is float64 trigonometry whose ties are libm noise, and the
-waypoints are consumed on the host anyway.
+for bit.  The default simplification stays on the host: it is float64 trigonometry whose ties are libm noise.
+simplify='exact' is the same algorithm with every comparison decided in integers (the rule of include/simq.h): on the host
+approximate_polygon_exact, on the device ``simq_grid_waypoints`` (csrc/grid_simplify.hip), which simplifies and prunes the dense paths
+where the search left them, so that only the waypoints come back.
 """
 import collections
 import ctypes
@@ -31,7 +33,15 @@ class GridPathProblem(ctypes.Structure):
                                               'box_rows', 'box_cols', 'reserved_')]
 
 
+class GridWaypointProblem(ctypes.Structure):
+    """simq_grid_waypoint_problem of include/simq.h."""
+    _fields_ = [(n, ctypes.c_int64) for n in ('grid_offset', 'path_offset', 'way_offset')] + \
+               [(n, ctypes.c_int32) for n in ('rows', 'cols', 'way_capacity', 'tolerance')]
+
+
 DensePaths = collections.namedtuple('DensePaths', 'paths status endpoints parents distances')
+Waypoints = collections.namedtuple('Waypoints', 'waypoints status endpoints')
+WAY_CAPACITY = 64                # pairs per problem in the first read-back; a longer list is fetched with the second
 
 
 def line(r0, c0, r1, c1):
@@ -59,8 +69,59 @@ def _default_simplify():
         from skimage.measure import approximate_polygon      # pylint: disable=import-outside-toplevel
     except ImportError:
         raise SimqError('shortest_path simplifies the dense path with skimage.measure.approximate_polygon and scikit-image is not '
-                        'installed: install it, or pass simplify=callable(coords, tolerance) (dense_path needs neither)') from None
+                        "installed: install it, pass simplify='exact' (the same algorithm decided in integers, no dependency) or pass "
+                        'simplify=callable(coords, tolerance) (dense_path needs neither)') from None
     return approximate_polygon
+
+
+def approximate_polygon_exact(coords, tolerance):
+    """skimage.measure.approximate_polygon on integer pixels with every comparison decided exactly (the rule of include/simq.h): a
+    segment (s, e) is split at the first interior point of largest distance iff that distance exceeds the tolerance, distances being
+    squared and kept as fractions over the segment's squared length.  coords: integer [n, 2], n >= 1; tolerance: an integer in
+    [1, 255].  Returns coords[kept].  Integer arithmetic throughout: int64 while the coordinates span less than 2^15, Python integers
+    beyond.  The kept set is that of simq_grid_waypoints before its pruning."""
+    coords = np.asarray(coords)
+    if coords.ndim != 2 or coords.shape[1] != 2 or coords.shape[0] < 1 or coords.dtype.kind not in 'iu':
+        raise ValueError('approximate_polygon_exact takes an integer [n, 2] array with n >= 1, got %s %s' % (coords.dtype, coords.shape))
+    if isinstance(tolerance, bool) or int(tolerance) != tolerance or not 1 <= int(tolerance) <= 255:
+        raise ValueError('approximate_polygon_exact takes an integer tolerance in [1, 255], got %r' % (tolerance,))
+    n, t2 = coords.shape[0], int(tolerance) ** 2
+    wide = int(coords.max()) - int(coords.min()) >= 1 << 15
+    pts = coords.astype(object) if wide else coords.astype(np.int64)
+    r, c = pts[:, 0], pts[:, 1]
+    keep = np.zeros(n, bool)
+    keep[0] = keep[n - 1] = True
+    stack = [(0, n - 1)]
+    while stack:
+        s, e = stack.pop()
+        if e <= s + 1:
+            continue
+        dr, dc = r[e] - r[s], c[e] - c[s]
+        L = dr * dr + dc * dc
+        r0, c0, r1, c1 = r[s + 1:e] - r[s], c[s + 1:e] - c[s], r[s + 1:e] - r[e], c[s + 1:e] - c[e]
+        perp = (r0 * dr + c0 * dc > 0) & (-r1 * dr - c1 * dc > 0)
+        cross, e0, e1 = r0 * dc - c0 * dr, r0 * r0 + c0 * c0, r1 * r1 + c1 * c1
+        scale = L if L else 1                                  # both ends on one pixel: no distance is perpendicular
+        v = np.where(perp, cross * cross, np.where(e1 < e0, e1, e0) * scale)          # every distance over the one denominator
+        m = v.max()
+        if m > t2 * scale:
+            k = s + 1 + int(np.flatnonzero(v == m)[0])
+            keep[k] = True
+            stack.append((k, e))
+            stack.append((s, k))
+    return coords[keep]
+
+
+def _simplifier(simplify):
+    """The callable behind a simplify= argument: None -> scikit-image, 'exact' -> approximate_polygon_exact, a callable -> itself."""
+    if simplify is None:
+        return _default_simplify()
+    if isinstance(simplify, str):
+        if simplify != 'exact':
+            raise ValueError("simplify=%r: the only named simplifier is 'exact' (None: skimage.measure.approximate_polygon, or a "
+                             'callable(coords, tolerance))' % simplify)
+        return approximate_polygon_exact
+    return simplify
 
 
 def walk(parents, source, target):
@@ -125,7 +186,17 @@ def _boxes(grids, used, dev):
 
 
 def _launch(dev, packed, closest_buf, descs, parents, distances):
-    """One simq_grid_paths call over `descs`: dicts with the descriptor's grid / thin / closest offsets, shape, pixels, box and capacity."""
+    """One simq_grid_paths call over `descs` and the read-back of its lengths, status words and end pixels."""
+    P = len(descs)
+    small = torch.empty((P, 6), dtype=torch.int32, device=dev)          # lengths | status | end pixels
+    paths, par, dist = _enqueue(dev, packed, closest_buf, descs, parents, distances, small.view(-1))
+    host = small.cpu().numpy().reshape(-1)
+    return paths, host[:P].copy(), host[P:2 * P].copy(), host[2 * P:].reshape(P, 4).copy(), par, dist
+
+
+def _enqueue(dev, packed, closest_buf, descs, parents, distances, small):
+    """Queues one simq_grid_paths call over `descs`: dicts with the descriptor's grid / thin / closest offsets, shape, pixels, box and
+    capacity.  small: int32 device tensor whose first 6 P entries receive lengths | status | end pixels.  Nothing is read back."""
     P = len(descs)
     probs = (GridPathProblem * P)()
     po = io = 0
@@ -137,15 +208,13 @@ def _launch(dev, packed, closest_buf, descs, parents, distances):
         io += cells
     d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
     paths = torch.empty((po, 2), dtype=torch.int32, device=dev)
-    small = torch.empty((P, 6), dtype=torch.int32, device=dev)          # lengths | status | end pixels
-    lengths, status, ends = small.view(-1)[:P], small.view(-1)[P:2 * P], small.view(-1)[2 * P:]
+    lengths, status, ends = small[:P], small[P:2 * P], small[2 * P:6 * P]
     par = torch.empty(io, dtype=torch.int32, device=dev) if parents else None
     dist = torch.empty(io, dtype=torch.float32, device=dev) if distances else None
     lib.call('simq_grid_paths', ptr(packed), ctypes.c_int64(packed.numel()), ptr(closest_buf),
              ctypes.c_int64(0 if closest_buf is None else closest_buf.numel()), probs, P, ptr(d_probs), ptr(paths), ctypes.c_int64(po),
              ptr(lengths), ptr(ends), ptr(par), ctypes.c_int64(io), ptr(dist), ctypes.c_int64(io), ptr(status), stream_ptr(dev))
-    host = small.cpu().numpy().reshape(-1)
-    return paths, host[:P].copy(), host[P:2 * P].copy(), host[2 * P:].reshape(P, 4).copy(), par, dist
+    return paths, par, dist
 
 
 def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, distances=False, thin=None, closest=None):
@@ -167,6 +236,35 @@ def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, di
 
     The search state lives in LDS over the bounding box of the grid's free cells: a box of more than MAX_BOX_CELLS cells with its
     one-cell halo is refused (SimqError, nothing launched).  A path longer than the first buffer is fetched with one more launch."""
+    dev, packed, closest_buf, descs = _prepare(grids, sources, targets, grid_index, thin, closest)
+    paths, lengths, status, ends, par, dist = _launch(dev, packed, closest_buf, descs, parents, distances)
+    _raise_for(status)
+    starts = np.concatenate([[0], np.cumsum([d['capacity'] for d in descs])])
+    host = paths.cpu().numpy()
+    out = [host[starts[p]:starts[p] + min(lengths[p], descs[p]['capacity'])].copy() for p in range(len(descs))]
+    short = np.flatnonzero(status == CAPACITY)
+    if short.size:                                       # a longer buffer for those problems, once; no image is written again
+        paths2, lengths2, status2, _, _, _ = _launch(dev, packed, None, _again(descs, short, lengths, ends), False, False)
+        _raise_for(status2, allow_capacity=False)
+        host2, o = paths2.cpu().numpy(), 0
+        for p, n in zip(short, lengths2):
+            out[p] = host2[o:o + n].copy()
+            o += int(lengths[p])
+            status[p] = TRACED
+    shapes = [(d['rows'], d['cols']) for d in descs]
+    return DensePaths(out, status, ends, *[None if flat is None else _batch.views(flat, shapes) for flat in (par, dist)])
+
+
+def _again(descs, problems, lengths, ends):
+    """The descriptors of `problems` for a second search whose path buffer holds the whole dense path: the pixels the first search
+    used, no straight-line test, no snap."""
+    return [dict(descs[p], capacity=int(lengths[p]), thin=-1, closest=-1, src=tuple(int(x) for x in ends[p, :2]),
+                 tgt=tuple(int(x) for x in ends[p, 2:])) for p in problems]
+
+
+def _prepare(grids, sources, targets, grid_index, thin, closest):
+    """What grid_dense_paths and grid_waypoints share: arguments checked, the used grids (then their thin maps) and closest cells packed
+    on the device, one descriptor dict per problem.  Returns (device, packed uint8 buffer, closest buffer or None, descriptors)."""
     grids, _ = _batch.as_maps(grids, 'grids')
     srcs, tgts = [pixel(s) for s in sources], [pixel(t) for t in targets]
     if not grids or not srcs:
@@ -203,25 +301,79 @@ def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, di
         box = boxes[k]
         descs.append(dict(grid=goff[k], thin=toff.get(k, -1), closest=coff.get(k, -1), rows=rows, cols=cols, src=s,
                           tgt=t, box=box, capacity=max(1, min(box[2] * box[3], 2 * (box[2] + box[3]) + 8))))
-    paths, lengths, status, ends, par, dist = _launch(dev, packed, closest_buf, descs, parents, distances)
+    return dev, packed, closest_buf, descs
+
+
+def _enqueue_waypoints(dev, packed, paths, descs, capacities, tolerance, small, base):
+    """Queues one simq_grid_waypoints call behind the search that filled `paths` and small[:6 P]: its status words, counts and
+    waypoints go to small[base:], problem p's waypoints at pair sum(capacities[:p]).  Nothing is read back."""
+    P = len(descs)
+    probs = (GridWaypointProblem * P)()
+    po = wo = 0
+    for p, d in enumerate(descs):
+        probs[p] = GridWaypointProblem(d['grid'], po, wo, d['rows'], d['cols'], capacities[p], tolerance)
+        po += d['capacity']
+        wo += capacities[p]
+    d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+    lib.call('simq_grid_waypoints', ptr(packed), ctypes.c_int64(packed.numel()), ptr(paths), ctypes.c_int64(po), ptr(small[:P]),
+             ptr(small[P:2 * P]), probs, P, ptr(d_probs), ptr(small[base + 2 * P:]), ctypes.c_int64(wo), ptr(small[base + P:base + 2 * P]),
+             ptr(small[base:base + P]), stream_ptr(dev))
+
+
+def _search_and_simplify(dev, packed, closest_buf, descs, capacities, tolerance):
+    """simq_grid_paths and simq_grid_waypoints back to back on the same device buffers and the one read-back of both: (lengths, path
+    status, end pixels [P, 4], waypoint status, counts, the waypoint buffer [pairs, 2]) as host arrays."""
+    P = len(descs)
+    base = 6 * P + (6 * P) % 2                           # the waypoints start on an 8-byte boundary
+    small = torch.empty(base + 2 * P + 2 * sum(capacities), dtype=torch.int32, device=dev)
+    paths, _, _ = _enqueue(dev, packed, closest_buf, descs, False, False, small)
+    _enqueue_waypoints(dev, packed, paths, descs, capacities, tolerance, small, base)
+    host = small.cpu().numpy()
+    return (host[:P], host[P:2 * P], host[2 * P:6 * P].reshape(P, 4), host[base:base + P], host[base + P:base + 2 * P],
+            host[base + 2 * P:].reshape(-1, 2))
+
+
+def grid_waypoints(grids, sources, targets, grid_index=None, thin=None, closest=None, tolerance=1):
+    """The waypoints of P (grid, source, target) problems without a dense path on the host: simq_grid_paths as in grid_dense_paths (same
+    arguments), and right behind it simq_grid_waypoints, which simplifies each dense path by the exact rule of include/simq.h
+    (approximate_polygon_exact, integer tolerance in [1, 255]) and prunes it against its grid as shortest_paths.pyx:142-149 does.  One
+    array comes back for the call: status words, counts, end pixels and waypoints; a problem whose dense path did not fit its first
+    buffer, or that has more than WAY_CAPACITY waypoints, is finished by one more pair of launches and one more read-back.
+
+    Returns Waypoints(waypoints, status, endpoints): waypoints, a list of P int32 numpy arrays [m, 2], source first -- what
+    prune(grid, dense, approximate_polygon_exact) returns -- and empty for a STRAIGHT problem; status, int32 numpy [P] of TRACED /
+    STRAIGHT; endpoints, int32 numpy [P, 4], the (source, target) pixels the search used."""
+    if isinstance(tolerance, bool) or int(tolerance) != tolerance or not 1 <= int(tolerance) <= 255:
+        raise ValueError('grid_waypoints takes an integer tolerance in [1, 255], got %r' % (tolerance,))
+    tolerance = int(tolerance)
+    dev, packed, closest_buf, descs = _prepare(grids, sources, targets, grid_index, thin, closest)
+    capacities = [min(d['capacity'], WAY_CAPACITY) for d in descs]
+    lengths, status, ends, wstatus, counts, ways = _search_and_simplify(dev, packed, closest_buf, descs, capacities, tolerance)
     _raise_for(status)
-    starts = np.concatenate([[0], np.cumsum([d['capacity'] for d in descs])])
-    host = paths.cpu().numpy()
-    out = [host[starts[p]:starts[p] + min(lengths[p], descs[p]['capacity'])].copy() for p in range(len(descs))]
-    short = np.flatnonzero(status == CAPACITY)
-    if short.size:                                       # a longer buffer for those problems, once; no image is written again
-        again = [dict(descs[p], capacity=int(lengths[p]), thin=-1, closest=-1, src=tuple(int(x) for x in ends[p, :2]),
-                      tgt=tuple(int(x) for x in ends[p, 2:]))
-                 for p in short]
-        paths2, lengths2, status2, _, _, _ = _launch(dev, packed, None, again, False, False)
+    _raise_for_waypoints(wstatus)
+    status, ends = status.copy(), ends.copy()
+    starts = np.concatenate([[0], np.cumsum(capacities)])
+    out = [ways[starts[p]:starts[p] + max(0, min(counts[p], capacities[p]))].copy() for p in range(len(descs))]
+    short = np.flatnonzero((status == CAPACITY) | (wstatus == CAPACITY))
+    if short.size:                                       # buffers that hold the whole dense path and every waypoint, once
+        again = _again(descs, short, lengths, ends)
+        capacities2 = [int(counts[p]) if status[p] == TRACED else int(lengths[p]) for p in short]
+        _, status2, _, wstatus2, counts2, ways2 = _search_and_simplify(dev, packed, None, again, capacities2, tolerance)
         _raise_for(status2, allow_capacity=False)
-        host2, o = paths2.cpu().numpy(), 0
-        for p, n in zip(short, lengths2):
-            out[p] = host2[o:o + n].copy()
-            o += int(lengths[p])
+        _raise_for_waypoints(wstatus2, allow_capacity=False)
+        o = 0
+        for p, n, cap in zip(short, counts2, capacities2):
+            out[p] = ways2[o:o + n].copy()
+            o += cap
             status[p] = TRACED
-    shapes = [(d['rows'], d['cols']) for d in descs]
-    return DensePaths(out, status, ends, *[None if flat is None else _batch.views(flat, shapes) for flat in (par, dist)])
+    return Waypoints(out, status, ends)
+
+
+def _raise_for_waypoints(status, allow_capacity=True):
+    bad, codes = _batch.bad_problems(status, (0, 1, CAPACITY) if allow_capacity else (0,))
+    if bad.size:
+        raise SimqError('simq_grid_waypoints: %d problem(s) failed (status %s at problems %s; 2: a bad length, path status or a point '
+                        'outside its grid, 3: waypoint buffer, 4: loop bound)' % (bad.size, codes[:8].tolist(), bad[:8].tolist()))
 
 
 def _raise_for(status, allow_capacity=True):
@@ -266,8 +418,9 @@ class WaypointGraph(GridGraph):
 
     def shortest_path(self, source, target, simplify=None):
         """The waypoints of GridGraph.shortest_path (shortest_paths.pyx:121-154) as a list of (i, j), source first.  simplify:
-        callable(coords, tolerance) standing in for skimage.measure.approximate_polygon (the default, imported here)."""
-        simplify = _default_simplify() if simplify is None else simplify
+        callable(coords, tolerance) standing in for skimage.measure.approximate_polygon (the default, imported here), or 'exact' for
+        approximate_polygon_exact -- on the host here: this object's paths are host walks over cached parents."""
+        simplify = _simplifier(simplify)
         return prune(self.grid, self.dense_path(source, target), simplify)
 
 
@@ -279,8 +432,12 @@ def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positi
     become pixels and pixels positions on the host, in float64 as the reference's scalars; the straight-line test, the snap to the
     closest free cells, the search and the walk run on the device; simplification (simplify, default
     skimage.measure.approximate_polygon) and pruning run on the host, over the free-cell boxes of the maps that had a problem that was
-    not straight -- nothing else of a configuration space is downloaded.  Returns P lists of positions: the two given tuples when the
-    line is clear or the path has fewer than two waypoints, otherwise (x, y, 0) tuples with the given tuples at both ends."""
+    not straight -- nothing else of a configuration space is downloaded.  With simplify='exact' they run on the device as well
+    (grid_waypoints): one small array of status words, counts, end pixels and waypoints is read back, no dense path and no map.
+    Returns P lists of positions: the two given tuples when the line is clear or the path has fewer than two waypoints, otherwise
+    (x, y, 0) tuples with the given tuples at both ends."""
+    if isinstance(simplify, str):
+        _simplifier(simplify)                                 # (an unknown name is refused before anything is queued)
     maps, _ = _batch.as_maps(cspace, 'cspace')
     P = len(source_positions)
     if len(target_positions) != P or P < 1:
@@ -289,20 +446,28 @@ def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positi
                                      'map_index must name one of the %d maps for each of the %d positions' % (len(maps), P))
     srcs = [position_to_pixel_indices(s[0], s[1], tuple(maps[k].shape)) for s, k in zip(source_positions, map_index)]
     tgts = [position_to_pixel_indices(t[0], t[1], tuple(maps[k].shape)) for t, k in zip(target_positions, map_index)]
-    got = grid_dense_paths(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest)
-    if (got.status == TRACED).any():
-        simplify = _default_simplify() if simplify is None else simplify
+    on_device = isinstance(simplify, str)
+    if on_device:
+        got = grid_waypoints(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest)
+    else:
+        got = grid_dense_paths(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest)
+        if (got.status == TRACED).any():
+            simplify = _simplifier(simplify)
     host_maps, result = {}, []
     for p, k in enumerate(map_index):
         source_position, target_position = source_positions[p], target_positions[p]
         if got.status[p] == STRAIGHT:
             result.append([source_position, target_position])
             continue
-        if k not in host_maps:
-            host_maps[k] = _download_box(maps[k], got.paths, [q for q in range(P) if map_index[q] == k and got.status[q] == TRACED])
+        if on_device:
+            pixels = got.waypoints[p].tolist()
+        else:
+            if k not in host_maps:
+                host_maps[k] = _download_box(maps[k], got.paths, [q for q in range(P) if map_index[q] == k and got.status[q] == TRACED])
+            pixels = prune(host_maps[k], got.paths[p], simplify)
         shape = tuple(maps[k].shape)
         path = []
-        for i, j in prune(host_maps[k], got.paths[p], simplify):
+        for i, j in pixels:
             position_x, position_y = pixel_indices_to_position(i, j, shape)
             path.append((position_x, position_y, 0))
         if len(path) < 2:

@@ -1,11 +1,17 @@
-"""Rate of simq_grid_paths on the GPU: one JSON line with per-launch latency and searches/s.
+"""Rate of simq_grid_paths on the GPU, and of simq.shortest_paths with its two exact simplifiers: one JSON line with per-launch
+latency and searches/s, and per-call latency of shortest_paths.
 
-    python tools/grid_waypoints_rate.py [--reps 10]
+    python tools/grid_waypoints_rate.py [--reps 10] [--no-searches]
 
 Workloads: those of tools/grid_paths_rate.py -- Mapper-style configuration spaces (184 x 232 small, 232 x 232 large), open and
 cluttered, P = 1, 8, 64, 256, 1024 problems per launch (distinct random free sources and targets, the P problems spread over 8
 grids).  Each problem is a whole search plus its walk; no image is written.  Timed with HIP events around `reps` back-to-back launches
 after a warm-up, every status checked.  Includes the 96-byte-per-problem descriptor upload the C-ABI makes on the launch stream.
+
+shortest_paths rows ('shortest_paths' in the result): the cluttered grids of both rooms as device-resident configuration spaces (the
+grid is its own thin map, every cell its own closest cell), the same P, two rows each: simplify=simq.approximate_polygon_exact (dense
+paths and map boxes to the host, simplification and pruning there) and simplify='exact' (simq_grid_waypoints behind the search, one
+small read-back).  Whole calls on a host clock with the device synchronised at both ends: the median of 10 after 2 warm-ups.
 """
 import argparse
 import ctypes
@@ -28,6 +34,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--sizes', default='1,8,64,256,1024')
+    ap.add_argument('--no-searches', action='store_true', help='only the shortest_paths rows')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('grid_waypoints_rate.py needs a GPU')
@@ -46,7 +53,7 @@ def main():
             for g in grids:
                 ii, jj = np.nonzero(g)
                 boxes.append((int(ii.min()), int(jj.min()), int(ii.max() - ii.min() + 1), int(jj.max() - jj.min() + 1)))
-            for P in [int(x) for x in args.sizes.split(',')]:
+            for P in [] if args.no_searches else [int(x) for x in args.sizes.split(',')]:
                 probs = (GridPathProblem * P)()
                 for p in range(P):
                     k = p % 8
@@ -79,7 +86,42 @@ def main():
                 ms = e0.elapsed_time(e1) / args.reps
                 result['rows'].append({'room': room, 'grid': [R, C], 'kind': kind, 'P': P, 'ms_per_launch': round(ms, 4),
                                        'us_per_search': round(1e3 * ms / P, 3), 'searches_per_s': round(P / ms * 1e3, 1)})
+    result['shortest_paths'] = shortest_paths_rows(dev, rooms, [int(x) for x in args.sizes.split(',')])
     print(json.dumps(result))
+
+
+def shortest_paths_rows(dev, rooms, sizes):
+    import statistics
+    import time
+    import simq
+    from simq.waypoints import pixel_indices_to_position
+    rows = []
+    rng = np.random.RandomState(1)
+    for room, (R, C, rr, rc) in rooms.items():
+        grids = [cluttered(R, C, rr, rc, 10, 100 + k) for k in range(8)]
+        cspace = torch.from_numpy(np.stack(grids)).to(dev)
+        ii, jj = np.meshgrid(np.arange(R, dtype=np.int32), np.arange(C, dtype=np.int32), indexing='ij')
+        closest = torch.from_numpy(np.stack([np.stack([ii, jj])] * 8)).to(dev)
+        free = [np.argwhere(g != 0) for g in grids]
+        for P in sizes:
+            index = [p % 8 for p in range(P)]
+            ends = [[pixel_indices_to_position(*[int(x) for x in free[k][rng.randint(len(free[k]))]], (R, C)) + (0.0,) for k in index]
+                    for _ in range(2)]
+            want = None
+            for label, simplify in (('host', simq.approximate_polygon_exact), ('exact', 'exact')):
+                times = []
+                for rep in range(12):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    got = simq.shortest_paths(cspace, cspace, closest, ends[0], ends[1], map_index=index, simplify=simplify)
+                    torch.cuda.synchronize()
+                    times.append(time.perf_counter() - t0)
+                assert want is None or got == want
+                want = got
+                ms = 1e3 * statistics.median(times[2:])
+                rows.append({'room': room, 'grid': [R, C], 'P': P, 'simplify': label, 'ms_per_call': round(ms, 3),
+                             'us_per_path': round(1e3 * ms / P, 2), 'bent': sum(len(q) > 2 for q in got)})
+    return rows
 
 
 if __name__ == '__main__':
