@@ -986,6 +986,40 @@ int simq_observation_update(const void* d_frames, int64_t frame_words, const sim
                             simq_observation_problem* d_problems, float* d_overhead, int64_t overhead_floats, uint8_t* d_occupancy,
                             int64_t occupancy_bytes, int32_t* d_status, void* stream);
 
+/* ---- observation maps, ordered frame sequences: several camera frames per pair of maps in one launch --------------------------------
+ * What successive simq_observation_update launches leave in a pair of maps, one frame each and in the order given, computed by one
+ * launch, bit for bit.  `frames`: host array of n_frames descriptors; the frame, camera and id-range fields of simq_observation_problem
+ * mean what they mean above.  `begin`: host table [n_sequences + 1]; sequence s is the frames begin[s] .. begin[s + 1] - 1 in
+ * application order, and all of them name one overhead_offset, occupancy_offset, rows and cols: the maps of the sequence.  In everything
+ * else the frames of a sequence may differ (height and width, so that cameras may mix; the id ranges).  Per frame the projection, seg,
+ * pixel (i, j) and the rule among the points of ONE frame are those of simq_observation_update, unchanged: the same fp32 operations,
+ * none fused, the correctly rounded division; among equal greatest p_z the largest frame index k; -0 equals +0.  Across the frames
+ * of a sequence:
+ *   overhead map   pixel (i, j) takes the value that the LAST frame of the sequence with a point on (i, j) gives it by the per-frame
+ *                  rule; the heights in earlier frames do not matter.  A seg of 0 is written like any other.  A pixel that no frame
+ *                  of the sequence reaches keeps its value.
+ *   occupancy map  pixel (i, j) becomes 1 where a point with seg == 2/8 of ANY applied frame lands, and is otherwise left as it is.
+ *   a frame with a point that is not finite is skipped as a whole: it gives status 1, decides no overhead pixel and sets no occupancy
+ *                  byte, and the other frames of its sequence are applied as if it were absent (the per-problem rule of
+ *                  simq_observation_update carried to frames).
+ * The configuration space is derived from the final occupancy map only (simq_occupancy_maps), so nothing between the frames is lost.
+ * A sequence holds at most SIMQ_OBSERVATION_MAX_SEQUENCE frames: the kernel orders points by one 64-bit key, [position in the
+ * sequence + 1 : 10 bits][order-preserving bits of p_z : 32][frame index k : 22], k < SIMQ_OBSERVATION_MAX_POINTS = 2^22 leaves 10
+ * bits, and key 0 marks the untouched pixel.  More frames of one map take successive launches.
+ * Validated here before anything is copied or launched: per frame everything simq_observation_update checks per problem; begin[0] = 0,
+ * begin[n_sequences] = n_frames and begin rising, so every sequence has 1 .. SIMQ_OBSERVATION_MAX_SEQUENCE frames; the frames of a
+ * sequence agreeing on the four map fields; no two SEQUENCES sharing a byte of any map, overhead or occupancy (the frames of one map
+ * belong in one sequence); every map disjoint from d_frames, d_problems, d_begin and d_status, and those from each other; alignment
+ * (d_problems 8-byte, the others 4-byte).  A refusal writes nothing.  The descriptors are copied to the caller's device buffers
+ * d_problems (n_frames descriptors) and d_begin (n_sequences + 1 int32) on `stream`.  d_status[n_frames] (int32), one word per frame:
+ * 0 = applied, 1 = a point was not finite (the frame was skipped), 2 = bad descriptor: the kernel checks sizes, offsets and the
+ * agreement of the map fields again, and a sequence with a bad descriptor writes nothing and gives 2 for all its frames. */
+#define SIMQ_OBSERVATION_MAX_SEQUENCE 1023
+int simq_observation_update_sequences(const void* d_frames, int64_t frame_words, const simq_observation_problem* frames, int n_frames,
+                                      const int32_t* begin, int n_sequences, simq_observation_problem* d_problems, int32_t* d_begin,
+                                      float* d_overhead, int64_t overhead_floats, uint8_t* d_occupancy, int64_t occupancy_bytes,
+                                      int32_t* d_status, void* stream);
+
 /* ---- Q-map visualisations: the state and output panels of utils.get_state_output_visualization (utils.py:97-131), as the training
  * loop draws them for tensorboard (train.py:292-304) and enjoy.py --debug on every step --------------------------------------------
  * One problem = one state [96][96][channels] fp32 NHWC (a batch row, a slice of a replay ring: read in place) and one output

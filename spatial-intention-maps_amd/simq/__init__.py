@@ -51,6 +51,7 @@ _LAZY = {
     'configuration_space': ('.occupancy', 'configuration_space'),
     'camera_geometry': ('.observation', 'camera_geometry'),
     'observation_update': ('.observation', 'observation_update'),
+    'observation_update_sequences': ('.observation', 'observation_update_sequences'),
     'observe': ('.observation', 'observe'),
     'BatchedMapper': ('.mapper', 'BatchedMapper'),
     'RobotState': ('.mapper', 'RobotState'),

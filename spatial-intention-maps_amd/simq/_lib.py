@@ -191,6 +191,8 @@ _SIGS = {
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                     c_void_p]),
     'simq_observation_update': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'simq_observation_update_sequences': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                                  c_int64, c_void_p, c_void_p]),
     'simq_state_output_visualizations': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_void_p, c_int64, c_void_p]),
 }
 

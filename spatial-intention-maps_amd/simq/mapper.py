@@ -7,6 +7,8 @@ object owns, and the two calls run the batched operators of this package as one 
 
     update       simq_observation_update  ->  simq_occupancy_maps                                     (envs.py:2053-2065, 2444-2459)
     get_states   simq_grid_distance_images_snapped  ->  simq_intention_maps  ->  simq_local_state_images     (envs.py:2067-2112)
+    defer ...    nothing: the frames of any number of update calls wait in pinned memory, per mapper in capture order
+    flush        simq_observation_update_sequences  ->  simq_occupancy_maps      (what those update calls would have left)
 
 Each stage is one launch however many mappers are named, reads the tensors of the stage before it where they lie, and leaves its
 status words on the device; the call reads them back once, at its end.  What lets the read-back wait is the upstream status of
@@ -321,6 +323,53 @@ class _Plan:
         return self._fixed
 
 
+class _Deferred:
+    """One deferred camera frame: px, py, depth and ids as `words` 4-byte words at word `at` of staging block `block`, and its
+    descriptor with every field final but the four frame offsets, which count from the frame's first word."""
+    __slots__ = ('block', 'at', 'words', 'problem')
+
+    def __init__(self, block, at, words, problem):
+        self.block, self.at, self.words, self.problem = block, at, words, problem
+
+
+class _Staging:
+    """The host memory deferred frames wait in: int32 blocks, pinned where there is a device to pin them for, handed out front to back.
+    It grows by blocks (each as large as all before it, at least BLOCK_WORDS and the frame that asked) and is never freed: `compact`
+    moves what still waits to the front and the rest is reused."""
+    BLOCK_WORDS = 1 << 22
+
+    def __init__(self):
+        self.tensors, self.arrays, self.used, self.cursor = [], [], [], 0
+
+    def take(self, words):
+        """(block, word offset) of `words` free words; the cursor never goes back to an earlier block."""
+        while self.cursor < len(self.tensors):
+            b = self.cursor
+            if self.used[b] + words <= self.arrays[b].size:
+                at = self.used[b]
+                self.used[b] += words
+                return b, at
+            self.cursor += 1
+        size = max(words, self.BLOCK_WORDS, sum(a.size for a in self.arrays))
+        t = torch.empty(size, dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        self.tensors.append(t)
+        self.arrays.append(t.numpy())
+        self.used.append(words)
+        return len(self.tensors) - 1, 0
+
+    def compact(self, waiting):
+        """Moves the frames `waiting` (_Deferred) to the front, in the order they lie in.  A frame never moves to a later place than
+        it has -- the frames before it take no more room than they did -- so no move overwrites a frame that has yet to move.  Only
+        for a time when no upload from the blocks is in flight."""
+        waiting = sorted(waiting, key=lambda f: (f.block, f.at))
+        self.used, self.cursor = [0] * len(self.tensors), 0
+        for f in waiting:
+            b, at = self.take(f.words)
+            if (b, at) != (f.block, f.at):
+                self.arrays[b][at:at + f.words] = self.arrays[f.block][f.at:f.at + f.words]
+                f.block, f.at = b, at
+
+
 def round_up_to_even(x):
     """envs.py:2404-2406."""
     return 2 * math.ceil(x / 2)
@@ -404,7 +453,8 @@ class BatchedMapper:
     `closest_cspace_indices` int32 [M, 2, rows, cols] when every environment has the same room, otherwise as lists of M views
     ([rows_m, cols_m], [2, rows_m, cols_m]) into those buffers.  `occupancy_status` int32 [M] holds the status word of each mapper's
     last configuration space (NOT_UPDATED before the first); `distance_to_receptacle_maps` (use_distance_to_receptacle_map) one
-    fp32 [rows, cols] device map per environment (environments of one room and receptacle share it)."""
+    fp32 [rows, cols] device map per environment (environments of one room and receptacle share it).  `pending` int64 [M] counts the
+    frames `defer` holds of each mapper until `flush` applies them."""
 
     def __init__(self, room_width, room_length, robot_types, robot_masks, group_indices=None, receptacle_position=None, *,
                  use_robot_map=True, use_distance_to_receptacle_map=False, use_shortest_path_to_receptacle_map=False,
@@ -480,6 +530,10 @@ class BatchedMapper:
         self.num_channels = len(self.channels)
         self.mask_bank = np.stack(bank)
         self._plans = {}                                   # what get_states' array form needs of a `mappers` tuple, made once
+        cells = [r * c for r, c in self.shapes]
+        self._at = np.concatenate([[0], np.cumsum(cells)]).tolist()                       # cell offset of mapper m's maps; [M]: all cells
+        self._pending = [[] for _ in range(M)]             # the deferred frames of every mapper in capture order (_Deferred)
+        self._staging = _Staging()
 
         # the device tensors come after the argument checks, which need no device; without one the object still checks the arguments
         # of its calls, and then says so
@@ -490,8 +544,6 @@ class BatchedMapper:
     def _allocate(self):
         dev = self.device = _batch.device('batched mappers')
         E, M = self.num_envs, self.num_mappers
-        cells = [r * c for r, c in self.shapes]
-        self._at = np.concatenate([[0], np.cumsum(cells)]).tolist()                       # cell offset of mapper m's maps; [M]: all cells
         total = self._at[M]
         # occupancy maps and room masks are one uint8 buffer: simq_occupancy_maps reads both from one base, where they lie
         rooms = {}
@@ -554,6 +606,13 @@ class BatchedMapper:
         for e in envs:
             if not 0 <= e < self.num_envs:
                 raise ValueError('no environment %d (0 .. %d)' % (e, self.num_envs - 1))
+        dropped = False
+        for e in envs:                                     # deferred frames belong to the Mapper objects the episode start replaces
+            for m in range(self.env_begin[e], self.env_begin[e + 1]):
+                dropped = dropped or bool(self._pending[m])
+                self._pending[m] = []
+        if dropped:
+            self._staging.compact([f for waiting in self._pending for f in waiting])
         if self.device is None:
             self._allocate()
         for e in envs:
@@ -574,21 +633,13 @@ class BatchedMapper:
         simq_occupancy_maps: their closest cells are undefined, and get_states reports them until an update succeeds); every
         other mapper of the call is updated."""
         ms = self._mappers(mappers)
+        self._nothing_pending(ms, 'update')
         if self.device is None:
             self._allocate()
-        P, dev, M = len(ms), self.device, self.num_mappers
+        P = len(ms)
         st_obs = observation._enqueue(depth, ids, geometries, id_ranges, [self._view(self._overhead, m) for m in ms],
                                       [self._view(self._bytes, m) for m in ms])
-        probs = (occupancy.OccupancyProblem * P)(*[occupancy.OccupancyProblem(self._at[m], self._mask_at[m], self._at[m], self.shapes[m][0],
-                                                                               self.shapes[m][1], self.radius[m], self.thin_radius) for m in ms])
-        d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
-        whole = ms == list(range(M))
-        st_occ = self.occupancy_status if whole else torch.empty(P, dtype=torch.int32, device=dev)
-        lib.call('simq_occupancy_maps', ptr(self._bytes), ctypes.c_int64(self._bytes.numel()), probs, P, ptr(d_probs), ptr(self._cspace),
-                 ptr(self._thin), ctypes.c_int64(self._cspace.numel()), ptr(self._closest), ctypes.c_int64(self._closest.numel()), ptr(st_occ),
-                 stream_ptr(dev))
-        if not whole:
-            self.occupancy_status[torch.as_tensor(ms, dtype=torch.int64).to(dev)] = st_occ
+        st_occ = self._enqueue_occupancy(ms)
         bad, codes = _batch.bad_problems(torch.cat([st_obs, st_occ]))                       # the one read-back of the call
         if bad.size:
             said = []
@@ -601,6 +652,123 @@ class BatchedMapper:
                 if other:
                     said.append('%s: status %s at mapper(s) %s' % (name, [c for _, c in other][:8], self._named([p for p, _ in other], ms)))
             raise SimqError('BatchedMapper.update: ' + '; '.join(said))
+
+    def _enqueue_occupancy(self, ms):
+        """simq_occupancy_maps over the mappers `ms`: queues the launch, stores its status words in `occupancy_status` and returns them
+        as a device tensor [len(ms)]."""
+        P, dev, M = len(ms), self.device, self.num_mappers
+        probs = (occupancy.OccupancyProblem * P)(*[occupancy.OccupancyProblem(self._at[m], self._mask_at[m], self._at[m], self.shapes[m][0],
+                                                                               self.shapes[m][1], self.radius[m], self.thin_radius) for m in ms])
+        d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+        whole = ms == list(range(M))
+        st_occ = self.occupancy_status if whole else torch.empty(P, dtype=torch.int32, device=dev)
+        lib.call('simq_occupancy_maps', ptr(self._bytes), ctypes.c_int64(self._bytes.numel()), probs, P, ptr(d_probs), ptr(self._cspace),
+                 ptr(self._thin), ctypes.c_int64(self._cspace.numel()), ptr(self._closest), ctypes.c_int64(self._closest.numel()), ptr(st_occ),
+                 stream_ptr(dev))
+        if not whole:
+            self.occupancy_status[torch.as_tensor(ms, dtype=torch.int64).to(dev)] = st_occ
+        return st_occ
+
+    # ---- deferred frames: several Mapper.update calls of a mapper applied by one launch ------------------------------------------
+    @property
+    def pending(self):
+        """The number of deferred frames of every mapper that no flush has applied yet: int64 [M]."""
+        return np.asarray([len(held) for held in self._pending], np.int64)
+
+    def _nothing_pending(self, ms, what):
+        held = [p for p, m in enumerate(ms) if self._pending[m]]
+        if held:
+            raise SimqError('BatchedMapper.%s: mapper(s) %s have deferred frames that are not in their maps yet (%s pending); call flush() first'
+                            % (what, self._named(held, ms), [len(self._pending[ms[p]]) for p in held[:8]]))
+
+    def defer(self, depth, ids, geometries, id_ranges, mappers=None):
+        """`update` put off: the arguments of `update`, checked as there, and every frame copied into host memory of this object
+        (pinned where there is a device; it grows in blocks and is reused after a flush), so that the caller may overwrite its arrays.
+        Nothing is launched and no device is needed.  A mapper may be named in any number of defer calls: its frames keep the order of
+        the calls, and `flush` applies them all in one launch.  Until then the mapper's maps are behind: update, get_states,
+        shortest_paths and distances_to_receptacle refuse it."""
+        ms = self._mappers(mappers)
+        depth, ids, geometries, id_ranges, P = observation._checked_frames(depth, ids, geometries, id_ranges, 'BatchedMapper.defer')
+        if P != len(ms):
+            raise ValueError('%d frames for %d mappers' % (P, len(ms)))
+        observation._layout(depth, ids, geometries)                                       # (the checks of every frame's shape against its geometry)
+        for p, m in enumerate(ms):
+            g = geometries[p]
+            h, w = depth[p].shape
+            parts = [np.ascontiguousarray(g.pixel_x, np.float32), np.ascontiguousarray(g.pixel_y, np.float32)] + \
+                [a.cpu().numpy() if isinstance(a, torch.Tensor) else a for a in (depth[p], ids[p])]
+            words = w + h + 2 * h * w
+            block, at = self._staging.take(words)
+            room, k = self._staging.arrays[block], at
+            for a in parts:
+                room[k:k + a.size] = a.reshape(-1).view(np.int32)
+                k += a.size
+            problem = observation.ObservationProblem()
+            observation._describe(problem, g, id_ranges[p], (w + h, w + h + h * w), (0, w), (h, w), self._at[m], self._at[m], self.shapes[m])
+            self._pending[m].append(_Deferred(block, at, words, problem))
+
+    def flush(self, mappers=None):
+        """Applies the deferred frames of the named mappers (of every mapper that has some when omitted) in capture order, as the
+        `update` calls they stand for would have: one upload per staging block that holds some of them, one
+        simq_observation_update_sequences launch (more only where a mapper has more than 1 023 frames), one simq_occupancy_maps
+        launch over those mappers, one read-back of all status words.  A mapper without deferred frames is left alone.  Raises
+        SimqError as `update` does, naming mappers and their frames (counted from 0 in capture order): a frame with a point that is
+        not finite is skipped, every other frame and mapper is applied; `occupancy_status` is kept as `update` keeps it."""
+        ms = [m for m in (range(self.num_mappers) if mappers is None else self._mappers(mappers)) if self._pending[m]]
+        if not ms:
+            return
+        if self.device is None:
+            self._allocate()
+        dev, staging = self.device, self._staging
+        held = [(p, k, f) for p, m in enumerate(ms) for k, f in enumerate(self._pending[m])]
+        spans = {}
+        for _, _, f in held:
+            lo, hi = spans.get(f.block, (f.at, f.at + f.words))
+            spans[f.block] = (min(lo, f.at), max(hi, f.at + f.words))
+        shift, words = {}, 0
+        for b in sorted(spans):
+            shift[b] = words - spans[b][0]
+            words += spans[b][1] - spans[b][0]
+        frames = torch.empty(words, dtype=torch.int32, device=dev)
+        for b, (lo, hi) in sorted(spans.items()):
+            frames[shift[b] + lo:shift[b] + hi].copy_(staging.tensors[b][lo:hi], non_blocking=True)
+        total = self._at[self.num_mappers]
+        bases = (self._overhead.data_ptr(), total, self._bytes.data_ptr(), total)
+        st_obs = torch.empty(len(held), dtype=torch.int32, device=dev)
+        where, at = np.empty(len(held), np.int64), 0
+        for mine, begin in observation.sequence_launches([p for p, _, _ in held]):
+            probs = (observation.ObservationProblem * len(mine))()
+            for i, n in enumerate(mine.tolist()):
+                f = held[n][2]
+                probs[i] = f.problem
+                q, by = probs[i], shift[f.block] + f.at
+                q.depth_offset, q.ids_offset, q.px_offset, q.py_offset = q.depth_offset + by, q.ids_offset + by, q.px_offset + by, q.py_offset + by
+            observation.call_sequences(frames, words, probs, begin, bases, st_obs[at:at + len(mine)], dev)
+            where[mine] = at + np.arange(len(mine))
+            at += len(mine)
+        st_occ = self._enqueue_occupancy(ms)
+        codes = torch.cat([st_obs, st_occ]).cpu().numpy()                                  # the one read-back of the call
+        for m in ms:
+            self._pending[m] = []
+        staging.compact([f for waiting in self._pending for f in waiting])                 # (the read-back has waited for the uploads)
+        obs, occ = codes[:len(held)][where], codes[len(held):]
+        if obs.any() or occ.any():
+            said = []
+            skipped = [n for n in np.flatnonzero(obs == 1).tolist()]
+            if skipped:
+                said.append('simq_observation_update_sequences: %s hold a point that is not finite, those frames are skipped' % ', '.join(
+                    'mapper %s frame %d' % (self._named([held[n][0]], ms), held[n][1]) for n in skipped[:8]))
+            other = [n for n in np.flatnonzero(obs > 1).tolist()]
+            if other:
+                said.append('simq_observation_update_sequences: status %s at %s' % (obs[other][:8].tolist(), ', '.join(
+                    'mapper %s frame %d' % (self._named([held[n][0]], ms), held[n][1]) for n in other[:8])))
+            first, rest = np.flatnonzero(occ == 1).tolist(), np.flatnonzero(occ > 1).tolist()
+            if first:
+                said.append('simq_occupancy_maps: mapper(s) %s have a configuration space without a free cell, their closest cells are undefined'
+                            % self._named(first, ms))
+            if rest:
+                said.append('simq_occupancy_maps: status %s at mapper(s) %s' % (occ[rest][:8].tolist(), self._named(rest, ms)))
+            raise SimqError('BatchedMapper.flush: ' + '; '.join(said))
 
     def _view(self, flat, m, per=()):
         k = 2 if per else 1
@@ -665,6 +833,7 @@ class BatchedMapper:
         configuration space without a free cell): their distance channels come from images of zeros, every other mapper's state is
         right."""
         ms = self._mappers(mappers)
+        self._nothing_pending(ms, 'get_states')
         P, C = len(ms), self.num_channels
         want = (P, arch.STATE_WIDTH, arch.STATE_WIDTH, C)
         pool = None
@@ -976,14 +1145,17 @@ class BatchedMapper:
         """Mapper.shortest_path (envs.py:2186-2187) of the named mappers: simq.shortest_paths on this object's tensors (simplify: None for
         scikit-image, 'exact' for the integer rule on the device behind the search, or a callable(coords, tolerance))."""
         from .waypoints import shortest_paths
+        ms = self._mappers(mappers)
+        self._nothing_pending(ms, 'shortest_paths')
         return shortest_paths(self.configuration_space, self.cspace_thin, self.closest_cspace_indices, source_positions, target_positions,
-                              self._mappers(mappers), simplify)
+                              ms, simplify)
 
     def distances_to_receptacle(self, positions, mappers=None, shortest_path=True):
         """Mapper.distance_to_receptacle (envs.py:2189-2194) for the named mappers' position lists: simq.distances_to_receptacle on this
         object's tensors, with the receptacle of each mapper's environment."""
         from .grid_queries import distances_to_receptacle
         ms = self._mappers(mappers)
+        self._nothing_pending(ms, 'distances_to_receptacle')
         if any(self.receptacle_positions[self.env_of[m]] is None for m in ms):
             raise ValueError('distances_to_receptacle needs the receptacle_position the object was built with')
         return distances_to_receptacle(self.configuration_space, self.closest_cspace_indices,

@@ -6,7 +6,8 @@ envs.py:1926-1954), sorts the points by height and scatters their segmentation v
 robot per step, on the host.  ``simq_observation_update`` (csrc/observation_maps.hip) does it for many frames in one launch, updating
 both maps in place on the device, bit for bit equal to that sequence; the rules are stated in include/simq.h.  The updated occupancy
 map is what ``simq.occupancy_maps`` reads and the overhead map is the base map of the ``overhead`` channel of
-``simq.local_state_images``: neither ever needs to be a host array.
+``simq.local_state_images``: neither ever needs to be a host array.  ``simq_observation_update_sequences`` applies several frames per
+pair of maps in one launch, in the order given (``observation_update_sequences``; ``BatchedMapper.defer`` / ``flush`` use it).
 
 The camera's unit vectors and pixel tables are formed here, on the host, in the reference's own sequence of numpy float32 operations
 (``camera_geometry``); the library has no trigonometry and no normalisation.
@@ -22,6 +23,7 @@ from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
 
 MAX_POINTS = 1 << 22             # SIMQ_OBSERVATION_MAX_POINTS of include/simq.h
+MAX_SEQUENCE = 1023              # SIMQ_OBSERVATION_MAX_SEQUENCE: the frames of one map in one launch
 
 # What the projection of one camera pose needs: float32 vectors [3], the tables pixel_x [width] and pixel_y [height], and the three
 # depth constants far * near, far, far - near as float32.
@@ -106,23 +108,20 @@ def _per_problem(values, P, cls, what):
     return values
 
 
-def _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
-    """The argument tuple of simq_observation_update, the status tensor and the device tensors the call reads
-    (tools/observation_maps_rate.py times the upload and the library call with it)."""
+def _checked_frames(depth, ids, geometries, id_ranges, entry='observation_update'):
+    """The frames, geometries and id ranges of a call as lists of P, checked as far as no device is needed."""
     depth, _ = _frames(depth, np.float32, 'depth')
     ids, _ = _frames(ids, np.int32, 'ids')
     P = len(depth)
     if P < 1 or len(ids) != P:
-        raise ValueError('observation_update needs at least one frame and as many id frames as depth frames (%d, %d)' % (P, len(ids)))
-    geometries = _per_problem(geometries, P, CameraGeometry, 'geometries')
-    id_ranges = _per_problem(id_ranges, P, IdRanges, 'id_ranges')
-    dev = _batch.device('observation maps')
-    overhead_maps = _maps(overhead_maps, torch.float32, dev, 'overhead_maps')
-    occupancy_maps = _maps(occupancy_maps, torch.uint8, dev, 'occupancy_maps')
-    if len(overhead_maps) != P or len(occupancy_maps) != P:
-        raise ValueError('%d frames but %d overhead maps and %d occupancy maps' % (P, len(overhead_maps), len(occupancy_maps)))
+        raise ValueError('%s needs at least one frame and as many id frames as depth frames (%d, %d)' % (entry, P, len(ids)))
+    return depth, ids, _per_problem(geometries, P, CameraGeometry, 'geometries'), _per_problem(id_ranges, P, IdRanges, 'id_ranges'), P
 
-    # one buffer of 4-byte words: each distinct geometry's tables once, then every frame's depth and ids
+
+def _layout(depth, ids, geometries):
+    """One buffer of 4-byte words: each distinct geometry's tables once, then every frame's depth and ids.  Returns the arrays in that
+    order, their word count, {id(geometry): (px_offset, py_offset)} and per frame (depth_offset, ids_offset)."""
+    P = len(depth)
     tables, words, parts = {}, 0, []
     for g in geometries:
         if id(g) not in tables:
@@ -141,33 +140,54 @@ def _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
         offsets.append((words, words + n))
         parts += [depth[p], ids[p]]
         words += 2 * n
-    frames, _ = _batch.pack(parts, torch.int32, dev)
+    return parts, words, tables, offsets
 
-    # the maps where they are: offsets from the lowest address of each kind
+
+def _map_bases(overhead_maps, occupancy_maps):
+    """The maps where they are: offsets from the lowest address of each kind.  Returns (base_o, overhead_floats, base_c, occupancy_bytes)."""
     base_o = min(m.data_ptr() for m in overhead_maps)
     base_c = min(m.data_ptr() for m in occupancy_maps)
     if any((m.data_ptr() - base_o) % 4 for m in overhead_maps):
         raise ValueError('overhead_maps: the maps must be 4-byte aligned to each other')
     overhead_floats = max((m.data_ptr() - base_o) // 4 + m.numel() for m in overhead_maps)
     occupancy_bytes = max(m.data_ptr() - base_c + m.numel() for m in occupancy_maps)
+    return base_o, overhead_floats, base_c, occupancy_bytes
+
+
+def _describe(q, g, r, frame_at, table_at, frame_shape, overhead_offset, occupancy_offset, map_shape):
+    """Fills the ObservationProblem q: the frame at word offsets frame_at = (depth, ids) with its tables at table_at = (px, py)."""
+    q.depth_offset, q.ids_offset = frame_at
+    q.px_offset, q.py_offset = table_at
+    q.overhead_offset, q.occupancy_offset = overhead_offset, occupancy_offset
+    for name, v in (('cam', g.position), ('principal', g.principal), ('right', g.right), ('up', g.up)):
+        setattr(q, name, (ctypes.c_float * 3)(*[float(x) for x in v]))
+    q.far_near, q.far, q.far_minus_near = float(g.far_near), float(g.far), float(g.far_minus_near)
+    q.min_obstacle, q.max_obstacle, q.min_cube, q.max_cube = int(r.min_obstacle), int(r.max_obstacle), int(r.min_cube), int(r.max_cube)
+    q.has_receptacle = 0 if r.receptacle is None else 1
+    q.receptacle = 0 if r.receptacle is None else int(r.receptacle)
+    q.height, q.width = frame_shape
+    q.rows, q.cols = map_shape
+
+
+def _prepare(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps):
+    """The argument tuple of simq_observation_update, the status tensor and the device tensors the call reads
+    (tools/observation_maps_rate.py times the upload and the library call with it)."""
+    depth, ids, geometries, id_ranges, P = _checked_frames(depth, ids, geometries, id_ranges)
+    dev = _batch.device('observation maps')
+    overhead_maps = _maps(overhead_maps, torch.float32, dev, 'overhead_maps')
+    occupancy_maps = _maps(occupancy_maps, torch.uint8, dev, 'occupancy_maps')
+    if len(overhead_maps) != P or len(occupancy_maps) != P:
+        raise ValueError('%d frames but %d overhead maps and %d occupancy maps' % (P, len(overhead_maps), len(occupancy_maps)))
+    parts, words, tables, offsets = _layout(depth, ids, geometries)
+    frames, _ = _batch.pack(parts, torch.int32, dev)
+    base_o, overhead_floats, base_c, occupancy_bytes = _map_bases(overhead_maps, occupancy_maps)
     probs = (ObservationProblem * P)()
     for p in range(P):
-        g, r, om, cm = geometries[p], id_ranges[p], overhead_maps[p], occupancy_maps[p]
+        om, cm = overhead_maps[p], occupancy_maps[p]
         if tuple(om.shape) != tuple(cm.shape):
             raise ValueError('problem %d: an overhead map of %s but an occupancy map of %s' % (p, tuple(om.shape), tuple(cm.shape)))
-        q = probs[p]
-        q.depth_offset, q.ids_offset = offsets[p]
-        q.px_offset, q.py_offset = tables[id(g)]
-        q.overhead_offset = (om.data_ptr() - base_o) // 4
-        q.occupancy_offset = cm.data_ptr() - base_c
-        for name, v in (('cam', g.position), ('principal', g.principal), ('right', g.right), ('up', g.up)):
-            setattr(q, name, (ctypes.c_float * 3)(*[float(x) for x in v]))
-        q.far_near, q.far, q.far_minus_near = float(g.far_near), float(g.far), float(g.far_minus_near)
-        q.min_obstacle, q.max_obstacle, q.min_cube, q.max_cube = int(r.min_obstacle), int(r.max_obstacle), int(r.min_cube), int(r.max_cube)
-        q.has_receptacle = 0 if r.receptacle is None else 1
-        q.receptacle = 0 if r.receptacle is None else int(r.receptacle)
-        q.height, q.width = depth[p].shape
-        q.rows, q.cols = om.shape
+        _describe(probs[p], geometries[p], id_ranges[p], offsets[p], tables[id(geometries[p])], depth[p].shape,
+                  (om.data_ptr() - base_o) // 4, cm.data_ptr() - base_c, om.shape)
     d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
     status = torch.empty(P, dtype=torch.int32, device=dev)
     args = (ptr(frames), ctypes.c_int64(words), probs, P, ptr(d_probs), ctypes.c_void_p(base_o), ctypes.c_int64(overhead_floats),
@@ -209,6 +229,100 @@ def observation_update(depth, ids, geometries, id_ranges, overhead_maps, occupan
             raise SimqError('simq_observation_update: %d frame(s) hold a point that is not finite (a depth buffer outside what the near and far '
                             'planes allow); their maps are unchanged (problems %s)' % (bad.size, bad[:8].tolist()))
         raise SimqError('simq_observation_update: %d problem(s) failed (status %s at problems %s)' % (bad.size, codes[:8].tolist(), bad[:8].tolist()))
+    return overhead_maps, occupancy_maps
+
+
+def sequence_launches(map_index):
+    """How frames that name the maps `map_index` (ints, in the order the frames are given) go into launches of
+    simq_observation_update_sequences: a list of (frames, begin) -- `frames` the positions of the launch's frames in `map_index`, map by
+    map and within a map in the order given (a stable sort), `begin` the int32 table of its sequences.  A map with more than
+    MAX_SEQUENCE frames continues in the next launch, so launch l holds of every map its frames l * MAX_SEQUENCE .. of that order."""
+    index = np.asarray(map_index, np.int64)
+    order = np.argsort(index, kind='stable')
+    by_map = index[order]
+    first = np.flatnonzero(np.concatenate([[True], by_map[1:] != by_map[:-1]]))          # where each map's frames begin in `order`
+    rank = np.arange(len(order)) - np.repeat(first, np.diff(np.concatenate([first, [len(order)]])))
+    out = []
+    for l in range(int(rank.max()) // MAX_SEQUENCE + 1):
+        mine = rank // MAX_SEQUENCE == l
+        frames, maps = order[mine], by_map[mine]
+        begin = np.concatenate([[0], np.flatnonzero(maps[1:] != maps[:-1]) + 1, [len(frames)]]).astype(np.int32)
+        out.append((frames, begin))
+    return out
+
+
+def call_sequences(frames, words, probs, begin, bases, status, dev):
+    """One simq_observation_update_sequences launch: the descriptors `probs` (ObservationProblem array) and the table `begin` (int32
+    array) go up in the call; `status` is the int32 device tensor of len(probs) words it writes."""
+    begin = np.ascontiguousarray(begin, np.int32)
+    d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+    d_begin = torch.empty(len(begin), dtype=torch.int32, device=dev)
+    base_o, overhead_floats, base_c, occupancy_bytes = bases
+    lib.call('simq_observation_update_sequences', ptr(frames), ctypes.c_int64(words), probs, len(probs), begin.ctypes.data_as(ctypes.c_void_p),
+             len(begin) - 1, ptr(d_probs), ptr(d_begin), ctypes.c_void_p(base_o), ctypes.c_int64(overhead_floats), ctypes.c_void_p(base_c),
+             ctypes.c_int64(occupancy_bytes), ptr(status), stream_ptr(dev))
+
+
+def _enqueue_sequences(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps, map_index):
+    """observation_update_sequences without its status read-back: returns the int32 device tensor of one word per frame in the order
+    of the launches, and the position of every frame of the call in it."""
+    depth, ids, geometries, id_ranges, P = _checked_frames(depth, ids, geometries, id_ranges, 'observation_update_sequences')
+    try:
+        index = [int(k) for k in map_index]
+    except TypeError:
+        raise ValueError('map_index holds the map of each frame, got %s' % type(map_index).__name__) from None
+    if len(index) != P:
+        raise ValueError('map_index holds the map of each frame: %d entries for %d frames' % (len(index), P))
+    dev = _batch.device('observation maps')
+    overhead_maps = _maps(overhead_maps, torch.float32, dev, 'overhead_maps')
+    occupancy_maps = _maps(occupancy_maps, torch.uint8, dev, 'occupancy_maps')
+    G = len(overhead_maps)
+    if G < 1 or len(occupancy_maps) != G:
+        raise ValueError('%d overhead maps and %d occupancy maps: one pair per map' % (G, len(occupancy_maps)))
+    if min(index) < 0 or max(index) >= G:
+        raise ValueError('map_index names maps in 0 .. %d, got %s' % (G - 1, [k for k in index if k < 0 or k >= G][:8]))
+    for k, (om, cm) in enumerate(zip(overhead_maps, occupancy_maps)):
+        if tuple(om.shape) != tuple(cm.shape):
+            raise ValueError('map %d: an overhead map of %s but an occupancy map of %s' % (k, tuple(om.shape), tuple(cm.shape)))
+    parts, words, tables, offsets = _layout(depth, ids, geometries)
+    frames, _ = _batch.pack(parts, torch.int32, dev)
+    bases = _map_bases(overhead_maps, occupancy_maps)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    where, at = np.empty(P, np.int64), 0
+    for mine, begin in sequence_launches(index):
+        probs = (ObservationProblem * len(mine))()
+        for q, p in zip(probs, mine.tolist()):
+            om, cm = overhead_maps[index[p]], occupancy_maps[index[p]]
+            _describe(q, geometries[p], id_ranges[p], offsets[p], tables[id(geometries[p])], depth[p].shape, (om.data_ptr() - bases[0]) // 4,
+                      cm.data_ptr() - bases[2], om.shape)
+        call_sequences(frames, words, probs, begin, bases, status[at:at + len(mine)], dev)
+        where[mine] = at + np.arange(len(mine))
+        at += len(mine)
+    return status, where
+
+
+def observation_update_sequences(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps, map_index):
+    """Mapper.update for P camera frames of G pairs of maps, P >= G, in one launch: what successive observation_update calls -- the
+    frames of each map one after the other in the order given -- leave in the maps, bit for bit (include/simq.h: the last frame that
+    reaches an overhead pixel decides it, an occupancy byte is the OR over the frames).
+
+    depth, ids, geometries, id_ranges: as observation_update takes them, one per frame.  overhead_maps, occupancy_maps: one
+    [G, rows, cols] device tensor or G 2-D device tensors each, as there.  map_index: the map pair of each frame, 0 .. G - 1.  The frames
+    of one map are applied in the order they are given; frames of different maps may interleave (they are ordered by map with a stable
+    sort).  A map with more than MAX_SEQUENCE frames is finished by successive launches.  A map no frame names is left alone.
+
+    Returns (overhead_maps, occupancy_maps) as given, after one status read-back.  Raises ValueError and SimqError as observation_update
+    does; a frame that holds a point that is not finite is skipped -- the other frames of its map are applied as if it were absent --
+    and named, by its position in the call, in the SimqError raised after every other frame has been applied."""
+    status, where = _enqueue_sequences(depth, ids, geometries, id_ranges, overhead_maps, occupancy_maps, map_index)
+    codes = status.cpu().numpy()[where]                                                  # the one read-back; in the caller's order
+    bad = np.flatnonzero(codes != 0)
+    if bad.size:
+        if (codes[bad] == 1).all():
+            raise SimqError('simq_observation_update_sequences: %d frame(s) hold a point that is not finite (a depth buffer outside what the '
+                            'near and far planes allow); they are skipped, every other frame is applied (frames %s)' % (bad.size, bad[:8].tolist()))
+        raise SimqError('simq_observation_update_sequences: %d frame(s) failed (status %s at frames %s)'
+                        % (bad.size, codes[bad][:8].tolist(), bad[:8].tolist()))
     return overhead_maps, occupancy_maps
 
 
