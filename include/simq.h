@@ -744,6 +744,62 @@ int simq_grid_waypoints(const uint8_t* d_grids, int64_t grids_bytes, const int32
                         simq_grid_waypoint_problem* d_problems, int32_t* d_ways, int64_t way_pairs, int32_t* d_counts,
                         int32_t* d_status, void* stream);
 
+/* ---- actions to waypoints (envs.py:856-902 Robot.store_new_action; envs.py:2477-2504 OccupancyMap.shortest_path) -------------------
+ * The rule.  Per robot: an action a, its position (x, y) and heading (float64), its type and its mapper.  Constants: W = 96
+ * (Mapper.LOCAL_MAP_PIXEL_WIDTH), CUBE_WIDTH = 0.044 (envs.py:25), END_EFFECTOR_LOCATION = BACKPACK_OFFSET + BASE_LENGTH of the
+ * robot's class (envs.py:804-807, 1059-1060, 1279-1280), C_out = NUM_OUTPUT_CHANNELS of the class.
+ *   1. action = unravel_index(a, (C_out, W, W)) = (channel, row, col); a outside [0, C_out W W) is refused.
+ *   2. (dx, dy) = pixel_indices_to_position(row, col, (W, W)); dist = sqrt(dx**2 + dy**2); theta = heading + atan2(-dx, dy);
+ *      target = (x + dist cos(theta), y + dist sin(theta), 0).
+ *   3. waypoints = OccupancyMap.shortest_path(position, target) when use_shortest_path_movement is set, else [position, target].
+ *      shortest_path: both positions to pixels; the straight-line test on the thin map; otherwise both pixels snapped to their closest
+ *      free cells, SPFA's path (simq_grid_paths' rules), simplified by the exact rule of simq_grid_waypoints with tolerance 1, pruned,
+ *      reversed; pixels back to positions (z = 0) with the two given positions at the ends; fewer than two waypoints: the two
+ *      positions alone.
+ *   4. headings[0] = heading; headings[k] = restrict_heading_range(atan2(dy_k, dx_k)) over successive waypoints, where
+ *      restrict_heading_range(h) = (h + pi) % (2 pi) - pi with Python's float %.
+ *   5. signed_dist = distance(wp[-2], wp[-1]) - (END_EFFECTOR_LOCATION + CUBE_WIDTH / 2); the last waypoint becomes
+ *      wp[-2] + signed_dist (cos, sin)(headings[-1]), z = 0.
+ *   6. With more than two waypoints and signed_dist < 0: wp[-2] = wp[-1] and headings[-2] is formed again from wp[-3] to wp[-2].
+ * Every float64 above is CPython's math on the host: `** 2` is libm's pow, and the library has no trigonometry.  What this entry
+ * point does is the integer and fp32 part of step 3, from the two pixels to the waypoint pixels, in ONE launch: one wavefront per
+ * problem runs the straight-line test, the snap, the search, the walk, the simplification and the pruning, with the dense path in LDS
+ * (no path buffer, no path capacity).  simq_grid_paths followed by simq_grid_waypoints (tolerance 1) gives the same waypoints, counts
+ * and end pixels.
+ * Inputs lie where a caller keeps them: three bases -- d_cspace (uint8 configuration spaces, free where != 0), d_thin (uint8 thin
+ * maps; NULL when no problem tests the line) and d_closest (int32 [2][rows][cols] blocks; NULL when no problem snaps) -- each with its
+ * extent, and per problem an element offset into each.  Several problems may share a map.  The window (box_*) is the caller's, as
+ * for simq_grid_paths: it must hold every free cell, the kernel's pass over the grid gives status 2 when one lies outside, and
+ * (box_rows + 2) * (box_cols + 2) <= SIMQ_GRID_PATH_MAX_BOX_CELLS.
+ * Upstream status: d_upstream (n_upstream int32 words on the device; NULL with 0) as for simq_grid_distance_images_snapped: a problem
+ * with upstream >= 0 whose word is not 0 gets that word as its status and count 0; nothing else of it is read or written.
+ * Outputs per problem: int32 (i, j) waypoint pixels, source first, at pair way_offset of d_ways, at most way_capacity pairs;
+ * d_counts[p] (1, the target alone, for an unreachable or blocked target, a blocked source and target == source: the caller applies
+ * the reference's len(path) < 2); d_endpoints[4 p .. 4 p + 4), the pixels the search used (as given when the line is clear).
+ * `problems`: host array of n descriptors, validated here before anything is copied or launched (rows, cols >= 1, rows * cols <
+ * SIMQ_GRID_MAX_CELLS; both pixels inside the grid; the window inside the grid and under the cap; way_capacity >= 1; every input and
+ * the waypoint range inside the declared extent of its base; upstream -1 or below n_upstream; no two waypoint ranges overlapping;
+ * d_problems, d_ways, d_counts, d_endpoints and d_status disjoint from each other and from every input; 8-byte alignment of d_problems
+ * and d_ways, 4 of the other int32 buffers) and copied to d_problems (n descriptors) on `stream`.
+ * d_status[n] (int32): 0 = traced, 1 = straight line clear (count 0), 2 = bad descriptor, pixel, snapped pixel or window (the kernel
+ * checks again and writes nothing else), 3 = way_capacity too small: d_counts[p] holds the need and nothing is written past the
+ * capacity, 4 = a loop passed its bound (cannot happen); or the upstream word. */
+typedef struct simq_action_waypoint_problem {
+    int64_t cspace_offset;      /* byte offset of the problem's [rows][cols] uint8 configuration space in d_cspace */
+    int64_t thin_offset;        /* byte offset of its [rows][cols] uint8 thin map in d_thin, or -1 (no straight-line test) */
+    int64_t closest_offset;     /* int32 offset of its [2][rows][cols] closest cells in d_closest, or -1 (no snap) */
+    int64_t way_offset;         /* pair offset of its waypoints in d_ways */
+    int32_t way_capacity;       /* pairs */
+    int32_t rows, cols;
+    int32_t src_i, src_j, tgt_i, tgt_j;
+    int32_t box_i0, box_j0, box_rows, box_cols;
+    int32_t upstream;           /* index of its word in d_upstream, or -1 */
+} simq_action_waypoint_problem;
+int simq_action_waypoints(const uint8_t* d_cspace, int64_t cspace_bytes, const uint8_t* d_thin, int64_t thin_bytes,
+                          const int32_t* d_closest, int64_t closest_ints, const simq_action_waypoint_problem* problems, int n,
+                          simq_action_waypoint_problem* d_problems, int32_t* d_ways, int64_t way_pairs, int32_t* d_counts,
+                          int32_t* d_endpoints, const int32_t* d_upstream, int n_upstream, int32_t* d_status, void* stream);
+
 /* ---- shortest-path distance queries: the point form of the distance images (envs.py:2506-2511 OccupancyMap.shortest_path_distance,
  * reached through Mapper.distance_to_receptacle, envs.py:2189-2194, by every partial reward; shortest_paths.pyx:150-158
  * GridGraph.shortest_path_distance) ------------------------------------------------------------------------------------------------

@@ -39,6 +39,8 @@ _LAZY = {
     'shortest_paths': ('.waypoints', 'shortest_paths'),
     'grid_waypoints': ('.waypoints', 'grid_waypoints'),
     'approximate_polygon_exact': ('.waypoints', 'approximate_polygon_exact'),
+    'store_new_actions': ('.actions', 'store_new_actions'),
+    'NewActions': ('.actions', 'NewActions'),
     'grid_distance_queries': ('.grid_queries', 'grid_distance_queries'),
     'shortest_path_distances': ('.grid_queries', 'shortest_path_distances'),
     'distances_to_receptacle': ('.grid_queries', 'distances_to_receptacle'),

@@ -178,6 +178,8 @@ _SIGS = {
                                 c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     'simq_grid_waypoints': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p]),
+    'simq_action_waypoints': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'simq_grid_distance_queries': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                            c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     'simq_local_state_desc_bytes': (c_int64, [c_int, c_int, c_int, c_int]),

@@ -39,11 +39,19 @@ SEG_VALUES = {                         # envs.py:1880-1889 Camera.SEG_VALUES
 }
 
 
-def get_robot_radius(robot_type):
-    """The class's RADIUS: envs.py:807-808 (Robot), 1060-1061 (PushingRobot), 1280-1281 (ThrowingRobot)."""
+CUBE_WIDTH = 0.044                     # envs.py:25 VectorEnv.CUBE_WIDTH
+
+
+def get_end_effector_location(robot_type):
+    """The class's END_EFFECTOR_LOCATION: envs.py:807 (Robot), 1060 (PushingRobot), 1280 (ThrowingRobot)."""
     if robot_type not in ROBOT_BASE_LENGTH:
         raise Exception(robot_type)
-    end_effector_location = ROBOT_BACKPACK_OFFSET + ROBOT_BASE_LENGTH[robot_type]
+    return ROBOT_BACKPACK_OFFSET + ROBOT_BASE_LENGTH[robot_type]
+
+
+def get_robot_radius(robot_type):
+    """The class's RADIUS: envs.py:807-808 (Robot), 1060-1061 (PushingRobot), 1280-1281 (ThrowingRobot)."""
+    end_effector_location = get_end_effector_location(robot_type)
     return math.sqrt(ROBOT_HALF_WIDTH**2 + end_effector_location**2)
 
 

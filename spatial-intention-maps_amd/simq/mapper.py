@@ -13,7 +13,8 @@ object owns, and the two calls run the batched operators of this package as one 
 Each stage is one launch however many mappers are named, reads the tensors of the stage before it where they lie, and leaves its
 status words on the device; the call reads them back once, at its end.  What lets the read-back wait is the upstream status of
 the snapped distance images (include/simq.h): a mapper whose configuration space has no free cell -- its closest cells are undefined
--- is not searched.  Douglas-Peucker and ``store_new_action`` stay on the host (DESIGN.md sections 13 and 17).
+-- is not searched.  ``store_new_actions`` is Robot.store_new_action for the deciding robots: one simq_action_waypoints launch on the same
+tensors, the float64 arithmetic on the host.  Douglas-Peucker by scikit-image stays on the host (section 13).
 """
 import collections
 import collections.abc
@@ -530,6 +531,7 @@ class BatchedMapper:
         self.num_channels = len(self.channels)
         self.mask_bank = np.stack(bank)
         self._plans = {}                                   # what get_states' array form needs of a `mappers` tuple, made once
+        self._windows = {}                                 # store_new_actions' per-mapper constants, the room masks' boxes among them
         cells = [r * c for r, c in self.shapes]
         self._at = np.concatenate([[0], np.cumsum(cells)]).tolist()                       # cell offset of mapper m's maps; [M]: all cells
         self._pending = [[] for _ in range(M)]             # the deferred frames of every mapper in capture order (_Deferred)
@@ -1149,6 +1151,81 @@ class BatchedMapper:
         self._nothing_pending(ms, 'shortest_paths')
         return shortest_paths(self.configuration_space, self.cspace_thin, self.closest_cspace_indices, source_positions, target_positions,
                               ms, simplify)
+
+    # ---- Robot.store_new_action on the stored tensors --------------------------------------------------------------------------
+    def _action_constants(self):
+        """What store_new_actions needs of every mapper and of no call, as arrays [M], made once: its robot's type, output channels
+        and END_EFFECTOR_LOCATION + CUBE_WIDTH / 2; its map's shape and cell offset; and the window simq_action_waypoints searches,
+        the bounding box of its room mask, a host constant per room -- the configuration space is zero outside the mask
+        (envs.py:2453), so the box holds every free cell."""
+        if not self._windows:
+            from .actions import constants_of, free_box
+            types = [t for env in self.robot_types for t in env]
+            boxes = {}
+            for e in range(self.num_envs):
+                key = (self.room_widths[e], self.room_lengths[e])
+                if key not in boxes:
+                    boxes[key] = free_box(room_mask(*key))
+            channels, reach = constants_of(types)
+            self._windows = dict(
+                types=np.asarray(types), channels=channels, reach=reach, rows=np.asarray([s[0] for s in self.shapes], np.int32),
+                cols=np.asarray([s[1] for s in self.shapes], np.int32), at=np.asarray(self._at[:-1], np.int64),
+                box=np.asarray([boxes[(self.room_widths[e], self.room_lengths[e])] for e in self.env_of], np.int32))
+        return self._windows
+
+    def store_new_actions(self, actions, robots, mappers=None, use_shortest_path_movement=True):
+        """Robot.store_new_action (envs.py:856-902) of the named mappers' robots (all when omitted) in one call: actions[p] is the
+        integer step_many returned for the robot of mapper mappers[p]; robots is get_states' argument in either form (only position
+        and heading of the named robots are read); robot types and maps are the object's.  Returns simq.actions.NewActions: arrays,
+        whose as_lists() gives per robot the reference's action, target_end_effector_position, waypoint_positions and
+        waypoint_headings bit for bit.
+
+        One simq_action_waypoints launch on the maps where they lie, windowed by the room mask's box, with `occupancy_status` as its
+        upstream status, and one read-back (one more round only for a robot with more than actions.WAY_CAPACITY waypoints); with
+        use_shortest_path_movement=False nothing is launched.  Raises ValueError for a wrong argument, without a device; SimqError
+        for pending deferred frames, and -- after the call has completed -- naming the mappers whose problem ended with another status
+        than traced or straight, or whose word of `occupancy_status` is not 0 (NOT_UPDATED: no update since the last reset, 1: a
+        configuration space without a free cell)."""
+        from . import actions as act
+        ms = self._mappers(mappers)
+        self._nothing_pending(ms, 'store_new_actions')
+        P, fixed = len(ms), self._action_constants()
+        if isinstance(robots, RobotArrays):
+            if robots.num_mappers != self.num_mappers:
+                raise ValueError('the RobotArrays hold %d mappers, the object has %d' % (robots.num_mappers, self.num_mappers))
+            given, positions, headings = None, robots.position[ms], robots.heading[ms]
+        else:
+            own = [(self.env_of[m], m - self.env_begin[self.env_of[m]]) for m in ms]
+            states = self._robots(robots, sorted(set(e for e, _ in own)))
+            given = [states[e][r].position for e, r in own]
+            positions = np.asarray([(p[0], p[1]) for p in given], np.float64).reshape(P, 2)
+            headings = np.asarray([states[e][r].heading for e, r in own], np.float64)
+        positions, headings, actions, _, _ = act._as_inputs(positions, headings, actions, fixed['types'][ms].tolist())
+        action, targets = act._targets(actions, positions, headings, fixed['channels'][ms])
+        rows, cols, reach = fixed['rows'][ms], fixed['cols'][ms], fixed['reach'][ms]
+        if not use_shortest_path_movement:
+            none = np.zeros(P, np.int64)
+            return act._finish(action, positions, headings, targets, reach, np.full(P, act.STRAIGHT), none, np.zeros((0, 2), np.int64), rows,
+                               cols, given)
+        probs = np.zeros(P, act.ACTION_PROBLEM)
+        probs['rows'], probs['cols'] = rows, cols
+        probs['src_i'], probs['src_j'] = local_maps.pixel_indices_many(positions[:, 0], positions[:, 1], (rows, cols))
+        probs['tgt_i'], probs['tgt_j'] = local_maps.pixel_indices_many(targets[:, 0], targets[:, 1], (rows, cols))
+        at = fixed['at'][ms]
+        probs['cspace_offset'], probs['thin_offset'], probs['closest_offset'], probs['upstream'] = at, at, 2 * at, ms
+        probs['box_i0'], probs['box_j0'], probs['box_rows'], probs['box_cols'] = fixed['box'][ms].T
+        if act.search is None and self.device is None:
+            self._allocate()
+        bases = None if self.device is None else (self._cspace, self._thin, self._closest)
+        status, counts, _, pixels, words = act.run_problems(probs, bases, None if self.device is None else self.occupancy_status,
+                                                            what='BatchedMapper.store_new_actions')
+        bad = np.flatnonzero((words != 0) | ((status != act.TRACED) & (status != act.STRAIGHT)))
+        codes = status[bad]
+        if bad.size:
+            raise SimqError('BatchedMapper.store_new_actions: no waypoints for mapper(s) %s (simq_action_waypoints status %s; %d: no update '
+                            'since the last reset, 1 from the occupancy maps: a configuration space without a free cell, 2: a bad pixel or '
+                            'window); every other robot of the call was computed' % (self._named(bad.tolist(), ms), codes[:8].tolist(), NOT_UPDATED))
+        return act._finish(action, positions, headings, targets, reach, status, counts, pixels, rows, cols, given)
 
     def distances_to_receptacle(self, positions, mappers=None, shortest_path=True):
         """Mapper.distance_to_receptacle (envs.py:2189-2194) for the named mappers' position lists: simq.distances_to_receptacle on this
