@@ -1,5 +1,5 @@
-// What the C entry points of the batched map operators share (grid_paths, grid_queries, grid_waypoints, local_maps, intention_maps, occupancy_maps,
-// observation_maps, visualization): the checks that keep a bad descriptor from becoming a fault, the descriptor upload, and the
+// What the C entry points of the batched map operators share (grid_paths, grid_queries, grid_waypoints, action_waypoints, local_maps, intention_maps,
+// occupancy_maps, observation_maps, visualization): the checks that keep a bad descriptor from becoming a fault, the descriptor upload, and the
 // NaN-keeping reduction of two of the kernels.  Nothing here knows an operator.  The helpers report -- a bool, an index, a pair -- and
 // the entry point words the refusal: every SIMQ_REQUIRE and its text stay with the operator.
 #pragma once

@@ -15,6 +15,7 @@
 // image is never `__restrict__`, so the compiler keeps loads and stores to it in program order across the fences.
 #include "batch_abi.h"
 #include "grid_relax.h"
+#include "grid_spfa.h"
 #include "../../include/simq.h"
 
 #include <vector>
@@ -24,15 +25,7 @@ namespace simq {
 namespace {
 
 using namespace grid_relax;
-
-// closest[:, i, j] of an int32 [2][R][C] block; false when it names no cell of the grid
-__device__ __forceinline__ bool snap(const int32_t* __restrict__ cl, int R, int C, int& i, int& j) {
-    const int a = cl[i * C + j], b = cl[R * C + i * C + j];
-    if (a < 0 || a >= R || b < 0 || b >= C) return false;
-    i = a;
-    j = b;
-    return true;
-}
+using grid_spfa::snap;
 
 __global__ void __launch_bounds__(kLanes) grid_queries_kernel(const uint8_t* __restrict__ grids, const int32_t* __restrict__ closest,
                                                               const simq_grid_query_problem* __restrict__ probs,

@@ -2,22 +2,11 @@
 //   grid_paths_kernel        GridGraph._spfa + the walk of GridGraph.shortest_path               shortest_paths.pyx:69-114, 126-137
 //                            (+ the front half of OccupancyMap.shortest_path: straight-line test, closest free cells   envs.py:2477-2490)
 //
-// Exactness.  SPFA's distances are a fixed point that any update order reaches (grid_paths.hip); its parents are not: where two paths
-// tie, the parent is the vertex whose relaxation was accepted last, and that follows the order of the queue, including the exchange
-// of the newest entry with the front.  So the search itself is emulated, one problem per wavefront, with the problems as the
-// parallel axis.  The rules are stated in include/simq.h; what is parallel inside one pop and what is not:
-//   * the eight relaxations of a pop read d[u] (fixed during the pop: u is not its own neighbour) and eight distinct cells, so lanes
-//     0 .. 7 take one edge each: load the neighbour, form fl32(d[u] + w), compare, store distance and parent.  Two ballots give the
-//     accepted edges and those that push.
-//   * the queue is sequential.  A uniform loop walks the accepted edges in the reference's order; it keeps the front vertex and the
-//     front's distance in registers, lowers that distance at the edge that relaxes the front, and decides each push's exchange against
-//     the value as it stands at that edge -- an exchange decided against the front's distance before or after the whole pop is
-//     sometimes the other way round.
-// State per cell of the caller's window plus a blocked one-cell halo (so no edge needs a bounds test), in LDS: fp32 distance, a
-// 16-bit ring entry, the parent as a direction byte, a flag byte (bit 0 free, bit 1 queued).  The ring is laid out for window cells + 1
-// entries and uses free cells + 1 of them: at most every vertex is queued at once, and slot numbers only ever grow, so positions wrap
-// (a cluttered grid pushes 1 - 7 % more often than it has vertices).
+// The search, the stages in front of it and why the search itself has to be emulated are grid_spfa.h's, shared with
+// action_waypoints.hip.  What is this kernel's own: the walk from the target into the caller's path buffer under its capacity, and
+// the optional parent and distance images over the full grid.
 #include "batch_abi.h"
+#include "grid_spfa.h"
 #include "../../include/simq.h"
 
 #include <algorithm>
@@ -27,21 +16,7 @@ namespace simq {
 
 namespace {
 
-constexpr int kLanes = 64;
-constexpr float kSqrt2 = 1.41421353816986083984375f;   // float32(np.sqrt(2)), shortest_paths.pyx:31
-constexpr int kNoParent = 0xFF;
-constexpr int kLdsBudget = 160 * 1024;
-
-// direction k of shortest_paths.pyx:30
-__device__ __forceinline__ int dir_di(int k) { return k < 2 ? 0 : (k < 5 ? -1 : 1); }
-__device__ __forceinline__ int dir_dj(int k) { return k < 2 ? 2 * k - 1 : (k - 2) % 3 - 1; }
-__device__ __forceinline__ float dir_w(int k) { return (0xB4 >> k) & 1 ? kSqrt2 : 1.f; }   // diagonals: 2, 4, 5, 7
-
-__host__ __device__ inline int64_t lds_bytes(int box_rows, int box_cols) {
-    const int64_t n = (int64_t)(box_rows + 2) * (box_cols + 2);
-    const int64_t q = (int64_t)box_rows * box_cols + 1;
-    return 4 * n + 2 * ((q + 1) & ~(int64_t)1) + 2 * n;
-}
+using namespace grid_spfa;
 
 __device__ __forceinline__ bool descriptor_ok(const simq_grid_path_problem& p, const int32_t* closest, const int32_t* parents,
                                               const float* dist) {
@@ -76,17 +51,7 @@ __global__ void __launch_bounds__(kLanes) grid_paths_kernel(const uint8_t* __res
     // ---- OccupancyMap.shortest_path's straight-line test, on the pixels as given (envs.py:2483-2485)
     if (p.thin_offset >= 0) {
         const uint8_t* thin = grids + p.thin_offset;
-        const int dr = abs(ti - si), dc = abs(tj - sj);
-        const int sr = ti > si ? 1 : -1, sc = tj > sj ? 1 : -1;
-        const int nn = max(dr, dc), mm = min(dr, dc);
-        bool hit = false;
-        for (int i = lane; i <= nn; i += kLanes) {
-            const int minor = nn > 0 ? (2 * mm * i + nn) / (2 * nn) : 0;
-            const int r = dr > dc ? si + sr * i : si + sr * minor;
-            const int c = dr > dc ? sj + sc * minor : sj + sc * i;
-            hit |= thin[r * C + c] != 1;
-        }
-        if (!__any(hit)) {
+        if (!line_hits([&](int r, int c) { return thin[r * C + c] != 1; }, si, sj, ti, tj, lane)) {
             if (lane == 0) {
                 status[blockIdx.x] = 1;
                 lengths[blockIdx.x] = 0;
@@ -99,128 +64,27 @@ __global__ void __launch_bounds__(kLanes) grid_paths_kernel(const uint8_t* __res
     // ---- OccupancyMap._closest_valid_cspace_indices (envs.py:2488-2489, 2522-2523)
     if (p.closest_offset >= 0) {
         const int32_t* cl = closest + p.closest_offset;
-        const int a = cl[si * C + sj], b = cl[n + si * C + sj], c = cl[ti * C + tj], d = cl[n + ti * C + tj];
-        if (a < 0 || a >= R || b < 0 || b >= C || c < 0 || c >= R || d < 0 || d >= C) {
-            if (lane == 0) status[blockIdx.x] = 2;
-            return;
-        }
-        si = a; sj = b; ti = c; tj = d;
-    }
-
-    // ---- every free cell must lie inside the declared window: one pass over the grid, 16 bytes at a time where aligned
-    const int bi0 = p.box_i0, bj0 = p.box_j0, bh = p.box_rows, bw = p.box_cols;
-    {
-        bool outside = false;
-        const int lead = min(n, (int)((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15));
-        const int chunks = (n - lead) / 16;
-        auto check = [&](int idx, int count) {
-            int r = idx / C, c = idx - r * C;
-            for (int t = 0; t < count; ++t) {
-                if (g[idx + t] != 0 && (r < bi0 || r >= bi0 + bh || c < bj0 || c >= bj0 + bw)) outside = true;
-                if (++c == C) { c = 0; ++r; }
-            }
-        };
-        if (lane == 0 && lead > 0) check(0, lead);
-        if (lane == 1 && lead + 16 * chunks < n) check(lead + 16 * chunks, n - lead - 16 * chunks);
-        const uint4* g16 = reinterpret_cast<const uint4*>(g + lead);
-        for (int q = lane; q < chunks; q += kLanes) {
-            const uint4 w = g16[q];
-            if ((w.x | w.y | w.z | w.w) != 0u) check(lead + 16 * q, 16);
-        }
-        if (__any(outside)) {
+        if (!snap(cl, R, C, si, sj) || !snap(cl, R, C, ti, tj)) {
             if (lane == 0) status[blockIdx.x] = 2;
             return;
         }
     }
 
-    // ---- LDS state over the window + halo
-    const int W = bw + 2, N = (bh + 2) * W;
-    float* dist = reinterpret_cast<float*>(smem);
-    uint16_t* ring = reinterpret_cast<uint16_t*>(smem + 4 * (int64_t)N);
-    uint8_t* par = reinterpret_cast<uint8_t*>(smem + 4 * (int64_t)N + 2 * ((bh * bw + 2) & ~1));
-    uint8_t* flg = par + N;
+    // ---- every free cell must lie inside the declared window
+    const Window box = {p.box_i0, p.box_j0, p.box_rows, p.box_cols};
+    if (!free_cells_inside(g, n, C, box, lane)) {
+        if (lane == 0) status[blockIdx.x] = 2;
+        return;
+    }
+
+    // ---- the search over the window + halo, in LDS
+    const Lds lds(smem, box);
     const float inf = 2.f * (float)n;                    // self.inf = 2 * max_num_verts (exact: < 2^24)
-    int vertices = 0;
-    for (int l = lane; l < N; l += kLanes) {
-        const int li = l / W, lj = l - li * W;
-        const bool inner = li >= 1 && li <= bh && lj >= 1 && lj <= bw;
-        const bool is_free = inner && g[(bi0 + li - 1) * C + (bj0 + lj - 1)] != 0;
-        dist[l] = inf;
-        par[l] = kNoParent;
-        flg[l] = is_free ? 1 : 0;
-        vertices += is_free ? 1 : 0;
-    }
-    for (int o = kLanes / 2; o >= 1; o >>= 1) vertices += __shfl_xor(vertices, o, kLanes);
-    const int Q = vertices + 1;                          // ring slots: at most every vertex is queued at once
-    __syncthreads();
-    const bool src_in = si >= bi0 && si < bi0 + bh && sj >= bj0 && sj < bj0 + bw;
-    const bool tgt_in = ti >= bi0 && ti < bi0 + bh && tj >= bj0 && tj < bj0 + bw;
-    const int s_l = src_in ? (si - bi0 + 1) * W + (sj - bj0 + 1) : -1;
-    const bool search = src_in && flg[s_l] != 0;         // edges leave a free cell only: a blocked source relaxes nothing
-    int st = 0;
-    if (src_in && lane == 0) dist[s_l] = 0.f;
-
-    if (search) {
-        const int k = lane & 7;
-        const int my_off = dir_di(k) * W + dir_dj(k);
-        const float my_w = dir_w(k);
-        int head = 0, tail = 1;
-        int hp = 1 % Q, tp = 1 % Q;                      // ring positions of slot head + 1 (the front) and of slot tail
-        int f = s_l;                                     // the front vertex (slot head + 1), -1 when nothing is queued
-        float df = 0.f;                                  // ... and its distance as it stands
-        if (lane == 0) { ring[hp] = (uint16_t)s_l; flg[s_l] = 3; }
-        const int64_t pop_cap = 64 * (int64_t)(Q - 1) + 64;
-        int64_t pops = 0;
-        __syncthreads();
-        while (head < tail) {
-            if (++pops > pop_cap) { st = 4; break; }
-            ++head;
-            const int u = f;
-            const float du = df;
-            hp = hp + 1 == Q ? 0 : hp + 1;
-            int nf = -1;
-            float ndf = 0.f;
-            if (head < tail) { nf = ring[hp]; ndf = dist[nf]; }
-            const int v = u + my_off;
-            const float dv = dist[v];
-            const unsigned fv = flg[v];
-            const float nw = du + my_w;
-            const bool acc = (fv & 1u) && nw < dv;
-            const unsigned accepted = (unsigned)__ballot(acc) & 0xFFu;
-            const unsigned pushing = (unsigned)__ballot(acc && !(fv & 2u)) & 0xFFu;
-            if (lane < 8 && acc) {
-                dist[v] = nw;
-                par[v] = (uint8_t)k;
-                if (!(fv & 2u)) flg[v] = 3;
-            }
-            if (lane == 0) flg[u] = 1;                   // in_queue[u] = 0
-            f = nf;
-            df = ndf;
-            for (unsigned m = accepted; m != 0u; m &= m - 1u) {
-                const int kk = __ffs(m) - 1;
-                const int vk = u + dir_di(kk) * W + dir_dj(kk);
-                const float nk = du + dir_w(kk);
-                if (vk == f) df = nk;                    // the front is a neighbour of u: later pushes of this pop see it lowered
-                if ((pushing >> kk) & 1u) {
-                    ++tail;
-                    tp = tp + 1 == Q ? 0 : tp + 1;
-                    if (head + 1 == tail) {              // the only one queued: both sides of the comparison are this slot
-                        if (lane == 0) ring[tp] = (uint16_t)vk;
-                        f = vk;
-                        df = nk;
-                    } else if (nk < df) {
-                        if (lane == 0) { ring[tp] = (uint16_t)f; ring[hp] = (uint16_t)vk; }
-                        f = vk;
-                        df = nk;
-                    } else if (lane == 0) {
-                        ring[tp] = (uint16_t)vk;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
+    const bool tgt_in = box.holds(ti, tj);
+    const int s_l = box.holds(si, sj) ? lds.index(box, si, sj) : -1;
+    const int vertices = init_window<false>(lds, g, C, box, s_l, inf, lane);
+    const bool searched = s_l >= 0 && lds.flg[s_l] != 0; // edges leave a free cell only: a blocked source relaxes nothing
+    int st = searched ? search<false>(lds, s_l, vertices + 1, lane) : 0;
 
     // ---- the walk from the target (shortest_paths.pyx:126-137)
     if (lane == 0) {
@@ -228,15 +92,15 @@ __global__ void __launch_bounds__(kLanes) grid_paths_kernel(const uint8_t* __res
         int len = 1;
         path[0] = ti;
         path[1] = tj;
-        if (search && tgt_in) {
+        if (searched && tgt_in) {
             int i = ti, j = tj;
-            int v = (ti - bi0 + 1) * W + (tj - bj0 + 1);
-            while (v != s_l && len <= N) {
-                const int pk = par[v];
+            int v = lds.index(box, ti, tj);
+            while (v != s_l && len <= lds.N) {
+                const int pk = lds.par[v];
                 if (pk == kNoParent) break;
                 i -= dir_di(pk);
                 j -= dir_dj(pk);
-                v -= dir_di(pk) * W + dir_dj(pk);
+                v -= dir_di(pk) * lds.W + dir_dj(pk);
                 if (len < p.path_capacity) { path[2 * len] = i; path[2 * len + 1] = j; }
                 ++len;
             }
@@ -253,15 +117,14 @@ __global__ void __launch_bounds__(kLanes) grid_paths_kernel(const uint8_t* __res
         int32_t* po = p.parents_offset >= 0 ? parents_out + p.parents_offset : nullptr;
         float* dout = p.dist_offset >= 0 ? dist_out + p.dist_offset : nullptr;
         for (int r = 0; r < R; ++r) {
-            const bool row_in = r >= bi0 && r < bi0 + bh;
             for (int c = lane; c < C; c += kLanes) {
                 int32_t pv = -1;
                 float x = r == si && c == sj ? 0.f : -1.f;
-                if (row_in && c >= bj0 && c < bj0 + bw) {
-                    const int l = (r - bi0 + 1) * W + (c - bj0 + 1);
-                    const int pk = par[l];
+                if (box.holds(r, c)) {
+                    const int l = lds.index(box, r, c);
+                    const int pk = lds.par[l];
                     if (pk != kNoParent) pv = (r - dir_di(pk)) * C + (c - dir_dj(pk));
-                    const float d = dist[l];
+                    const float d = lds.dist[l];
                     x = d == inf ? -1.f : d;
                 }
                 if (po) po[r * C + c] = pv;

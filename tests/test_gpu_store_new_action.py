@@ -158,6 +158,21 @@ def test_long_dense_path_in_one_library_call(S, monkeypatch):
     assert calls == ['simq_grid_paths', 'simq_grid_waypoints'] * 2 and np.array_equal(pair.waypoints[0], want)
 
 
+def test_dense_path_past_one_ballot_of_the_kept_mask(S):
+    """next_kept searches 64 mask words (2 048 points) a ballot and the reversed output carries the ranks from one chunk of 64 words to
+    the next: a dense path longer than that takes the second trip of both loops of csrc/waypoint_rule.h, in both routes."""
+    grid = serpentine(73)
+    s, t = (0, 0), (72, 0)
+    dense = wo.dense_path(wo.spfa(grid, s)[1], s, t)
+    want = so.waypoints(grid, dense)
+    assert len(dense) > 2048 + 64 and 2 < len(want) <= 64
+    got, counts, status, ends = run([grid], [dict(map=0, src=s, tgt=t, capacity=64)])
+    assert status.tolist() == [0] and counts.tolist() == [len(want)] and ends.tolist() == [[0, 0, 72, 0]]
+    assert np.array_equal(got[0], want)
+    pair = S.grid_waypoints([grid], [s], [t])                               # a second round gives the dense path its room
+    assert pair.status.tolist() == [0] and np.array_equal(pair.waypoints[0], want)
+
+
 def test_window_at_the_cap(S):
     grid = np.zeros((100, 200), np.uint8)
     grid[1:99, 1:199] = 1                                                   # 98 x 198 free cells: 20 000 with the halo
