@@ -289,7 +289,8 @@ int simq_comm_reduce_f64(void* comm, double* d_buf, int64_t count, void* stream)
 int simq_forward_sync_null(const simq_plan* plan, int layout_batch, float* d_bnbuf, void* d_workspace, void* stream, const simq_sync* sync);
 
 /* ---- learner pieces of train() (train.py:115-129) -------------------------------------------- */
-/* flat max / first-index argmax over each row of d_q [rows][n]  (train.py:121,124; policies.py:64) */
+/* flat max / first-index argmax over each row of d_q [rows][n]  (train.py:121,124; policies.py:64): tensor.max(1) -- a NaN is the
+ * maximum, the first NaN's index is returned and d_max is NaN */
 int simq_q_argmax(const float* d_q, int rows, int n, int64_t* d_index, float* d_max, void* stream);
 /* d_out[i] = d_q[i][d_index[i]]  (train.py:115,122) */
 int simq_q_gather(const float* d_q, int rows, int n, const int64_t* d_index, float* d_out, void* stream);
@@ -298,7 +299,7 @@ int simq_q_gather(const float* d_q, int rows, int n, const int64_t* d_index, flo
 int simq_scatter_next_values(const float* d_values, const int32_t* d_nonfinal_pos, int n_nonfinal,
                              float* d_next_state_values, int batch, void* stream);
 /* y = r + gamma*v ; td = |q_sa - y| ; loss = mean Huber(delta=1) ; dq = one-hot dLoss/dQ
- * (train.py:115,126-129 and the gradient autograd would deliver to `output`).
+ * (train.py:115,126-129 and the gradient autograd would deliver to `output`).  A NaN difference gives a NaN gradient.
  * grad_scale = 1/global_batch (train.py:129 'mean'; data-parallel ranks pass the GLOBAL batch).
  * d_out4: {sum Huber, sum |td|, unused, unused} over this rank's rows (host divides).       */
 int simq_td_huber(const float* d_q, int batch, int n, const int64_t* d_action, const float* d_reward,
@@ -307,6 +308,7 @@ int simq_td_huber(const float* d_q, int batch, int n, const int64_t* d_action, c
 
 /* ---- clip_grad_norm_ + SGD.step (train.py:133-135,186) ----------------------------------------
  * total_norm = ||g||_2 ; g *= min(1, max_norm/(total_norm+1e-6)) (skipped when max_norm <= 0);
+ * a NaN norm gives a NaN coefficient, an Inf norm 0, as clip_grad_norm_ has them;
  * g += wd*p ; m = first_step ? g : momentum*m + g ; p -= lr*m.
  * d_scratch: >= 16 bytes; receives {double sumsq}.  d_total_norm (may be NULL): 1 float.     */
 int simq_clip_sgd_step(float* d_params, float* d_grads, float* d_momentum, int64_t count,

@@ -82,7 +82,7 @@ __device__ __forceinline__ void inbn_coeff4(const InBn& in, int c, floatx4& sc, 
 // relu(v * sc + sh): the fma / max sequence of bn_apply
 __device__ __forceinline__ floatx4 inbn_apply(floatx4 v, const floatx4& sc, const floatx4& sh) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = fmaxf(__builtin_fmaf(v[c], sc[c], sh[c]), 0.f);
+    for (int c = 0; c < 4; ++c) v[c] = relu_nan(__builtin_fmaf(v[c], sc[c], sh[c]));
     return v;
 }
 // block 0 of a forward consumer commits the layer (mean / invstd / scale / shift for backward, running statistics)

@@ -12,6 +12,17 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 void set_error(const char* fmt, ...);
 
+// The ReLU of every plan: F.relu, which keeps a NaN (fmaxf(NaN, 0) is 0: C's maximum returns the operand that is a number).  Every
+// other input gives what fmaxf(v, 0.f) gave, bit for bit: -0.0, negative values and -Inf give +0.0 (the comparison is true for -0.0,
+// and a bare `v < 0 ? 0 : v` would hand -0.0 on), +Inf stays.  v_cmp_nge_f32 vcc, 0, v ; v_cndmask_b32 v, 0, v, vcc.
+__host__ __device__ __forceinline__ float relu_nan(float v) { return v <= 0.f ? 0.f : v; }
+// d smooth_l1_loss(d, beta = 1) / dd in ATen's form: -1 below -1, 1 above 1, d between -- and a NaN d, which neither comparison takes,
+// stays NaN (fminf(fmaxf(d, -1), 1) made it -1).  Every other d gives what the clamp gave.
+__host__ __device__ __forceinline__ float huber_grad(float d) { return d < -1.f ? -1.f : d > 1.f ? 1.f : d; }
+// (a > 0) of a bf16 activation read as its bits -- a ReLU mask plane: 0x0001 .. 0x7f80, the positive numbers and +Inf.  A NaN selects
+// nothing, as (NaN > 0) is false in the reference's ReLU backward (a signed `(short)h > 0` took the NaNs of positive sign for positive).
+__host__ __device__ __forceinline__ bool bf16_pos(uint16_t h) { return (uint16_t)(h - 1) < 0x7f80; }
+
 // Kernel-selection / tuning / timing-ablation switches.  They never change WHAT is computed (beyond fp32 summation order) and they are
 // not part of the product: libsimq.so is built without SIMQ_ABLATIONS, every SIMQ_TUNE_INT is then its default as a compile-time
 // constant (the environment is not read, the switch's name is not even in the binary) and the ablation instantiations of the

@@ -269,8 +269,8 @@ __global__ void __launch_bounds__(256, (BM * BN <= 96 * 64) ? 5 : (BM * BN <= 96
                 if constexpr (XBN) {
                     const bool ok = (xok[SET] >> ps) & 1u;
                     const float4 sc = *reinterpret_cast<const float4*>(xtab + xch[SET]), sh = *reinterpret_cast<const float4*>(xtab + kCoeffMaxC + xch[SET]);
-                    v.x = ok ? fmaxf(__builtin_fmaf(v.x, sc.x, sh.x), 0.f) : 0.f; v.y = ok ? fmaxf(__builtin_fmaf(v.y, sc.y, sh.y), 0.f) : 0.f;
-                    v.z = ok ? fmaxf(__builtin_fmaf(v.z, sc.z, sh.z), 0.f) : 0.f; v.w = ok ? fmaxf(__builtin_fmaf(v.w, sc.w, sh.w), 0.f) : 0.f;
+                    v.x = ok ? relu_nan(__builtin_fmaf(v.x, sc.x, sh.x)) : 0.f; v.y = ok ? relu_nan(__builtin_fmaf(v.y, sc.y, sh.y)) : 0.f;
+                    v.z = ok ? relu_nan(__builtin_fmaf(v.z, sc.z, sh.z)) : 0.f; v.w = ok ? relu_nan(__builtin_fmaf(v.w, sc.w, sh.w)) : 0.f;
                 }
                 if (BM % 64 == 0 || r < BM) *reinterpret_cast<float4*>(As + r * LDK + ((kq ^ lds_sw(r)) << 2)) = v;
             }

@@ -235,8 +235,8 @@ __global__ void __launch_bounds__(NW * 64, 2) igemm_bf16_img_kernel(const IgemmB
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const float lo = __uint_as_float(rw[k] << 16), hi = __uint_as_float(rw[k] & 0xffff0000u);
-                        const float a = fmaxf(__builtin_fmaf(lo, k < 2 ? s0[2 * k] : s1[2 * k - 4], k < 2 ? h0[2 * k] : h1[2 * k - 4]), 0.f);
-                        const float b = fmaxf(__builtin_fmaf(hi, k < 2 ? s0[2 * k + 1] : s1[2 * k - 3], k < 2 ? h0[2 * k + 1] : h1[2 * k - 3]), 0.f);
+                        const float a = relu_nan(__builtin_fmaf(lo, k < 2 ? s0[2 * k] : s1[2 * k - 4], k < 2 ? h0[2 * k] : h1[2 * k - 4]));
+                        const float b = relu_nan(__builtin_fmaf(hi, k < 2 ? s0[2 * k + 1] : s1[2 * k - 3], k < 2 ? h0[2 * k + 1] : h1[2 * k - 3]));
                         ow[k] = (unsigned)__builtin_bit_cast(uint16_t, (__bf16)a) | ((unsigned)__builtin_bit_cast(uint16_t, (__bf16)b) << 16);
                     }
                     typedef unsigned uintx4 __attribute__((ext_vector_type(4)));

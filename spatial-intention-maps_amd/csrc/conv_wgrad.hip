@@ -188,8 +188,8 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs p) {
                 float4 v = vx[SET][ps];
                 if constexpr (XBN) {
                     const bool ok = (xok[SET] >> ps) & 1u;
-                    v.x = ok ? fmaxf(__builtin_fmaf(v.x, xsc.x, xsh.x), 0.f) : 0.f; v.y = ok ? fmaxf(__builtin_fmaf(v.y, xsc.y, xsh.y), 0.f) : 0.f;
-                    v.z = ok ? fmaxf(__builtin_fmaf(v.z, xsc.z, xsh.z), 0.f) : 0.f; v.w = ok ? fmaxf(__builtin_fmaf(v.w, xsc.w, xsh.w), 0.f) : 0.f;
+                    v.x = ok ? relu_nan(__builtin_fmaf(v.x, xsc.x, xsh.x)) : 0.f; v.y = ok ? relu_nan(__builtin_fmaf(v.y, xsc.y, xsh.y)) : 0.f;
+                    v.z = ok ? relu_nan(__builtin_fmaf(v.z, xsc.z, xsh.z)) : 0.f; v.w = ok ? relu_nan(__builtin_fmaf(v.w, xsc.w, xsh.w)) : 0.f;
                 }
                 if (X_F4 % 256 == 0 || idx < X_F4) *reinterpret_cast<float4*>(Xs + idx * 4) = v;
             }

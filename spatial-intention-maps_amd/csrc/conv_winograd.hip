@@ -244,7 +244,7 @@ __global__ void __launch_bounds__(256) wino_output_kernel(const float* __restric
                 v = v * sc + sh;
                 const size_t o = ((size_t)(b * H + 2 * ty + i) * W + 2 * tx + j) * C + n;
                 if (p.addend) v += *reinterpret_cast<const floatx4*>(p.addend + o);
-                if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                if (p.relu) { v[0] = relu_nan(v[0]); v[1] = relu_nan(v[1]); v[2] = relu_nan(v[2]); v[3] = relu_nan(v[3]); }
                 *reinterpret_cast<floatx4*>(p.y + o) = v;
                 if (bnr) {
                     floatx4 dz;
@@ -255,8 +255,8 @@ __global__ void __launch_bounds__(256) wino_output_kernel(const float* __restric
                         for (int c = 0; c < 4; ++c) dz[c] = mk[c] > 0.f ? v[c] : 0.f;
                     } else if (p.bnr_mask16) {
                         const ushort4 mk = *reinterpret_cast<const ushort4*>(p.bnr_mask16 + o);
-                        dz[0] = (short)mk.x > 0 ? v[0] : 0.f; dz[1] = (short)mk.y > 0 ? v[1] : 0.f;
-                        dz[2] = (short)mk.z > 0 ? v[2] : 0.f; dz[3] = (short)mk.w > 0 ? v[3] : 0.f;
+                        dz[0] = bf16_pos(mk.x) ? v[0] : 0.f; dz[1] = bf16_pos(mk.y) ? v[1] : 0.f;
+                        dz[2] = bf16_pos(mk.z) ? v[2] : 0.f; dz[3] = bf16_pos(mk.w) ? v[3] : 0.f;
                     } else {                         // the activation was never stored: its sign from the pre-BN output (common.h InBn)
 #pragma unroll
                         for (int c = 0; c < 4; ++c) dz[c] = __builtin_fmaf(y1[c], msc[c], msh[c]) > 0.f ? v[c] : 0.f;
@@ -382,7 +382,7 @@ __global__ void __launch_bounds__(256) wino4f_output_kernel(const float* __restr
                 v = v * sc + sh;
                 const size_t o = ((size_t)(b * H + 4 * ty + i) * W + 4 * tx + j) * C + n;
                 if (p.addend) v += *reinterpret_cast<const floatx4*>(p.addend + o);
-                if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                if (p.relu) { v[0] = relu_nan(v[0]); v[1] = relu_nan(v[1]); v[2] = relu_nan(v[2]); v[3] = relu_nan(v[3]); }
                 *reinterpret_cast<floatx4*>(p.y + o) = v;
                 if (bnr) {
                     floatx4 dz;
@@ -393,8 +393,8 @@ __global__ void __launch_bounds__(256) wino4f_output_kernel(const float* __restr
                         for (int c = 0; c < 4; ++c) dz[c] = mk[c] > 0.f ? v[c] : 0.f;
                     } else if (p.bnr_mask16) {
                         const ushort4 mk = *reinterpret_cast<const ushort4*>(p.bnr_mask16 + o);
-                        dz[0] = (short)mk.x > 0 ? v[0] : 0.f; dz[1] = (short)mk.y > 0 ? v[1] : 0.f;
-                        dz[2] = (short)mk.z > 0 ? v[2] : 0.f; dz[3] = (short)mk.w > 0 ? v[3] : 0.f;
+                        dz[0] = bf16_pos(mk.x) ? v[0] : 0.f; dz[1] = bf16_pos(mk.y) ? v[1] : 0.f;
+                        dz[2] = bf16_pos(mk.z) ? v[2] : 0.f; dz[3] = bf16_pos(mk.w) ? v[3] : 0.f;
                     } else {                         // the activation was never stored: its sign from the pre-BN output (common.h InBn)
 #pragma unroll
                         for (int c = 0; c < 4; ++c) dz[c] = __builtin_fmaf(y1[c], msc[c], msh[c]) > 0.f ? v[c] : 0.f;
@@ -553,7 +553,7 @@ __global__ void __launch_bounds__(256, 2) wino4f_output2_kernel(const float* __r
                     v_ = v_ * sc + sh;
                     if constexpr (ADD) v_ += ad[i][j];
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) v_[c] = relu ? fmaxf(v_[c], 0.f) : v_[c];      // (a select, not a branch per pixel)
+                    for (int c = 0; c < 4; ++c) v_[c] = relu ? relu_nan(v_[c]) : v_[c];      // (a select, not a branch per pixel)
                     v[i][j] = v_;
                     if constexpr (bnr) {
                         floatx4 dz;
@@ -562,8 +562,8 @@ __global__ void __launch_bounds__(256, 2) wino4f_output2_kernel(const float* __r
                             for (int c = 0; c < 4; ++c) dz[c] = mk[i][j][c] > 0.f ? v_[c] : 0.f;
                         } else if constexpr (BNR == 2) {
                             const ushort4 m16 = mk16[i][j];
-                            dz[0] = (short)m16.x > 0 ? v_[0] : 0.f; dz[1] = (short)m16.y > 0 ? v_[1] : 0.f;
-                            dz[2] = (short)m16.z > 0 ? v_[2] : 0.f; dz[3] = (short)m16.w > 0 ? v_[3] : 0.f;
+                            dz[0] = bf16_pos(m16.x) ? v_[0] : 0.f; dz[1] = bf16_pos(m16.y) ? v_[1] : 0.f;
+                            dz[2] = bf16_pos(m16.z) ? v_[2] : 0.f; dz[3] = bf16_pos(m16.w) ? v_[3] : 0.f;
                         } else {                     // the activation was never stored: its sign from the pre-BN output (common.h InBn)
 #pragma unroll
                             for (int c = 0; c < 4; ++c) dz[c] = __builtin_fmaf(y1[i][j][c], msc[c], msh[c]) > 0.f ? v_[c] : 0.f;

@@ -68,7 +68,7 @@ __device__ __forceinline__ float4 ld4y(const float* y, size_t i4, int y_bf16) {
     return make_float4(from_bf16(h.x), from_bf16(h.y), from_bf16(h.z), from_bf16(h.w));
 }
 __device__ __forceinline__ float4 relu4(float4 a) {
-    return make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f));
+    return make_float4(relu_nan(a.x), relu_nan(a.y), relu_nan(a.z), relu_nan(a.w));
 }
 
 // out = [relu]( y*scale+shift [+ res | + res*rscale+rshift] ), one float4 per thread-iteration
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) bn_apply16_kernel(const uint16_t* __restr
         for (int k = 0; k < 8; ++k) {
             float v = fmaf(a.v[k], scp[k], shp[k]);
             if (res) v += has_rbn ? fmaf(r.v[k], rscp[k], rshp[k]) : r.v[k];
-            a.v[k] = relu ? fmaxf(v, 0.f) : v;
+            a.v[k] = relu ? relu_nan(v) : v;
         }
         return pack8(a);
     };
@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply16_kernel(const uint16_t* __r
             const short m = (short)(k & 1 ? mw[k >> 1] >> 16 : mw[k >> 1] & 0xffffu);
             bool pos;
             if constexpr (MFY) pos = fmaf(yv.v[k], ms[k], mh[k]) > 0.f;
-            else pos = m > 0;
+            else pos = bf16_pos((uint16_t)m);
             if (!pos) zw[k >> 1] &= (k & 1) ? 0x0000ffffu : 0xffff0000u;
             const float dz = pos ? gv.v[k] : 0.f;
             o.v[k] = ka[k] * (dz - db[k] - (yv.v[k] - mu[k]) * is[k] * dg[k]);
@@ -288,10 +288,11 @@ __global__ void stem_pool_fwd_kernel(const float* __restrict__ y, BnRef bn, floa
                 if (ix < 0 || ix >= W) continue;
                 float4 v = relu4(fma4(ld4y(y, (((size_t)b * H + iy) * W + ix) * C4 + c4, y_bf16), sc, sh));
                 unsigned char s = (unsigned char)(dy * 3 + dx);
-                if (v.x > best.x) { best.x = v.x; bi.x = s; }
-                if (v.y > best.y) { best.y = v.y; bi.y = s; }
-                if (v.z > best.z) { best.z = v.z; bi.z = s; }
-                if (v.w > best.w) { best.w = v.w; bi.w = s; }
+                // a NaN of the window is the maximum, as max_pool2d has it (and stays: nothing compares greater than it)
+                if (v.x > best.x || v.x != v.x) { best.x = v.x; bi.x = s; }
+                if (v.y > best.y || v.y != v.y) { best.y = v.y; bi.y = s; }
+                if (v.z > best.z || v.z != v.z) { best.z = v.z; bi.z = s; }
+                if (v.w > best.w || v.w != v.w) { best.w = v.w; bi.w = s; }
             }
         }
         st4(pooled + i * 4, best);
@@ -455,8 +456,8 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __
             dz.z = m.z > 0.f ? dz.z : 0.f; dz.w = m.w > 0.f ? dz.w : 0.f;
         } else if (mask16) {
             const ushort4 m = *reinterpret_cast<const ushort4*>(mask16 + i * 4);
-            dz.x = (short)m.x > 0 ? dz.x : 0.f; dz.y = (short)m.y > 0 ? dz.y : 0.f;
-            dz.z = (short)m.z > 0 ? dz.z : 0.f; dz.w = (short)m.w > 0 ? dz.w : 0.f;
+            dz.x = bf16_pos(m.x) ? dz.x : 0.f; dz.y = bf16_pos(m.y) ? dz.y : 0.f;
+            dz.z = bf16_pos(m.z) ? dz.z : 0.f; dz.w = bf16_pos(m.w) ? dz.w : 0.f;
         } else if (mscale) {                 // the activation was never stored: its sign from the pre-BN output (common.h InBn)
             const float4 a = fma4(yv, ld4(mscale + c), ld4(mshift + c));
             dz.x = a.x > 0.f ? dz.x : 0.f; dz.y = a.y > 0.f ? dz.y : 0.f;

@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(256) head_conv3_bwd_kernel(const float* __rest
 // One-hot upstream gradient: the TD loss touches ONE Q-value per transition (train.py:115,129), so dLoss/dQ has exactly B
 // non-zeros.  This launch replaces the dense head_conv3_bwd + upsample2x_bwd pair (and the zero-filled dQ map) by B tiny
 // blocks: conv3 backward at the one pixel, then the bilinear x2 transpose scatters its 32 channels onto <= 4 pixels of the
-// 48x48 head activation gradient (ds1, zero on entry).  g = clamp(q_sa - y, -1, 1) * grad_scale is the Huber derivative.
+// 48x48 head activation gradient (ds1, zero on entry).  g = huber_grad(q_sa - y) * grad_scale is the Huber derivative (common.h).
 __device__ __forceinline__ void lerp2x(int o, int in_size, float scale, int& i0, int& i1, float& l0, float& l1) {
     const float real = scale * (float)o;       // ATen upsample_bilinear2d, align_corners=True (as elementwise.hip lerp_coord)
     i0 = (int)real;
@@ -132,13 +132,20 @@ __global__ void __launch_bounds__(256) head_up_relu_conv3_kernel(const float* __
         const float* base = z2 + (size_t)b * W1 * W1 * CIN + sub * 4;
         const float4 v00 = *reinterpret_cast<const float4*>(base + (y0 * W1 + x0) * CIN), v01 = *reinterpret_cast<const float4*>(base + (y0 * W1 + x1) * CIN);
         const float4 v10 = *reinterpret_cast<const float4*>(base + (y1 * W1 + x0) * CIN), v11 = *reinterpret_cast<const float4*>(base + (y1 * W1 + x1) * CIN);
+        // ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d) and the dot product below with their fused multiply-adds WRITTEN OUT, in the
+        // order the compiler's contraction gave this kernel before the ReLU kept NaNs: left to it, the other ReLU regrouped them (packed
+        // multiplies, unfused adds) and the Q-map moved by an ulp
+        auto lerp = [&](float a, float b, float c, float d) {
+            const float top = __builtin_fmaf(lx0, a, lx1 * b), bot = __builtin_fmaf(lx0, c, lx1 * d);
+            return relu_nan(__builtin_fmaf(ly0, top, ly1 * bot));
+        };
         float4 v;
-        v.x = fmaxf(ly0 * (lx0 * v00.x + lx1 * v01.x) + ly1 * (lx0 * v10.x + lx1 * v11.x), 0.f);
-        v.y = fmaxf(ly0 * (lx0 * v00.y + lx1 * v01.y) + ly1 * (lx0 * v10.y + lx1 * v11.y), 0.f);
-        v.z = fmaxf(ly0 * (lx0 * v00.z + lx1 * v01.z) + ly1 * (lx0 * v10.z + lx1 * v11.z), 0.f);
-        v.w = fmaxf(ly0 * (lx0 * v00.w + lx1 * v01.w) + ly1 * (lx0 * v10.w + lx1 * v11.w), 0.f);
+        v.x = lerp(v00.x, v01.x, v10.x, v11.x);
+        v.y = lerp(v00.y, v01.y, v10.y, v11.y);
+        v.z = lerp(v00.z, v01.z, v10.z, v11.z);
+        v.w = lerp(v00.w, v01.w, v10.w, v11.w);
         for (int co = 0; co < Cout; ++co) {
-            float s = v.x * wv[co].x + v.y * wv[co].y + v.z * wv[co].z + v.w * wv[co].w;
+            float s = __builtin_fmaf(v.w, wv[co].w, __builtin_fmaf(v.z, wv[co].z, __builtin_fmaf(v.x, wv[co].x, v.y * wv[co].y)));
 #pragma unroll
             for (int o = L / 2; o >= 1; o >>= 1) s += __shfl_xor(s, o);
             if (sub == 0) z[((size_t)b * Cout + co) * (W2 * W2) + p] = s;
@@ -171,7 +178,7 @@ __global__ void __launch_bounds__(32) head_onehot_bwd_kernel(const float* __rest
     }
     const int oy = p / W2, ox = p - oy * W2;
     const float d = q_sa[b] - y[b];
-    const float g = fminf(fmaxf(d, -1.f), 1.f) * grad_scale;
+    const float g = huber_grad(d) * grad_scale;
     const float s = (float)(W1 - 1) / (float)(W2 - 1);
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;

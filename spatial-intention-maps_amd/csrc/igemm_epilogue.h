@@ -85,7 +85,7 @@ __device__ __forceinline__ void igemm_epilogue(const EpiArgs& p, floatx4 (&acc)[
                     adv[r] = !p.addend ? 0.f : p.addend_bf16 ? epi_from_bf16(reinterpret_cast<const uint16_t*>(p.addend)[o]) : p.addend[o];
                     if (bnr) {
                         y1v[r] = p.bnr_y_bf16 ? epi_from_bf16(reinterpret_cast<const uint16_t*>(p.bnr_y1)[o]) : p.bnr_y1[o];
-                        posv[r] = p.bnr_mask ? p.bnr_mask[o] > 0.f : p.bnr_mask16 ? (short)p.bnr_mask16[o] > 0 : __builtin_fmaf(y1v[r], msc, msh) > 0.f;
+                        posv[r] = p.bnr_mask ? p.bnr_mask[o] > 0.f : p.bnr_mask16 ? bf16_pos(p.bnr_mask16[o]) : __builtin_fmaf(y1v[r], msc, msh) > 0.f;
                         if (bnr2) y2v[r] = p.bnr_y_bf16 ? epi_from_bf16(reinterpret_cast<const uint16_t*>(p.bnr_y2)[o]) : p.bnr_y2[o];
                     }
                 }
@@ -99,7 +99,7 @@ __device__ __forceinline__ void igemm_epilogue(const EpiArgs& p, floatx4 (&acc)[
                     v = v * sc + sh;
                     const size_t o = (size_t)m * Cout + n;
                     if (p.addend) v += adv[r];
-                    if (p.relu) v = fmaxf(v, 0.f);
+                    if (p.relu) v = relu_nan(v);
                     if (p.y_bf16) reinterpret_cast<uint16_t*>(p.y)[o] = epi_to_bf16(v);
                     else p.y[o] = v;
                     if (bnr) {
@@ -232,7 +232,7 @@ __device__ __forceinline__ void igemm_epilogue_staged(const EpiArgs& p, floatx4 
                         v += bias;
                         v = v * sc + sh;
                         if (ad16) v += floatx4{epi_from_bf16(ha[u].x), epi_from_bf16(ha[u].y), epi_from_bf16(ha[u].z), epi_from_bf16(ha[u].w)};
-                        if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                        if (p.relu) { v[0] = relu_nan(v[0]); v[1] = relu_nan(v[1]); v[2] = relu_nan(v[2]); v[3] = relu_nan(v[3]); }
                         *reinterpret_cast<ushort4*>(out16 + off[u]) = make_ushort4(epi_to_bf16(v[0]), epi_to_bf16(v[1]), epi_to_bf16(v[2]), epi_to_bf16(v[3]));
                         floatx4 dz;
                         const floatx4 y1 = {epi_from_bf16(h1[u].x), epi_from_bf16(h1[u].y), epi_from_bf16(h1[u].z), epi_from_bf16(h1[u].w)};
@@ -240,8 +240,8 @@ __device__ __forceinline__ void igemm_epilogue_staged(const EpiArgs& p, floatx4 
 #pragma unroll
                             for (int c = 0; c < 4; ++c) dz[c] = __builtin_fmaf(y1[c], msc[c], msh[c]) > 0.f ? v[c] : 0.f;
                         } else {
-                            dz[0] = (short)hm[u].x > 0 ? v[0] : 0.f; dz[1] = (short)hm[u].y > 0 ? v[1] : 0.f;
-                            dz[2] = (short)hm[u].z > 0 ? v[2] : 0.f; dz[3] = (short)hm[u].w > 0 ? v[3] : 0.f;
+                            dz[0] = bf16_pos(hm[u].x) ? v[0] : 0.f; dz[1] = bf16_pos(hm[u].y) ? v[1] : 0.f;
+                            dz[2] = bf16_pos(hm[u].z) ? v[2] : 0.f; dz[3] = bf16_pos(hm[u].w) ? v[3] : 0.f;
                         }
                         s0 += dz;
                         s1 += dz * ((y1 - mu1) * is1);
@@ -273,7 +273,7 @@ __device__ __forceinline__ void igemm_epilogue_staged(const EpiArgs& p, floatx4 
                         v += *reinterpret_cast<const floatx4*>(p.addend + o);
                     }
                 }
-                if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                if (p.relu) { v[0] = relu_nan(v[0]); v[1] = relu_nan(v[1]); v[2] = relu_nan(v[2]); v[3] = relu_nan(v[3]); }
                 if (p.y_bf16) {
                     *reinterpret_cast<ushort4*>(reinterpret_cast<uint16_t*>(p.y) + o) =
                         make_ushort4(epi_to_bf16(v[0]), epi_to_bf16(v[1]), epi_to_bf16(v[2]), epi_to_bf16(v[3]));
@@ -294,8 +294,8 @@ __device__ __forceinline__ void igemm_epilogue_staged(const EpiArgs& p, floatx4 
                         for (int c = 0; c < 4; ++c) dz[c] = mk[c] > 0.f ? v[c] : 0.f;
                     } else if (p.bnr_mask16) {
                         const ushort4 mk = *reinterpret_cast<const ushort4*>(p.bnr_mask16 + o);
-                        dz[0] = (short)mk.x > 0 ? v[0] : 0.f; dz[1] = (short)mk.y > 0 ? v[1] : 0.f;
-                        dz[2] = (short)mk.z > 0 ? v[2] : 0.f; dz[3] = (short)mk.w > 0 ? v[3] : 0.f;
+                        dz[0] = bf16_pos(mk.x) ? v[0] : 0.f; dz[1] = bf16_pos(mk.y) ? v[1] : 0.f;
+                        dz[2] = bf16_pos(mk.z) ? v[2] : 0.f; dz[3] = bf16_pos(mk.w) ? v[3] : 0.f;
                     } else {
 #pragma unroll
                         for (int c = 0; c < 4; ++c) dz[c] = __builtin_fmaf(y1[c], msc[c], msh[c]) > 0.f ? v[c] : 0.f;

@@ -12,7 +12,10 @@ namespace simq {
 namespace {
 
 __device__ __forceinline__ bool better(float bv, int bi, float av, int ai) {
-    // true if (bv, bi) should replace (av, ai): larger value, or equal value at a smaller index (first-index tie-break)
+    // true if (bv, bi) should replace (av, ai): larger value, or equal value at a smaller index (first-index tie-break).  A NaN is
+    // larger than every number and equal to another NaN, as tensor.max(1) orders it: the first NaN of a row wins
+    const bool bnan = bv != bv, anan = av != av;
+    if (bnan || anan) return bnan && (!anan || bi < ai);
     return (bv > av) || (bv == av && bi < ai);
 }
 
@@ -74,7 +77,7 @@ __global__ void __launch_bounds__(256) td_huber_kernel(const float* __restrict__
         td[i] = ad;
         ls += ad < 1.f ? 0.5f * d * d : ad - 0.5f;          // smooth_l1, beta = 1
         ts += ad;
-        if (dq) dq[o] = fminf(fmaxf(d, -1.f), 1.f) * grad_scale;
+        if (dq) dq[o] = huber_grad(d) * grad_scale;
     }
     sl[threadIdx.x] = ls;
     st[threadIdx.x] = ts;
@@ -127,7 +130,10 @@ __global__ void __launch_bounds__(256) clip_sgd_kernel(float* __restrict__ p, fl
                                                        float* total_norm) {
     float norm = (float)sqrt(*sumsq);
     float coef = 1.f;
-    if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
+    if (max_norm > 0.f) {         // clamp(max_norm / (norm + 1e-6), max = 1), which keeps the NaN of a NaN norm (fminf would answer 1)
+        const float c = max_norm / (norm + 1e-6f);
+        coef = c > 1.f ? 1.f : c;
+    }
     if (total_norm && blockIdx.x == 0 && threadIdx.x == 0) *total_norm = norm;
     size_t n4 = count / 4;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
