@@ -665,7 +665,8 @@ int simq_grid_distance_images_snapped(const uint8_t* d_grids, int64_t grids_byte
  * The search state lives in LDS over a window of the grid that the caller declares: rows [box_i0, box_i0 + box_rows), columns
  * [box_j0, box_j0 + box_cols), which must hold every free cell (empty when there is none).  The window plus a blocked one-cell halo
  * has (box_rows + 2) * (box_cols + 2) <= SIMQ_GRID_PATH_MAX_BOX_CELLS cells (8 bytes each of the 160 KiB); a Mapper room needs
- * 94 x 94.  The kernel reads the whole grid once and gives status 2 when a free cell lies outside the window.
+ * 94 x 94, and simq_grid_paths_large below takes the windows over the cap.  The kernel reads the whole grid once and gives status 2
+ * when a free cell lies outside the window.
  * `problems`: host array of n descriptors, validated here before anything is copied or launched (rows, cols >= 1, rows * cols <
  * SIMQ_GRID_MAX_CELLS; source and target inside the grid; the window inside the grid and under the cap; path_capacity >= 1; every
  * input and output inside the declared extent of its buffer; no two problems' outputs overlapping; the output buffers, d_lengths,
@@ -693,6 +694,42 @@ int simq_grid_paths(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* 
                     const simq_grid_path_problem* problems, int n, simq_grid_path_problem* d_problems, int32_t* d_paths,
                     int64_t path_pairs, int32_t* d_lengths, int32_t* d_endpoints, int32_t* d_parents, int64_t parents_ints, float* d_dist,
                     int64_t dist_floats, int32_t* d_status, void* stream);
+
+/* The same search for windows of any size: the state lies in a workspace of the caller's in global memory instead of LDS, so
+ * SIMQ_GRID_PATH_MAX_BOX_CELLS does not apply -- any window inside a grid of rows * cols < SIMQ_GRID_MAX_CELLS is taken, the empty one
+ * and those under the cap included.  Rules, front stages, outputs, the kernel's re-check (status 2 for a free cell outside the window
+ * included) and status words are those of simq_grid_paths: for a problem both entry points accept, every byte either writes is equal.
+ * One wavefront per problem as there, and a pop costs a few times what it costs in LDS: this entry point is for the windows the
+ * other refuses.
+ * Workspace: d_work (work_bytes bytes, 16-byte aligned) is the caller's; the library allocates nothing.  Problem p's state is the
+ * simq_grid_paths_large_work_bytes(box_rows, box_cols) bytes from byte work_offset (a multiple of 16) on: fp32 distances over the
+ * window plus its halo, a ring of window cells + 1 uint32 entries, one parent byte and one flag byte per cell, in that order, the sum
+ * rounded up to 16 (10 bytes a cell; 543 840 for a 232 x 232 window).  The kernel initialises what it reads; the content after the
+ * call is unspecified.  simq_grid_paths_large_work_bytes is a host function of the two numbers alone (-1 for a negative side or
+ * box_rows * box_cols >= SIMQ_GRID_MAX_CELLS).
+ * Validation as for simq_grid_paths, without the cap, and in addition: d_work not NULL and 16-byte aligned; every problem's range
+ * inside work_bytes at a non-negative multiple of 16; no two problems' ranges overlapping; d_work sharing no byte with any other
+ * buffer of the call. */
+typedef struct simq_grid_path_large_problem {
+    int64_t grid_offset;        /* the fields of simq_grid_path_problem, with the same meaning ... */
+    int64_t thin_offset;
+    int64_t closest_offset;
+    int64_t path_offset;
+    int64_t parents_offset;
+    int64_t dist_offset;
+    int64_t work_offset;        /* ... and the byte offset of the problem's search state in d_work, a multiple of 16 */
+    int32_t path_capacity;
+    int32_t rows, cols;
+    int32_t src_i, src_j, tgt_i, tgt_j;
+    int32_t box_i0, box_j0, box_rows, box_cols;
+    int32_t reserved_;
+} simq_grid_path_large_problem;
+int64_t simq_grid_paths_large_work_bytes(int32_t box_rows, int32_t box_cols);
+int simq_grid_paths_large(const uint8_t* d_grids, int64_t grids_bytes, const int32_t* d_closest, int64_t closest_ints,
+                          const simq_grid_path_large_problem* problems, int n, simq_grid_path_large_problem* d_problems,
+                          int32_t* d_paths, int64_t path_pairs, int32_t* d_lengths, int32_t* d_endpoints, int32_t* d_parents,
+                          int64_t parents_ints, float* d_dist, int64_t dist_floats, int32_t* d_status, void* d_work, int64_t work_bytes,
+                          void* stream);
 
 /* ---- waypoints from dense paths: exact simplification and pruning (shortest_paths.pyx:139-154, the back half of
  * GridGraph.shortest_path: skimage.measure.approximate_polygon, then the waypoints a clear line makes unnecessary) ---------------

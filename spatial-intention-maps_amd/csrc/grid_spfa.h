@@ -19,6 +19,12 @@
 // ring is laid out for window cells + 1 entries and uses free cells + 1 of them: at most every vertex is queued at once, and slot
 // numbers only ever grow, so positions wrap (a cluttered grid pushes 1 - 7 % more often than it has vertices).
 //
+// The state's home.  init_window and search take the state as a type: the four arrays, the ring's entry type, W, N and index.  Lds is
+// the carve-up above.  Hbm is the same carve-up over a caller's workspace in global memory with a 32-bit ring entry -- a window of a
+// grid of SIMQ_GRID_MAX_CELLS cells plus its halo needs 23 bits -- for windows no LDS holds (grid_paths_kernel<InHbm>).  The rules do not
+// know which one they run on; between the lanes of the one wavefront the barrier at the end of each pop orders the stores of that pop
+// before the loads of the next in either memory.
+//
 // kKeepOne.  action_waypoints_kernel's pruning reads "the cell is 1" from the flag byte, so its search must carry that bit through
 // every flag store: it reads the popped vertex's flags and writes them back without kQueued.  grid_paths_kernel has no such reader;
 // with kKeepOne = false every flag store is a constant and the pop loop, the serial chain of that kernel, has no LDS access for it.
@@ -56,15 +62,40 @@ struct Window {
 
 // the carve-up of lds_bytes over the window + halo: W cells a row, N cells in all, the grid's cell (i, j) at index(b, i, j)
 struct Lds {
+    using Entry = uint16_t;
     float* dist;
-    uint16_t* ring;
+    Entry* ring;
     uint8_t* par;
     uint8_t* flg;
     int W, N;
     __device__ __forceinline__ Lds(char* smem, const Window& b) : W(b.cols + 2), N((b.rows + 2) * (b.cols + 2)) {
         dist = reinterpret_cast<float*>(smem);
-        ring = reinterpret_cast<uint16_t*>(smem + 4 * (int64_t)N);
+        ring = reinterpret_cast<Entry*>(smem + 4 * (int64_t)N);
         par = reinterpret_cast<uint8_t*>(smem + 4 * (int64_t)N + 2 * ((b.rows * b.cols + 2) & ~1));
+        flg = par + N;
+    }
+    __device__ __forceinline__ int index(const Window& b, int i, int j) const { return (i - b.i0 + 1) * W + (j - b.j0 + 1); }
+};
+
+// distances | ring | parents | flags over a workspace in global memory: 10 bytes a cell, rounded up to 16
+__host__ __device__ inline int64_t work_bytes(int box_rows, int box_cols) {
+    const int64_t n = (int64_t)(box_rows + 2) * (box_cols + 2);
+    const int64_t q = (int64_t)box_rows * box_cols + 1;
+    return (4 * n + 4 * q + 2 * n + 15) & ~(int64_t)15;
+}
+
+// the carve-up of work_bytes at `work` (16-byte aligned): Lds's members and index, a 32-bit ring entry
+struct Hbm {
+    using Entry = uint32_t;
+    float* dist;
+    Entry* ring;
+    uint8_t* par;
+    uint8_t* flg;
+    int W, N;
+    __device__ __forceinline__ Hbm(char* work, const Window& b) : W(b.cols + 2), N((b.rows + 2) * (b.cols + 2)) {
+        dist = reinterpret_cast<float*>(work);
+        ring = reinterpret_cast<Entry*>(work + 4 * (int64_t)N);
+        par = reinterpret_cast<uint8_t*>(work + 4 * (int64_t)N + 4 * ((int64_t)b.rows * b.cols + 1));
         flg = par + N;
     }
     __device__ __forceinline__ int index(const Window& b, int i, int j) const { return (i - b.i0 + 1) * W + (j - b.j0 + 1); }
@@ -125,8 +156,8 @@ __device__ __forceinline__ bool free_cells_inside(const uint8_t* __restrict__ g,
 // the state before the search: every distance inf but the source's (s_l, -1 when it lies outside the window: 0 there even when the
 // cell is blocked, which the distance image of simq_grid_paths documents), no parents, the flags from the grid, the halo blocked.
 // Returns the number of vertices (wave-uniform); the state is visible to every lane on return.
-template <bool kKeepOne>
-__device__ __forceinline__ int init_window(const Lds& lds, const uint8_t* __restrict__ g, int C, const Window& b, int s_l, float inf,
+template <bool kKeepOne, typename State>
+__device__ __forceinline__ int init_window(const State& lds, const uint8_t* __restrict__ g, int C, const Window& b, int s_l, float inf,
                                            int lane) {
     int vertices = 0;
     for (int l = lane; l < lds.N; l += kLanes) {
@@ -145,10 +176,11 @@ __device__ __forceinline__ int init_window(const Lds& lds, const uint8_t* __rest
 
 // the search from the free window cell s_l over a ring of Q = vertices + 1 slots: distances and parents as the reference leaves them.
 // Returns 0, or 4 when the pop cap was passed (cannot happen); the state is visible to every lane on return.
-template <bool kKeepOne>
-__device__ __forceinline__ int search(const Lds lds, int s_l, int Q, int lane) {
+template <bool kKeepOne, typename State>
+__device__ __forceinline__ int search(const State lds, int s_l, int Q, int lane) {
+    using Entry = typename State::Entry;
     float* const dist = lds.dist;
-    uint16_t* const ring = lds.ring;
+    Entry* const ring = lds.ring;
     uint8_t* const par = lds.par;
     uint8_t* const flg = lds.flg;
     const int W = lds.W;
@@ -161,7 +193,7 @@ __device__ __forceinline__ int search(const Lds lds, int s_l, int Q, int lane) {
     int f = s_l;                                     // the front vertex (slot head + 1), -1 when nothing is queued
     float df = 0.f;                                  // ... and its distance as it stands
     if (lane == 0) {
-        ring[hp] = (uint16_t)s_l;
+        ring[hp] = (Entry)s_l;
         if (kKeepOne) flg[s_l] |= kQueued;
         else flg[s_l] = kFree | kQueued;
     }
@@ -203,15 +235,15 @@ __device__ __forceinline__ int search(const Lds lds, int s_l, int Q, int lane) {
                 ++tail;
                 tp = tp + 1 == Q ? 0 : tp + 1;
                 if (head + 1 == tail) {              // the only one queued: both sides of the comparison are this slot
-                    if (lane == 0) ring[tp] = (uint16_t)vk;
+                    if (lane == 0) ring[tp] = (Entry)vk;
                     f = vk;
                     df = nk;
                 } else if (nk < df) {
-                    if (lane == 0) { ring[tp] = (uint16_t)f; ring[hp] = (uint16_t)vk; }
+                    if (lane == 0) { ring[tp] = (Entry)f; ring[hp] = (Entry)vk; }
                     f = vk;
                     df = nk;
                 } else if (lane == 0) {
-                    ring[tp] = (uint16_t)vk;
+                    ring[tp] = (Entry)vk;
                 }
             }
         }

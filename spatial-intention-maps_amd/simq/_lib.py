@@ -176,6 +176,9 @@ _SIGS = {
                                                   c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     'simq_grid_paths': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'simq_grid_paths_large_work_bytes': (c_int64, [c_int, c_int]),
+    'simq_grid_paths_large': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     'simq_grid_waypoints': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p]),
     'simq_action_waypoints': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,

@@ -8,7 +8,9 @@ emulates the search itself, one problem per wavefront, and returns parents, dist
 for bit.  The default simplification stays on the host: it is float64 trigonometry whose ties are libm noise.
 simplify='exact' is the same algorithm with every comparison decided in integers (the rule of include/simq.h): on the host
 approximate_polygon_exact, on the device ``simq_grid_waypoints`` (csrc/grid_simplify.hip), which simplifies and prunes the dense paths
-where the search left them, so that only the waypoints come back.
+where the search left them, so that only the waypoints come back.  The search keeps its state in LDS, which bounds the box of a
+grid's free cells; large_windows=True sends the problems over that bound to ``simq_grid_paths_large``, the same search with its state in
+a workspace in device memory.
 """
 import collections
 import ctypes
@@ -31,6 +33,56 @@ class GridPathProblem(ctypes.Structure):
                                               'dist_offset')] + \
                [(n, ctypes.c_int32) for n in ('path_capacity', 'rows', 'cols', 'src_i', 'src_j', 'tgt_i', 'tgt_j', 'box_i0', 'box_j0',
                                               'box_rows', 'box_cols', 'reserved_')]
+
+
+class GridPathLargeProblem(ctypes.Structure):
+    """simq_grid_path_large_problem of include/simq.h: GridPathProblem's fields plus work_offset."""
+    _fields_ = [(n, ctypes.c_int64) for n in ('grid_offset', 'thin_offset', 'closest_offset', 'path_offset', 'parents_offset',
+                                              'dist_offset', 'work_offset')] + GridPathProblem._fields_[6:]
+
+
+def large_work_bytes(box_rows, box_cols):
+    """simq_grid_paths_large_work_bytes of include/simq.h restated: fp32 distances, one-byte parents and flags over the window plus
+    its halo, a ring of window cells + 1 32-bit entries, rounded up to 16."""
+    cells = (box_rows + 2) * (box_cols + 2)
+    return (6 * cells + 4 * (box_rows * box_cols + 1) + 15) // 16 * 16
+
+
+def split_by_window(boxes):
+    """(fit, over): the problems whose window (i0, j0, rows, cols) plus its halo has at most MAX_BOX_CELLS cells -- simq_grid_paths
+    takes them, its search state in LDS -- and the others, for simq_grid_paths_large; both ascending."""
+    fit = [p for p, b in enumerate(boxes) if (b[2] + 2) * (b[3] + 2) <= MAX_BOX_CELLS]
+    over = [p for p, b in enumerate(boxes) if (b[2] + 2) * (b[3] + 2) > MAX_BOX_CELLS]
+    return fit, over
+
+
+def entry_calls(n_fit, n):
+    """The entry points a call over n problems makes when the first n_fit fit the LDS cap: [(name, first, last + 1)], an empty part
+    left out."""
+    return [c for c in (('simq_grid_paths', 0, n_fit), ('simq_grid_paths_large', n_fit, n)) if c[2] > c[1]]
+
+
+def restore_order(order, items):
+    """items[k] belongs to problem order[k]: the list in problem order."""
+    out = [None] * len(order)
+    for k, p in enumerate(order):
+        out[p] = items[k]
+    return out
+
+
+def _check_large_windows(large_windows):
+    if not isinstance(large_windows, bool):
+        raise ValueError('large_windows must be True or False, got %r' % (large_windows,))
+    return large_windows
+
+
+def _window_order(descs, large_windows):
+    """(order, n_fit): the problems in the order they are launched -- with large_windows those over the LDS cap behind the others,
+    descs[order[n_fit:]] for simq_grid_paths_large; without it all as they come, for simq_grid_paths to take or refuse."""
+    if not large_windows:
+        return list(range(len(descs))), len(descs)
+    fit, over = split_by_window([d['box'] for d in descs])
+    return fit + over, len(fit)
 
 
 class GridWaypointProblem(ctypes.Structure):
@@ -185,39 +237,54 @@ def _boxes(grids, used, dev):
     return boxes
 
 
-def _launch(dev, packed, closest_buf, descs, parents, distances):
-    """One simq_grid_paths call over `descs` and the read-back of its lengths, status words and end pixels."""
+def _launch(dev, packed, closest_buf, descs, parents, distances, n_fit=None):
+    """The search over `descs` (_enqueue) and the read-back of its lengths, status words and end pixels."""
     P = len(descs)
     small = torch.empty((P, 6), dtype=torch.int32, device=dev)          # lengths | status | end pixels
-    paths, par, dist = _enqueue(dev, packed, closest_buf, descs, parents, distances, small.view(-1))
+    paths, par, dist = _enqueue(dev, packed, closest_buf, descs, parents, distances, small.view(-1), n_fit)
     host = small.cpu().numpy().reshape(-1)
     return paths, host[:P].copy(), host[P:2 * P].copy(), host[2 * P:].reshape(P, 4).copy(), par, dist
 
 
-def _enqueue(dev, packed, closest_buf, descs, parents, distances, small):
-    """Queues one simq_grid_paths call over `descs`: dicts with the descriptor's grid / thin / closest offsets, shape, pixels, box and
-    capacity.  small: int32 device tensor whose first 6 P entries receive lengths | status | end pixels.  Nothing is read back."""
+def _enqueue(dev, packed, closest_buf, descs, parents, distances, small, n_fit=None):
+    """Queues the search over `descs`: dicts with the descriptor's grid / thin / closest offsets, shape, pixels, box and capacity.  The
+    first n_fit of them (all when None) go to simq_grid_paths, the others to simq_grid_paths_large with a workspace allocated here;
+    both calls write the same buffers, each its own problems' ranges.  small: int32 device tensor whose first 6 P entries receive
+    lengths | status | end pixels.  Nothing is read back."""
     P = len(descs)
-    probs = (GridPathProblem * P)()
+    n_fit = P if n_fit is None else n_fit
     po = io = 0
-    for p, d in enumerate(descs):
-        cells = d['rows'] * d['cols']
-        probs[p] = GridPathProblem(d['grid'], d['thin'], d['closest'], po, io if parents else -1, io if distances else -1, d['capacity'],
-                                   d['rows'], d['cols'], d['src'][0], d['src'][1], d['tgt'][0], d['tgt'][1], *d['box'], 0)
+    fields = []
+    for d in descs:
+        fields.append(([d['grid'], d['thin'], d['closest'], po, io if parents else -1, io if distances else -1],
+                       [d['capacity'], d['rows'], d['cols'], d['src'][0], d['src'][1], d['tgt'][0], d['tgt'][1], *d['box'], 0]))
         po += d['capacity']
-        io += cells
-    d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+        io += d['rows'] * d['cols']
     paths = torch.empty((po, 2), dtype=torch.int32, device=dev)
     lengths, status, ends = small[:P], small[P:2 * P], small[2 * P:6 * P]
     par = torch.empty(io, dtype=torch.int32, device=dev) if parents else None
     dist = torch.empty(io, dtype=torch.float32, device=dev) if distances else None
-    lib.call('simq_grid_paths', ptr(packed), ctypes.c_int64(packed.numel()), ptr(closest_buf),
-             ctypes.c_int64(0 if closest_buf is None else closest_buf.numel()), probs, P, ptr(d_probs), ptr(paths), ctypes.c_int64(po),
-             ptr(lengths), ptr(ends), ptr(par), ctypes.c_int64(io), ptr(dist), ctypes.c_int64(io), ptr(status), stream_ptr(dev))
+    for name, a, b in entry_calls(n_fit, P):
+        extra = ()
+        if name == 'simq_grid_paths':
+            probs = (GridPathProblem * (b - a))(*[GridPathProblem(*offsets, *ints) for offsets, ints in fields[a:b]])
+        else:
+            need = [large_work_bytes(d['box'][2], d['box'][3]) for d in descs[a:b]]
+            at = np.concatenate([[0], np.cumsum(need)]).tolist()
+            probs = (GridPathLargeProblem * (b - a))(*[GridPathLargeProblem(*offsets, at[k], *ints)
+                                                       for k, (offsets, ints) in enumerate(fields[a:b])])
+            work = torch.empty(at[-1], dtype=torch.uint8, device=dev)
+            extra = (ptr(work), ctypes.c_int64(at[-1]))
+        d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+        lib.call(name, ptr(packed), ctypes.c_int64(packed.numel()), ptr(closest_buf),
+                 ctypes.c_int64(0 if closest_buf is None else closest_buf.numel()), probs, b - a, ptr(d_probs), ptr(paths), ctypes.c_int64(po),
+                 ptr(lengths[a:b]), ptr(ends[4 * a:4 * b]), ptr(par), ctypes.c_int64(io), ptr(dist), ctypes.c_int64(io), ptr(status[a:b]),
+                 *extra, stream_ptr(dev))
     return paths, par, dist
 
 
-def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, distances=False, thin=None, closest=None):
+def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, distances=False, thin=None, closest=None,
+                     large_windows=False):
     """The dense paths of P (grid, source, target) problems in one launch: SPFA from the source, then the walk over its parents from
     the target (shortest_paths.pyx:69-137), bit for bit.
 
@@ -235,16 +302,24 @@ def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, di
     asked), P float32 device tensors [rows, cols], -1 where unreachable.  The images of a STRAIGHT problem are not written.
 
     The search state lives in LDS over the bounding box of the grid's free cells: a box of more than MAX_BOX_CELLS cells with its
-    one-cell halo is refused (SimqError, nothing launched).  A path longer than the first buffer is fetched with one more launch."""
+    one-cell halo is refused (SimqError, nothing launched) unless large_windows is True.  Then the problems over the cap go to
+    simq_grid_paths_large, whose state lies in a workspace in device memory allocated here (10 bytes a cell of the box), the others
+    to simq_grid_paths as before, both queued before the one read-back; the results are the same and come in problem order, and a
+    search over the cap costs a few times what one in LDS costs per cell.  A path longer than the first buffer is fetched with one
+    more launch."""
+    _check_large_windows(large_windows)
     dev, packed, closest_buf, descs = _prepare(grids, sources, targets, grid_index, thin, closest)
-    paths, lengths, status, ends, par, dist = _launch(dev, packed, closest_buf, descs, parents, distances)
+    order, n_fit = _window_order(descs, large_windows)   # (the launches, and everything up to the return, in this order)
+    descs = [descs[p] for p in order]
+    paths, lengths, status, ends, par, dist = _launch(dev, packed, closest_buf, descs, parents, distances, n_fit)
     _raise_for(status)
     starts = np.concatenate([[0], np.cumsum([d['capacity'] for d in descs])])
     host = paths.cpu().numpy()
     out = [host[starts[p]:starts[p] + min(lengths[p], descs[p]['capacity'])].copy() for p in range(len(descs))]
     short = np.flatnonzero(status == CAPACITY)
     if short.size:                                       # a longer buffer for those problems, once; no image is written again
-        paths2, lengths2, status2, _, _, _ = _launch(dev, packed, None, _again(descs, short, lengths, ends), False, False)
+        paths2, lengths2, status2, _, _, _ = _launch(dev, packed, None, _again(descs, short, lengths, ends), False, False,
+                                                     int((short < n_fit).sum()))
         _raise_for(status2, allow_capacity=False)
         host2, o = paths2.cpu().numpy(), 0
         for p, n in zip(short, lengths2):
@@ -252,7 +327,9 @@ def grid_dense_paths(grids, sources, targets, grid_index=None, parents=False, di
             o += int(lengths[p])
             status[p] = TRACED
     shapes = [(d['rows'], d['cols']) for d in descs]
-    return DensePaths(out, status, ends, *[None if flat is None else _batch.views(flat, shapes) for flat in (par, dist)])
+    images = [None if flat is None else restore_order(order, _batch.views(flat, shapes)) for flat in (par, dist)]
+    back = np.argsort(order)
+    return DensePaths(restore_order(order, out), status[back], ends[back], *images)
 
 
 def _again(descs, problems, lengths, ends):
@@ -320,25 +397,27 @@ def _enqueue_waypoints(dev, packed, paths, descs, capacities, tolerance, small, 
              ptr(small[base:base + P]), stream_ptr(dev))
 
 
-def _search_and_simplify(dev, packed, closest_buf, descs, capacities, tolerance):
-    """simq_grid_paths and simq_grid_waypoints back to back on the same device buffers and the one read-back of both: (lengths, path
+def _search_and_simplify(dev, packed, closest_buf, descs, capacities, tolerance, n_fit=None):
+    """The search (_enqueue: simq_grid_paths, simq_grid_paths_large or both) and simq_grid_waypoints back to back on the same device buffers and the one read-back of both: (lengths, path
     status, end pixels [P, 4], waypoint status, counts, the waypoint buffer [pairs, 2]) as host arrays."""
     P = len(descs)
     base = 6 * P + (6 * P) % 2                           # the waypoints start on an 8-byte boundary
     small = torch.empty(base + 2 * P + 2 * sum(capacities), dtype=torch.int32, device=dev)
-    paths, _, _ = _enqueue(dev, packed, closest_buf, descs, False, False, small)
+    paths, _, _ = _enqueue(dev, packed, closest_buf, descs, False, False, small, n_fit)
     _enqueue_waypoints(dev, packed, paths, descs, capacities, tolerance, small, base)
     host = small.cpu().numpy()
     return (host[:P], host[P:2 * P], host[2 * P:6 * P].reshape(P, 4), host[base:base + P], host[base + P:base + 2 * P],
             host[base + 2 * P:].reshape(-1, 2))
 
 
-def grid_waypoints(grids, sources, targets, grid_index=None, thin=None, closest=None, tolerance=1):
+def grid_waypoints(grids, sources, targets, grid_index=None, thin=None, closest=None, tolerance=1, large_windows=False):
     """The waypoints of P (grid, source, target) problems without a dense path on the host: simq_grid_paths as in grid_dense_paths (same
     arguments), and right behind it simq_grid_waypoints, which simplifies each dense path by the exact rule of include/simq.h
     (approximate_polygon_exact, integer tolerance in [1, 255]) and prunes it against its grid as shortest_paths.pyx:142-149 does.  One
     array comes back for the call: status words, counts, end pixels and waypoints; a problem whose dense path did not fit its first
     buffer, or that has more than WAY_CAPACITY waypoints, is finished by one more pair of launches and one more read-back.
+    large_windows: as for grid_dense_paths; simq_grid_waypoints then simplifies the paths of both searches in its one launch, and a
+    dense path of more than SIMQ_GRID_WAYPOINTS_MAX_PATH points stays its refusal.
 
     Returns Waypoints(waypoints, status, endpoints): waypoints, a list of P int32 numpy arrays [m, 2], source first -- what
     prune(grid, dense, approximate_polygon_exact) returns -- and empty for a STRAIGHT problem; status, int32 numpy [P] of TRACED /
@@ -346,9 +425,12 @@ def grid_waypoints(grids, sources, targets, grid_index=None, thin=None, closest=
     if isinstance(tolerance, bool) or int(tolerance) != tolerance or not 1 <= int(tolerance) <= 255:
         raise ValueError('grid_waypoints takes an integer tolerance in [1, 255], got %r' % (tolerance,))
     tolerance = int(tolerance)
+    _check_large_windows(large_windows)
     dev, packed, closest_buf, descs = _prepare(grids, sources, targets, grid_index, thin, closest)
+    order, n_fit = _window_order(descs, large_windows)   # (the launches, and everything up to the return, in this order)
+    descs = [descs[p] for p in order]
     capacities = [min(d['capacity'], WAY_CAPACITY) for d in descs]
-    lengths, status, ends, wstatus, counts, ways = _search_and_simplify(dev, packed, closest_buf, descs, capacities, tolerance)
+    lengths, status, ends, wstatus, counts, ways = _search_and_simplify(dev, packed, closest_buf, descs, capacities, tolerance, n_fit)
     _raise_for(status)
     _raise_for_waypoints(wstatus)
     status, ends = status.copy(), ends.copy()
@@ -358,7 +440,8 @@ def grid_waypoints(grids, sources, targets, grid_index=None, thin=None, closest=
     if short.size:                                       # buffers that hold the whole dense path and every waypoint, once
         again = _again(descs, short, lengths, ends)
         capacities2 = [int(counts[p]) if status[p] == TRACED else int(lengths[p]) for p in short]
-        _, status2, _, wstatus2, counts2, ways2 = _search_and_simplify(dev, packed, None, again, capacities2, tolerance)
+        _, status2, _, wstatus2, counts2, ways2 = _search_and_simplify(dev, packed, None, again, capacities2, tolerance,
+                                                                       int((short < n_fit).sum()))
         _raise_for(status2, allow_capacity=False)
         _raise_for_waypoints(wstatus2, allow_capacity=False)
         o = 0
@@ -366,7 +449,8 @@ def grid_waypoints(grids, sources, targets, grid_index=None, thin=None, closest=
             out[p] = ways2[o:o + n].copy()
             o += cap
             status[p] = TRACED
-    return Waypoints(out, status, ends)
+    back = np.argsort(order)
+    return Waypoints(restore_order(order, out), status[back], ends[back])
 
 
 def _raise_for_waypoints(status, allow_capacity=True):
@@ -394,8 +478,11 @@ class WaypointGraph(GridGraph):
     #: the tests pin the host half (walk, pruning, reversal) through it without a device
     search = None
 
-    def __init__(self, grid):
+    def __init__(self, grid, large_windows=False):
+        """large_windows: as for grid_dense_paths -- a grid whose free cells span a box over the LDS cap is searched in device memory
+        instead of being refused."""
         super().__init__(grid)
+        self.large_windows = _check_large_windows(large_windows)
         self.parents = {}
 
     def _parents(self, source):
@@ -405,7 +492,8 @@ class WaypointGraph(GridGraph):
             else:
                 if self._dev_grid is None:
                     self._dev_grid = torch.from_numpy(self.grid).to(_batch.device('grid distance images'))
-                got = grid_dense_paths([self._dev_grid], [source], [source], parents=True, distances=True)
+                got = grid_dense_paths([self._dev_grid], [source], [source], parents=True, distances=True,
+                                       large_windows=self.large_windows)
                 par, dist = got.parents[0].cpu().numpy(), got.distances[0].cpu().numpy()
             self.parents[source] = np.asarray(par, np.int32)
             self.cache.setdefault(source, np.asarray(dist, np.float32))
@@ -424,7 +512,8 @@ class WaypointGraph(GridGraph):
         return prune(self.grid, self.dense_path(source, target), simplify)
 
 
-def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positions, map_index=None, simplify=None):
+def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positions, map_index=None, simplify=None,
+                   large_windows=False):
     """OccupancyMap.shortest_path (envs.py:2477-2504) for P robots in one launch, on the device tensors simq.occupancy_maps returned.
 
     cspace, cspace_thin: M uint8 maps each ([M, rows, cols] tensor or a list), closest: M int32 [2, rows, cols]; source_positions,
@@ -434,10 +523,12 @@ def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positi
     skimage.measure.approximate_polygon) and pruning run on the host, over the free-cell boxes of the maps that had a problem that was
     not straight -- nothing else of a configuration space is downloaded.  With simplify='exact' they run on the device as well
     (grid_waypoints): one small array of status words, counts, end pixels and waypoints is read back, no dense path and no map.
+    large_windows: as for grid_dense_paths, for maps whose free cells span a box over the LDS cap.
     Returns P lists of positions: the two given tuples when the line is clear or the path has fewer than two waypoints, otherwise
     (x, y, 0) tuples with the given tuples at both ends."""
     if isinstance(simplify, str):
         _simplifier(simplify)                                 # (an unknown name is refused before anything is queued)
+    _check_large_windows(large_windows)
     maps, _ = _batch.as_maps(cspace, 'cspace')
     P = len(source_positions)
     if len(target_positions) != P or P < 1:
@@ -447,10 +538,11 @@ def shortest_paths(cspace, cspace_thin, closest, source_positions, target_positi
     srcs = [position_to_pixel_indices(s[0], s[1], tuple(maps[k].shape)) for s, k in zip(source_positions, map_index)]
     tgts = [position_to_pixel_indices(t[0], t[1], tuple(maps[k].shape)) for t, k in zip(target_positions, map_index)]
     on_device = isinstance(simplify, str)
+    large = {'large_windows': True} if large_windows else {}          # (the default call is the call as it was)
     if on_device:
-        got = grid_waypoints(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest)
+        got = grid_waypoints(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest, **large)
     else:
-        got = grid_dense_paths(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest)
+        got = grid_dense_paths(maps, srcs, tgts, grid_index=map_index, thin=cspace_thin, closest=closest, **large)
         if (got.status == TRACED).any():
             simplify = _simplifier(simplify)
     host_maps, result = {}, []
