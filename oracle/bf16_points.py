@@ -162,7 +162,7 @@ def fcn_forward(state, x, training, points=True, update_buffers=True, taps=None)
             y = y + identity
         return P.fwd(F.relu(y) if relu else y)
 
-    y0 = P.fwd(conv(P.fwd(x), P.w(state[r + 'conv1.weight']), None, stride=2, padding=3))
+    y0 = tap('stem.conv', P.fwd(conv(P.fwd(x), P.w(state[r + 'conv1.weight']), None, stride=2, padding=3)))
     sc, sh = _bn_eval_coeff(state, r + 'bn1')
     pooled = F.max_pool2d(F.relu(y0 * sc[None, :, None, None] + sh[None, :, None, None]), kernel_size=3, stride=2, padding=1)
     tap('stem.pool', pooled)
@@ -170,14 +170,15 @@ def fcn_forward(state, x, training, points=True, update_buffers=True, taps=None)
     for li in range(1, 5):
         for bi in range(2):
             b = '%slayer%d.%d.' % (r, li, bi)
-            a1 = folded(cur, b + 'conv1.weight', None, b + 'bn1')
+            a1 = tap('layer%d.%d.a1' % (li, bi), folded(cur, b + 'conv1.weight', None, b + 'bn1'))
             identity = cur
             if (b + 'downsample.0.weight') in state:
-                identity = folded(cur, b + 'downsample.0.weight', None, b + 'downsample.1', relu=False)
+                identity = tap('layer%d.%d.yd' % (li, bi), folded(cur, b + 'downsample.0.weight', None, b + 'downsample.1', relu=False))
             cur = tap('layer%d.%d' % (li, bi), folded(a1, b + 'conv2.weight', None, b + 'bn2', identity=identity))
-    a1 = folded(cur, p + 'conv1.weight', p + 'conv1.bias', p + 'bn1')
+    a1 = tap('head.a1', folded(cur, p + 'conv1.weight', p + 'conv1.bias', p + 'bn1'))
     sc, sh = _bn_eval_coeff(state, p + 'bn2')
     z2 = conv(a1, P.w(state[p + 'conv2.weight']), state[p + 'conv2.bias']) * sc[None, :, None, None] + sh[None, :, None, None]
+    tap('head.z2', z2)
     a2 = F.relu(F.interpolate(z2, scale_factor=2, mode='bilinear', align_corners=True))
     q = F.interpolate(a2, scale_factor=2, mode='bilinear', align_corners=True)
     return conv(q, state[p + 'conv3.weight'], state[p + 'conv3.bias'])
