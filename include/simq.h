@@ -809,7 +809,7 @@ int simq_grid_waypoints(const uint8_t* d_grids, int64_t grids_bytes, const int32
  * maps; NULL when no problem tests the line) and d_closest (int32 [2][rows][cols] blocks; NULL when no problem snaps) -- each with its
  * extent, and per problem an element offset into each.  Several problems may share a map.  The window (box_*) is the caller's, as
  * for simq_grid_paths: it must hold every free cell, the kernel's pass over the grid gives status 2 when one lies outside, and
- * (box_rows + 2) * (box_cols + 2) <= SIMQ_GRID_PATH_MAX_BOX_CELLS.
+ * (box_rows + 2) * (box_cols + 2) <= SIMQ_GRID_PATH_MAX_BOX_CELLS; simq_action_waypoints_large below takes the windows over the cap.
  * Upstream status: d_upstream (n_upstream int32 words on the device; NULL with 0) as for simq_grid_distance_images_snapped: a problem
  * with upstream >= 0 whose word is not 0 gets that word as its status and count 0; nothing else of it is read or written.
  * Outputs per problem: int32 (i, j) waypoint pixels, source first, at pair way_offset of d_ways, at most way_capacity pairs;
@@ -838,6 +838,42 @@ int simq_action_waypoints(const uint8_t* d_cspace, int64_t cspace_bytes, const u
                           const int32_t* d_closest, int64_t closest_ints, const simq_action_waypoint_problem* problems, int n,
                           simq_action_waypoint_problem* d_problems, int32_t* d_ways, int64_t way_pairs, int32_t* d_counts,
                           int32_t* d_endpoints, const int32_t* d_upstream, int n_upstream, int32_t* d_status, void* stream);
+
+/* The same launch for windows of any size: the search state, and after the search the dense path and the kept flags, lie in a
+ * workspace of the caller's in global memory instead of LDS (the state and the carve-up of simq_grid_paths_large), so
+ * SIMQ_GRID_PATH_MAX_BOX_CELLS does not apply; the windows under the cap are accepted too.  Rules, front stages, the upstream word,
+ * outputs, the kernel's re-check and status words are those of simq_action_waypoints: for a problem both entry points accept, every
+ * byte either writes is equal.  No dynamic LDS.
+ * Limits: box_rows + 2 and box_cols + 2 at most 32 767, so that window coordinates stay below 2^15 and the simplification's products
+ * below 2^62 for any caller (a map simq_occupancy_maps_large writes has at most 2 050).  The dense path is not bounded by
+ * SIMQ_GRID_WAYPOINTS_MAX_PATH: it has at most as many points as the window has free cells, n <= box_rows * box_cols, which is what the
+ * workspace is laid out for, and the loop bounds of the simplification and the pruning follow n (at most n - 2 splits, 2 n verdicts,
+ * n lines).
+ * Workspace: as for simq_grid_paths_large -- problem p's state is the simq_action_waypoints_large_work_bytes(box_rows, box_cols) =
+ * simq_grid_paths_large_work_bytes(box_rows, box_cols) bytes from byte work_offset (a multiple of 16) on; after the search the path
+ * lies as 16-bit window pairs where the distances lay and the kept flags as a bit mask where the ring lay.  The kernel initialises
+ * what it reads; the content after the call is unspecified.  The host function gives -1 for a negative side, a side over 32 765 or
+ * box_rows * box_cols >= SIMQ_GRID_MAX_CELLS.
+ * Validation as for simq_action_waypoints, with the limit above in place of the cap, and the workspace rules of
+ * simq_grid_paths_large. */
+typedef struct simq_action_waypoint_large_problem {
+    int64_t cspace_offset;      /* the fields of simq_action_waypoint_problem, with the same meaning ... */
+    int64_t thin_offset;
+    int64_t closest_offset;
+    int64_t way_offset;
+    int64_t work_offset;        /* ... and the byte offset of the problem's search state in d_work, a multiple of 16 */
+    int32_t way_capacity;
+    int32_t rows, cols;
+    int32_t src_i, src_j, tgt_i, tgt_j;
+    int32_t box_i0, box_j0, box_rows, box_cols;
+    int32_t upstream;
+} simq_action_waypoint_large_problem;
+int64_t simq_action_waypoints_large_work_bytes(int32_t box_rows, int32_t box_cols);
+int simq_action_waypoints_large(const uint8_t* d_cspace, int64_t cspace_bytes, const uint8_t* d_thin, int64_t thin_bytes,
+                                const int32_t* d_closest, int64_t closest_ints, const simq_action_waypoint_large_problem* problems,
+                                int n, simq_action_waypoint_large_problem* d_problems, int32_t* d_ways, int64_t way_pairs,
+                                int32_t* d_counts, int32_t* d_endpoints, const int32_t* d_upstream, int n_upstream, int32_t* d_status,
+                                void* d_work, int64_t work_bytes, void* stream);
 
 /* ---- shortest-path distance queries: the point form of the distance images (envs.py:2506-2511 OccupancyMap.shortest_path_distance,
  * reached through Mapper.distance_to_receptacle, envs.py:2189-2194, by every partial reward; shortest_paths.pyx:150-158
@@ -1015,7 +1051,7 @@ int simq_intention_maps(const simq_intention_segment* segments, int n_segments, 
  * buffers and d_status disjoint from each other, from d_maps and from d_problems; several problems may share a room mask) and copied
  * to the caller's device buffer d_problems (n descriptors) on `stream`.  d_status[n] (int32): 0 = ok, 1 = the configuration space
  * has no free cell (the closest cells are all -1; both uint8 maps are valid), 2 = bad descriptor (the kernel checks again and writes
- * nothing else). */
+ * nothing else).  The planes lie in LDS, which bounds the sides; simq_occupancy_maps_large below takes the larger maps. */
 #define SIMQ_OCCUPANCY_MAX_DIM 256
 #define SIMQ_OCCUPANCY_MAX_RADIUS 16
 typedef struct simq_occupancy_problem {
@@ -1028,6 +1064,37 @@ typedef struct simq_occupancy_problem {
 int simq_occupancy_maps(const uint8_t* d_maps, int64_t maps_bytes, const simq_occupancy_problem* problems, int n,
                         simq_occupancy_problem* d_problems, uint8_t* d_cspace, uint8_t* d_thin, int64_t cspace_bytes, int32_t* d_closest,
                         int64_t closest_ints, int32_t* d_status, void* stream);
+
+/* The same three results for maps of up to SIMQ_OCCUPANCY_LARGE_MAX_DIM cells a side: the 16-bit plane of column distances, then of
+ * nearest free rows, lies in a workspace of the caller's in global memory instead of LDS, and the configuration space is read back
+ * from d_cspace where the kernel has just written it.  Rules, outputs, the kernel's re-check and the status words are those of
+ * simq_occupancy_maps: for a problem both entry points accept -- the maps under SIMQ_OCCUPANCY_MAX_DIM are accepted here too --
+ * every byte either writes is equal.  One workgroup per problem as there, its columns and pixels looped over the block; a pass over
+ * a map costs a few times what it costs in LDS, so this entry point is for the maps the other refuses.
+ * Limits: rows, cols in [1, SIMQ_OCCUPANCY_LARGE_MAX_DIM] and rows * cols < SIMQ_GRID_MAX_CELLS (what the distance images and the
+ * action waypoints behind this stage take); radii in [0, SIMQ_OCCUPANCY_MAX_RADIUS].
+ * Workspace: d_work (work_bytes bytes, 16-byte aligned) is the caller's; the library allocates nothing.  Problem p's plane is the
+ * simq_occupancy_maps_large_work_bytes(rows, cols) = (2 * rows * cols + 15) / 16 * 16 bytes from byte work_offset (a multiple of 16)
+ * on: one uint16 per cell (a row index no longer fits a byte), rounded up to 16.  The kernel initialises what it reads; the content
+ * after the call is unspecified.  simq_occupancy_maps_large_work_bytes is a host function of the two numbers alone (-1 for a shape
+ * outside the limits above).
+ * Validation as for simq_occupancy_maps with the limits above, and in addition: d_work not NULL and 16-byte aligned; every problem's
+ * range inside work_bytes at a non-negative multiple of 16; no two problems' ranges overlapping; d_work sharing no byte with any
+ * other buffer of the call. */
+#define SIMQ_OCCUPANCY_LARGE_MAX_DIM 2048
+typedef struct simq_occupancy_large_problem {
+    int64_t occupancy_offset;   /* the fields of simq_occupancy_problem, with the same meaning ... */
+    int64_t mask_offset;
+    int64_t out_offset;
+    int64_t work_offset;        /* ... and the byte offset of the problem's plane in d_work, a multiple of 16 */
+    int32_t rows, cols;
+    int32_t radius, thin_radius;
+} simq_occupancy_large_problem;
+int64_t simq_occupancy_maps_large_work_bytes(int32_t rows, int32_t cols);
+int simq_occupancy_maps_large(const uint8_t* d_maps, int64_t maps_bytes, const simq_occupancy_large_problem* problems, int n,
+                              simq_occupancy_large_problem* d_problems, uint8_t* d_cspace, uint8_t* d_thin, int64_t cspace_bytes,
+                              int32_t* d_closest, int64_t closest_ints, int32_t* d_status, void* d_work, int64_t work_bytes,
+                              void* stream);
 
 /* ---- observation maps: camera frames into the overhead and occupancy maps (Camera.capture_image, envs.py:1926-1954; the scatters of
  * Mapper.update, envs.py:2053-2061, and OccupancyMap.update, envs.py:2444-2449) ----------------------------------------------------

@@ -1,5 +1,5 @@
 // From a dense path to its waypoints, which grid_simplify.hip (grid_waypoints_kernel: a path of int32 grid pixels in global memory)
-// and action_waypoints.hip (action_waypoints_kernel: a path of 16-bit window pairs in LDS) share: skimage.measure.approximate_polygon
+// and action_waypoints.hip (action_waypoints_kernel: a path of 16-bit window pairs in LDS, or in its workspace) share: skimage.measure.approximate_polygon
 // decided in integers, then the pruning of the back half of GridGraph.shortest_path (shortest_paths.pyx:139-154).  The rule is stated
 // in include/simq.h; this header holds it once, over three functors, and nothing of an entry point:
 //   point(k) -> int2             point k of the path, 0 <= k < n, both coordinates in [0, 2^15)
@@ -46,8 +46,10 @@ __device__ __forceinline__ int next_kept(const uint32_t* keep, int after, int wo
 }
 
 // the waypoints of the n >= 1 points of a path: simplified at tolerance sqrt(t2), pruned, and the kept points given to `emit` last
-// first, those at or past `capacity` left out.  `keep` is LDS for (n + 31) / 32 words.  Returns 0, or 4 when a loop bound was passed
-// (cannot happen; nothing is emitted then); *total is the number of waypoints, whatever the capacity.  All of it wave-uniform.
+// first, those at or past `capacity` left out.  `keep` is (n + 31) / 32 words of LDS, or of global memory the workgroup alone uses
+// (action_waypoints_kernel<InHbm>): every store to it is followed by __syncthreads() before a load.  Returns 0, or 4 when a loop
+// bound was passed (cannot happen; nothing is emitted then); *total is the number of waypoints, whatever the capacity.  All of it
+// wave-uniform.
 template <typename Point, typename NotOne, typename Emit>
 __device__ __forceinline__ int waypoints(uint32_t* keep, int n, unsigned long long t2, int capacity, Point point, NotOne not_one,
                                          Emit emit, int lane, int* total_out) {

@@ -183,6 +183,9 @@ _SIGS = {
                                     c_void_p, c_void_p, c_void_p]),
     'simq_action_waypoints': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'simq_action_waypoints_large_work_bytes': (c_int64, [c_int, c_int]),
+    'simq_action_waypoints_large': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                            c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     'simq_grid_distance_queries': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                            c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     'simq_local_state_desc_bytes': (c_int64, [c_int, c_int, c_int, c_int]),
@@ -195,6 +198,9 @@ _SIGS = {
     'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                     c_void_p]),
+    'simq_occupancy_maps_large_work_bytes': (c_int64, [c_int, c_int]),
+    'simq_occupancy_maps_large': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                          c_void_p, c_int64, c_void_p]),
     'simq_observation_update': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     'simq_observation_update_sequences': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                                   c_int64, c_void_p, c_void_p]),

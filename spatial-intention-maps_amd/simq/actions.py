@@ -32,7 +32,50 @@ class ActionWaypointProblem(ctypes.Structure):
                                               'box_cols', 'upstream')]
 
 
+class ActionWaypointLargeProblem(ctypes.Structure):
+    """simq_action_waypoint_large_problem of include/simq.h: ActionWaypointProblem's fields plus work_offset."""
+    _fields_ = ActionWaypointProblem._fields_[:4] + [('work_offset', ctypes.c_int64)] + ActionWaypointProblem._fields_[4:]
+
+
 ACTION_PROBLEM = np.dtype(ActionWaypointProblem)
+ACTION_LARGE_PROBLEM = np.dtype(ActionWaypointLargeProblem)
+
+
+def large_work_bytes(box_rows, box_cols):
+    """simq_action_waypoints_large_work_bytes of include/simq.h restated: simq_grid_paths_large's state -- fp32 distances, one-byte
+    parents and flags over the window plus its halo, a ring of window cells + 1 32-bit entries, rounded up to 16."""
+    cells = (box_rows + 2) * (box_cols + 2)
+    return (6 * cells + 4 * (box_rows * box_cols + 1) + 15) // 16 * 16
+
+
+def split_by_window(boxes):
+    """(fit, over): the problems whose window (i0, j0, rows, cols) plus its halo has at most MAX_BOX_CELLS cells --
+    simq_action_waypoints takes them, its search state in LDS -- and the others, for simq_action_waypoints_large; both ascending."""
+    fit = [p for p, b in enumerate(boxes) if (int(b[2]) + 2) * (int(b[3]) + 2) <= MAX_BOX_CELLS]
+    over = [p for p, b in enumerate(boxes) if (int(b[2]) + 2) * (int(b[3]) + 2) > MAX_BOX_CELLS]
+    return fit, over
+
+
+def entry_calls(n_fit, n):
+    """The entry points a call over n problems makes when the first n_fit fit the LDS cap: [(name, first, last + 1)], an empty part
+    left out."""
+    return [c for c in (('simq_action_waypoints', 0, n_fit), ('simq_action_waypoints_large', n_fit, n)) if c[2] > c[1]]
+
+
+def _check_large_windows(large_windows):
+    if not isinstance(large_windows, bool):
+        raise ValueError('large_windows must be True or False, got %r' % (large_windows,))
+    return large_windows
+
+
+def launch_order(problems, large_windows):
+    """(order, n_fit) of an ACTION_PROBLEM table: the problems in the order they are launched -- with large_windows those over the LDS
+    cap behind the others, for simq_action_waypoints_large; without it all as they come, for simq_action_waypoints to take or refuse."""
+    if not large_windows:
+        return np.arange(len(problems)), len(problems)
+    fit, over = split_by_window(np.stack([problems[n] for n in ('box_i0', 'box_j0', 'box_rows', 'box_cols')], axis=1).tolist())
+    return np.asarray(fit + over, np.int64), len(fit)
+
 
 #: replaces the device when set: callable(problems: ACTION_PROBLEM table) -> (status int32 [P], counts int32 [P], endpoints int32
 #: [P, 4], waypoint pixels int32 [sum of the counts of the traced problems, 2]); the tests pin the host arithmetic through it without
@@ -176,10 +219,14 @@ def free_box(grid):
     return int(ii.min()), int(jj.min()), int(ii.max() - ii.min() + 1), int(jj.max() - jj.min() + 1)
 
 
-def run_problems(problems, bases, upstream=None, capacity=WAY_CAPACITY, what='store_new_actions'):
+def run_problems(problems, bases, upstream=None, capacity=WAY_CAPACITY, what='store_new_actions', large_windows=False, work=None):
     """The device side of a call: one simq_action_waypoints over the ACTION_PROBLEM table `problems` (way_offset and way_capacity are
     set here), one read-back of status words, counts, end pixels, waypoints and the upstream words, and one more round for the
     problems whose waypoints did not fit `capacity` pairs.  bases: (cspace, thin or None, closest or None) flat device tensors.
+    large_windows: the problems whose window is over the LDS cap go to simq_action_waypoints_large, queued behind the launch of the
+    others and before the one read-back; both write their own problems' ranges of the same buffers, and the second round works over
+    both parts in the same way.  work: (uint8 device tensor, int64 byte offset of each problem's search state in it) for the large
+    part; omitted, a workspace is allocated per launch.
     Returns (status, counts, endpoints [P, 4], pixels [sum(counts), 2], words) as host arrays: counts is 0 for every problem that was
     not traced, status 3 does not come back, and words holds every problem's upstream word (0 without one) -- a passed-on word is told
     from the entry's own codes by it (include/simq.h)."""
@@ -188,28 +235,44 @@ def run_problems(problems, bases, upstream=None, capacity=WAY_CAPACITY, what='st
     cspace, thin, closest = bases
     dev = cspace.device
 
-    def launch(probs, cap, up):
+    def launch(probs, cap, up, work):
         P = len(probs)
         probs['way_capacity'] = cap
-        probs['way_offset'] = _starts(probs['way_capacity'].astype(np.int64))
+        order, n_fit = launch_order(probs, large_windows)            # (the launches in this order; the results back in the problems')
+        probs['way_offset'][order] = _starts(probs['way_capacity'][order].astype(np.int64))
         pairs = int(probs['way_capacity'].sum())
         n_up = 0 if up is None else up.numel()
         base = 6 * P + n_up
         base += base % 2                                             # the waypoints start on an 8-byte boundary
         small = torch.empty(base + 2 * pairs, dtype=torch.int32, device=dev)          # status | counts | end pixels | upstream | waypoints
-        d_probs = torch.empty(probs.nbytes, dtype=torch.uint8, device=dev)
-        lib.call('simq_action_waypoints', ptr(cspace), ctypes.c_int64(cspace.numel()), ptr(thin), ctypes.c_int64(0 if thin is None else thin.numel()),
-                 ptr(closest), ctypes.c_int64(0 if closest is None else closest.numel()), as_ctypes(probs, ActionWaypointProblem), P,
-                 ptr(d_probs), ptr(small[base:]), ctypes.c_int64(pairs), ptr(small[P:2 * P]), ptr(small[2 * P:6 * P]), ptr(up), n_up,
-                 ptr(small[:P]), stream_ptr(dev))
+        for name, a, b in entry_calls(n_fit, P):
+            extra = ()
+            table, struct = np.ascontiguousarray(probs[order[a:b]]), ActionWaypointProblem
+            if name == 'simq_action_waypoints_large':
+                small_table, table, struct = table, np.zeros(b - a, ACTION_LARGE_PROBLEM), ActionWaypointLargeProblem
+                for field in ACTION_PROBLEM.names:
+                    table[field] = small_table[field]
+                if work is None:
+                    need = [large_work_bytes(int(r), int(c)) for r, c in zip(table['box_rows'], table['box_cols'])]
+                    table['work_offset'] = _starts(np.asarray(need, np.int64))
+                    space = torch.empty(int(sum(need)), dtype=torch.uint8, device=dev)
+                else:
+                    space, table['work_offset'] = work[0], np.asarray(work[1], np.int64)[order[a:b]]
+                extra = (ptr(space), ctypes.c_int64(space.numel()))
+            d_probs = torch.empty(table.nbytes, dtype=torch.uint8, device=dev)
+            lib.call(name, ptr(cspace), ctypes.c_int64(cspace.numel()), ptr(thin), ctypes.c_int64(0 if thin is None else thin.numel()),
+                     ptr(closest), ctypes.c_int64(0 if closest is None else closest.numel()), as_ctypes(table, struct), b - a,
+                     ptr(d_probs), ptr(small[base:]), ctypes.c_int64(pairs), ptr(small[P + a:P + b]), ptr(small[2 * P + 4 * a:2 * P + 4 * b]),
+                     ptr(up), n_up, ptr(small[a:b]), *extra, stream_ptr(dev))
         if n_up:
             small[6 * P:6 * P + n_up].copy_(up)
         host = small.cpu().numpy()                                    # the one read-back of the round
-        return (host[:P].copy(), host[P:2 * P].copy(), host[2 * P:6 * P].reshape(P, 4).copy(), host[base:].reshape(-1, 2),
+        back = np.argsort(order)
+        return (host[:P][back], host[P:2 * P][back], host[2 * P:6 * P].reshape(P, 4)[back], host[base:].reshape(-1, 2),
                 host[6 * P:6 * P + n_up])
 
     probs = np.ascontiguousarray(problems)
-    status, counts, ends, ways, up = launch(probs, capacity, upstream)
+    status, counts, ends, ways, up = launch(probs, capacity, upstream, work)
     words = np.where(probs['upstream'] >= 0, up[np.maximum(probs['upstream'], 0)], 0).astype(np.int32) if len(up) else np.zeros(len(probs), np.int32)
     counts = np.where(((status == TRACED) | (status == CAPACITY)) & (words == 0), counts, 0)          # (nothing is counted for any other status)
     at = _starts(counts.astype(np.int64))
@@ -221,24 +284,28 @@ def run_problems(problems, bases, upstream=None, capacity=WAY_CAPACITY, what='st
         again = probs[short].copy()
         again['src_i'], again['src_j'], again['tgt_i'], again['tgt_j'] = ends[short].T
         again['thin_offset'] = again['closest_offset'] = again['upstream'] = -1
-        status2, counts2, _, ways2, _ = launch(again, counts[short], None)
+        status2, counts2, _, ways2, _ = launch(again, counts[short], None, None if work is None else (work[0], np.asarray(work[1])[short]))
         if (status2 != TRACED).any() or (counts2 != counts[short]).any():
             raise SimqError('%s: the second round of simq_action_waypoints ended with status %s and counts %s for %s'
                             % (what, status2[:8].tolist(), counts2[:8].tolist(), counts[short][:8].tolist()))
         status[short] = TRACED
-        pixels[ragged(at[short], counts[short])] = ways2
+        pixels[ragged(at[short], counts[short])] = ways2[ragged(again['way_offset'], counts[short])]
     return status, counts, ends, pixels, words
 
 
 def store_new_actions(cspace, cspace_thin, closest, positions, headings, actions, robot_types, map_index=None,
-                      use_shortest_path_movement=True, upstream=None, window=None):
+                      use_shortest_path_movement=True, upstream=None, window=None, large_windows=False):
     """Robot.store_new_action for P robots on loose tensors: the maps simq.occupancy_maps returned (cspace, cspace_thin: M uint8 maps
     each as one [M, rows, cols] tensor or a list; closest: M int32 [2, rows, cols]), positions float64 [P, 2] (or P tuples), headings
     float64 [P], actions P integers, robot_types P names (or one for all); map_index: the map of each robot (robot p uses map p when
     omitted).  upstream: an int32 device tensor with one word per map, e.g. the status words of simq.occupancy_maps: a robot whose
     map's word is not 0 is not searched and is reported.  window: (i0, j0, rows, cols) per map, or one for all, that holds every free
     cell of the configuration space; omitted, host maps are measured on the host and device maps once each on the device (the
-    reduction and read-back BatchedMapper.store_new_actions does without).  Returns NewActions."""
+    reduction and read-back BatchedMapper.store_new_actions does without).  large_windows: a window of more than MAX_BOX_CELLS cells
+    with its halo is refused (SimqError, nothing launched) unless this is True; then those robots go to simq_action_waypoints_large,
+    whose search state lies in a workspace in device memory allocated here, the others to simq_action_waypoints as before, with the
+    one read-back behind both.  Returns NewActions."""
+    _check_large_windows(large_windows)
     positions, headings, actions, robot_types, given = _as_inputs(positions, headings, actions, robot_types)
     P = len(positions)
     channels, reach = constants_of(robot_types)
@@ -292,11 +359,11 @@ def store_new_actions(cspace, cspace_thin, closest, positions, headings, actions
     box = np.asarray([window[k] for k in map_index], np.int32).reshape(P, 4)
     probs['box_i0'], probs['box_j0'], probs['box_rows'], probs['box_cols'] = box.T
     over = np.flatnonzero((box[:, 2].astype(np.int64) + 2) * (box[:, 3] + 2) > MAX_BOX_CELLS)
-    if over.size:
+    if over.size and not large_windows:
         raise SimqError('store_new_actions: the window of map %d is %d x %d cells, with its halo over SIMQ_GRID_PATH_MAX_BOX_CELLS = %d'
                         % (map_index[over[0]], box[over[0], 2], box[over[0], 3], MAX_BOX_CELLS))
     probs['upstream'] = map_index if upstream is not None else -1
-    status, counts, _, pixels, words = run_problems(probs, bases, upstream)
+    status, counts, _, pixels, words = run_problems(probs, bases, upstream, **({'large_windows': True} if large_windows else {}))
     bad = np.flatnonzero((words != 0) | ((status != TRACED) & (status != STRAIGHT)))
     codes = status[bad]
     if bad.size:

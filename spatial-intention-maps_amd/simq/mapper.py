@@ -15,6 +15,9 @@ status words on the device; the call reads them back once, at its end.  What let
 the snapped distance images (include/simq.h): a mapper whose configuration space has no free cell -- its closest cells are undefined
 -- is not searched.  ``store_new_actions`` is Robot.store_new_action for the deciding robots: one simq_action_waypoints launch on the same
 tensors, the float64 arithmetic on the host.  Douglas-Peucker by scikit-image stays on the host (section 13).
+simq_occupancy_maps and simq_action_waypoints keep their state in LDS, which bounds a room (a padded map of 256 cells a side, a
+room-mask box of 20 000 cells with its halo); with large_rooms=True the mappers over a bound go to simq_occupancy_maps_large and
+simq_action_waypoints_large, the same kernels with that state in workspaces of this object's in device memory (section 24).
 """
 import collections
 import collections.abc
@@ -455,14 +458,23 @@ class BatchedMapper:
     ([rows_m, cols_m], [2, rows_m, cols_m]) into those buffers.  `occupancy_status` int32 [M] holds the status word of each mapper's
     last configuration space (NOT_UPDATED before the first); `distance_to_receptacle_maps` (use_distance_to_receptacle_map) one
     fp32 [rows, cols] device map per environment (environments of one room and receptacle share it).  `pending` int64 [M] counts the
-    frames `defer` holds of each mapper until `flush` applies them."""
+    frames `defer` holds of each mapper until `flush` applies them.
+
+    large_rooms: without it a room whose padded map has a side over 256 cells is refused by update and flush, and one whose
+    room-mask box has more than 20 000 cells with its halo by store_new_actions, both by the library.  With it the constructor decides
+    per mapper, from the shapes and the room masks' boxes, which entry point each stage uses (`occupancy_entry`, `action_entry`: one
+    name per mapper) and allocates the two workspaces once; update / flush and store_new_actions then make at most two launches per
+    stage, the mappers under the caps first, and a set of mappers on both sides of a cap works as one."""
 
     def __init__(self, room_width, room_length, robot_types, robot_masks, group_indices=None, receptacle_position=None, *,
                  use_robot_map=True, use_distance_to_receptacle_map=False, use_shortest_path_to_receptacle_map=False,
                  use_shortest_path_map=False, use_history_map=False, use_intention_map=False, use_intention_channels=False,
                  intention_map_encoding='ramp', intention_map_scale=1.0, intention_map_line_thickness=2, intention_channel_encoding='spatial',
-                 intention_channel_nonspatial_scale=0.1, distance_to_receptacle_map_scale=0.25, shortest_path_map_scale=0.25, seg_values=None):
+                 intention_channel_nonspatial_scale=0.1, distance_to_receptacle_map_scale=0.25, shortest_path_map_scale=0.25, seg_values=None, large_rooms=False):
         given = locals()
+        if not isinstance(large_rooms, bool):
+            raise ValueError('large_rooms must be True or False, got %r' % (large_rooms,))
+        self.large_rooms = large_rooms
         self.flags = {f: bool(given[f]) for f in FLAGS}
         try:
             self.robot_types = [[str(t) for t in env] for env in robot_types]
@@ -536,12 +548,38 @@ class BatchedMapper:
         self._at = np.concatenate([[0], np.cumsum(cells)]).tolist()                       # cell offset of mapper m's maps; [M]: all cells
         self._pending = [[] for _ in range(M)]             # the deferred frames of every mapper in capture order (_Deferred)
         self._staging = _Staging()
+        self._route()
 
         # the device tensors come after the argument checks, which need no device; without one the object still checks the arguments
         # of its calls, and then says so
         self.device, self.stage_maps = None, {}
         if torch.cuda.is_available():
             self._allocate()
+
+    def _route(self):
+        """Which entry point each mapper's occupancy maps and action waypoints go through, and where its state lies in the two
+        workspaces: host constants of the shapes and the room masks' boxes.  Without large_rooms every mapper takes the LDS entries,
+        which refuse what they do not hold."""
+        M = self.num_mappers
+        self.occupancy_entry, self.action_entry = ['simq_occupancy_maps'] * M, ['simq_action_waypoints'] * M
+        self._occupancy_work_at, self._action_work_at = np.zeros(M + 1, np.int64), np.zeros(M + 1, np.int64)
+        if not self.large_rooms:
+            return
+        from .actions import split_by_window
+        for m in occupancy.split_by_shape(self.shapes)[1]:
+            self.occupancy_entry[m] = 'simq_occupancy_maps_large'
+        boxes = self._action_constants()['box']
+        for m in split_by_window(boxes.tolist())[1]:
+            self.action_entry[m] = 'simq_action_waypoints_large'
+        def need(fn, a, b):                                                               # (the exported host functions: no device)
+            return int(fn(int(a), int(b)))
+        self._occupancy_work_at[1:] = np.cumsum([need(lib.c.simq_occupancy_maps_large_work_bytes, *self.shapes[m])
+                                                 if self.occupancy_entry[m].endswith('large') else 0 for m in range(M)])
+        self._action_work_at[1:] = np.cumsum([need(lib.c.simq_action_waypoints_large_work_bytes, boxes[m][2], boxes[m][3])
+                                              if self.action_entry[m].endswith('large') else 0 for m in range(M)])
+        if (np.diff(self._occupancy_work_at) < 0).any() or (np.diff(self._action_work_at) < 0).any():
+            raise ValueError('large_rooms: a room of %s padded cells is over what simq_occupancy_maps_large and simq_action_waypoints_large '
+                             'take (sides up to %d, fewer than 2^22 cells)' % (sorted(set(self.shapes))[-1], occupancy.LARGE_MAX_DIM))
 
     def _allocate(self):
         dev = self.device = _batch.device('batched mappers')
@@ -562,6 +600,10 @@ class BatchedMapper:
         self._thin = torch.zeros(total, dtype=torch.uint8, device=dev)
         self._closest = torch.zeros(2 * total, dtype=torch.int32, device=dev)
         self.occupancy_status = torch.full((M,), NOT_UPDATED, dtype=torch.int32, device=dev)
+        # the workspaces of the large entries (large_rooms): every such mapper's state at its own offset, so any set of mappers may be
+        # named in one call; the kernels initialise what they read
+        self._occupancy_work = torch.empty(int(self._occupancy_work_at[-1]), dtype=torch.uint8, device=dev) if self._occupancy_work_at[-1] else None
+        self._action_work = torch.empty(int(self._action_work_at[-1]), dtype=torch.uint8, device=dev) if self._action_work_at[-1] else None
         self.masks = torch.from_numpy(self.mask_bank).to(dev)
         self.uniform = len(set(self.shapes)) == 1
 
@@ -656,19 +698,23 @@ class BatchedMapper:
             raise SimqError('BatchedMapper.update: ' + '; '.join(said))
 
     def _enqueue_occupancy(self, ms):
-        """simq_occupancy_maps over the mappers `ms`: queues the launch, stores its status words in `occupancy_status` and returns them
-        as a device tensor [len(ms)]."""
+        """simq_occupancy_maps over the mappers `ms` -- with large_rooms simq_occupancy_maps over those within its cap, then
+        simq_occupancy_maps_large over the others: queues the launches, stores their status words in `occupancy_status` and returns
+        them as a device tensor [len(ms)] in the order of `ms`."""
         P, dev, M = len(ms), self.device, self.num_mappers
-        probs = (occupancy.OccupancyProblem * P)(*[occupancy.OccupancyProblem(self._at[m], self._mask_at[m], self._at[m], self.shapes[m][0],
-                                                                               self.shapes[m][1], self.radius[m], self.thin_radius) for m in ms])
-        d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
-        whole = ms == list(range(M))
+        fit = [p for p, m in enumerate(ms) if not self.occupancy_entry[m].endswith('large')]
+        order = fit + [p for p, m in enumerate(ms) if self.occupancy_entry[m].endswith('large')]
+        sent = [ms[p] for p in order]
+        fields = [(self._at[m], self._mask_at[m], self._at[m], self.shapes[m][0], self.shapes[m][1], self.radius[m], self.thin_radius)
+                  for m in sent]
+        whole = sent == list(range(M))
         st_occ = self.occupancy_status if whole else torch.empty(P, dtype=torch.int32, device=dev)
-        lib.call('simq_occupancy_maps', ptr(self._bytes), ctypes.c_int64(self._bytes.numel()), probs, P, ptr(d_probs), ptr(self._cspace),
-                 ptr(self._thin), ctypes.c_int64(self._cspace.numel()), ptr(self._closest), ctypes.c_int64(self._closest.numel()), ptr(st_occ),
-                 stream_ptr(dev))
+        occupancy.call_entries(fields, len(fit), self._bytes, (self._cspace, self._thin, self._closest), st_occ, dev,
+                               self._occupancy_work, [int(self._occupancy_work_at[m]) for m in sent[len(fit):]])
         if not whole:
-            self.occupancy_status[torch.as_tensor(ms, dtype=torch.int64).to(dev)] = st_occ
+            self.occupancy_status[torch.as_tensor(sent, dtype=torch.int64).to(dev)] = st_occ
+        if order != list(range(P)):
+            st_occ = st_occ[torch.as_tensor(np.argsort(order), dtype=torch.int64).to(dev)]
         return st_occ
 
     # ---- deferred frames: several Mapper.update calls of a mapper applied by one launch ------------------------------------------
@@ -1150,7 +1196,7 @@ class BatchedMapper:
         ms = self._mappers(mappers)
         self._nothing_pending(ms, 'shortest_paths')
         return shortest_paths(self.configuration_space, self.cspace_thin, self.closest_cspace_indices, source_positions, target_positions,
-                              ms, simplify)
+                              ms, simplify, **({'large_windows': True} if self.large_rooms else {}))
 
     # ---- Robot.store_new_action on the stored tensors --------------------------------------------------------------------------
     def _action_constants(self):
@@ -1217,8 +1263,11 @@ class BatchedMapper:
         if act.search is None and self.device is None:
             self._allocate()
         bases = None if self.device is None else (self._cspace, self._thin, self._closest)
+        large = {}
+        if self.large_rooms:                                         # (the default call is the call as it was)
+            large = dict(large_windows=True, work=None if self.device is None else (self._action_work, self._action_work_at[ms]))
         status, counts, _, pixels, words = act.run_problems(probs, bases, None if self.device is None else self.occupancy_status,
-                                                            what='BatchedMapper.store_new_actions')
+                                                            what='BatchedMapper.store_new_actions', **large)
         bad = np.flatnonzero((words != 0) | ((status != act.TRACED) & (status != act.STRAIGHT)))
         codes = status[bad]
         if bad.size:

@@ -5,7 +5,9 @@ with a disk of the robot's radius), the closest free cell of every pixel (``scip
 return_indices=True)``, through which every shortest-path source pixel goes, envs.py:2522-2523) and a thin configuration space for the
 straight-line test.  ``simq_occupancy_maps`` (csrc/occupancy_maps.hip) computes the three for many maps in one launch, element for
 element equal to that sequence; the rules and scipy's tie rule are stated in include/simq.h.  A row of the configuration space is a
-grid ``simq.grid_distance_images`` takes as it is.
+grid ``simq.grid_distance_images`` takes as it is.  The kernel keeps its planes in LDS, which bounds a map's sides by MAX_DIM;
+large_maps=True sends the maps over that bound to ``simq_occupancy_maps_large``, the same passes with the plane in a workspace in
+device memory.
 """
 import collections
 import ctypes
@@ -17,6 +19,7 @@ from . import _batch
 from ._lib import SimqError, lib, ptr, stream_ptr
 
 MAX_DIM = 256                    # SIMQ_OCCUPANCY_MAX_DIM of include/simq.h
+LARGE_MAX_DIM = 2048             # SIMQ_OCCUPANCY_LARGE_MAX_DIM
 MAX_RADIUS = 16                  # SIMQ_OCCUPANCY_MAX_RADIUS
 
 OccupancyMaps = collections.namedtuple('OccupancyMaps', ('configuration_space', 'cspace_thin', 'closest_cspace_indices'))
@@ -28,7 +31,70 @@ class OccupancyProblem(ctypes.Structure):
                 ('rows', ctypes.c_int32), ('cols', ctypes.c_int32), ('radius', ctypes.c_int32), ('thin_radius', ctypes.c_int32)]
 
 
+class OccupancyLargeProblem(ctypes.Structure):
+    """simq_occupancy_large_problem of include/simq.h: OccupancyProblem's fields plus work_offset."""
+    _fields_ = OccupancyProblem._fields_[:3] + [('work_offset', ctypes.c_int64)] + OccupancyProblem._fields_[3:]
+
+
 MAPS = 'a sequence of 2-D uint8 maps or one [G, rows, cols] array'
+
+
+def large_work_bytes(rows, cols):
+    """simq_occupancy_maps_large_work_bytes of include/simq.h restated: one uint16 per cell, rounded up to 16."""
+    return (2 * rows * cols + 15) // 16 * 16
+
+
+def split_by_shape(shapes):
+    """(fit, over): the problems whose map (rows, cols) has both sides within MAX_DIM -- simq_occupancy_maps takes them, its planes
+    in LDS -- and the others, for simq_occupancy_maps_large; both ascending."""
+    fit = [p for p, s in enumerate(shapes) if s[0] <= MAX_DIM and s[1] <= MAX_DIM]
+    over = [p for p, s in enumerate(shapes) if s[0] > MAX_DIM or s[1] > MAX_DIM]
+    return fit, over
+
+
+def entry_calls(n_fit, n):
+    """The entry points a call over n problems makes when the first n_fit fit the LDS cap: [(name, first, last + 1)], an empty part
+    left out."""
+    return [c for c in (('simq_occupancy_maps', 0, n_fit), ('simq_occupancy_maps_large', n_fit, n)) if c[2] > c[1]]
+
+
+def _check_large_maps(large_maps):
+    if not isinstance(large_maps, bool):
+        raise ValueError('large_maps must be True or False, got %r' % (large_maps,))
+    return large_maps
+
+
+def launch_order(shapes, large_maps):
+    """(order, n_fit): the problems in the order they are launched -- with large_maps those over the LDS cap behind the others, for
+    simq_occupancy_maps_large; without it all as they come, for simq_occupancy_maps to take or refuse."""
+    if not large_maps:
+        return list(range(len(shapes))), len(shapes)
+    fit, over = split_by_shape(shapes)
+    return fit + over, len(fit)
+
+
+def call_entries(fields, n_fit, maps, outs, status, dev, work=None, work_at=None):
+    """Queues the call over `fields`, one (occupancy_offset, mask_offset, out_offset, rows, cols, radius, thin_radius) per problem in
+    launch order: the first n_fit through simq_occupancy_maps, the others through simq_occupancy_maps_large; both read `maps`, write
+    their own problems' ranges of the three tensors `outs` and their own words of `status` (int32 [len(fields)], launch order).
+    work, work_at: the workspace of the large part and each of its problems' byte offset in it; allocated here when omitted."""
+    cspace, thin, closest = outs
+    for name, a, b in entry_calls(n_fit, len(fields)):
+        extra = ()
+        if name == 'simq_occupancy_maps':
+            probs = (OccupancyProblem * (b - a))(*[OccupancyProblem(*f) for f in fields[a:b]])
+        else:
+            if work is None:
+                need = [large_work_bytes(f[3], f[4]) for f in fields[a:b]]
+                work_at = np.concatenate([[0], np.cumsum(need)]).astype(np.int64).tolist()
+                work = torch.empty(work_at[-1], dtype=torch.uint8, device=dev)
+            probs = (OccupancyLargeProblem * (b - a))(*[OccupancyLargeProblem(*f[:3], int(work_at[k]), *f[3:])
+                                                        for k, f in enumerate(fields[a:b])])
+            extra = (ptr(work), ctypes.c_int64(work.numel()))
+        d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+        lib.call(name, ptr(maps), ctypes.c_int64(maps.numel()), probs, b - a, ptr(d_probs), ptr(cspace), ptr(thin),
+                 ctypes.c_int64(min(cspace.numel(), thin.numel())), ptr(closest), ctypes.c_int64(closest.numel()), ptr(status[a:b]), *extra,
+                 stream_ptr(dev))
 
 
 def _radii(radius, P, what):
@@ -44,9 +110,11 @@ def _radii(radius, P, what):
     return [int(v) for v in values]
 
 
-def _enqueue(occupancy, room_masks, radius, thin_radius, room_index=None, out=None):
-    """occupancy_maps without its status read-back: checks, uploads and queues the launch, and returns (out, status, uniform, shapes)
-    with `out` the three output tensors and `status` the int32 device tensor the launch writes."""
+def _enqueue(occupancy, room_masks, radius, thin_radius, room_index=None, out=None, large_maps=False):
+    """occupancy_maps without its status read-back: checks, uploads and queues the launch (with large_maps the two of
+    launch_order), and returns (out, status, uniform, shapes) with `out` the three output tensors and `status` the int32 device
+    tensor of the status words in problem order."""
+    _check_large_maps(large_maps)
     occupancy, occupancy_block = _batch.as_maps(occupancy, 'occupancy', expects=MAPS)
     room_masks, _ = _batch.as_maps(room_masks, 'room_masks', expects=MAPS)
     P = len(occupancy)
@@ -88,16 +156,16 @@ def _enqueue(occupancy, room_masks, radius, thin_radius, room_index=None, out=No
             if not _batch.out_fits(t, d, dev, w if uniform else None, w[0]):
                 raise ValueError('out: %s must be a contiguous %s tensor on %s of %s' % (
                     name, str(d).replace('torch.', ''), dev, 'shape %s' % (w,) if uniform else 'at least %d elements' % w[0]))
-    probs = (OccupancyProblem * P)(*[OccupancyProblem(offsets[p], moff[room_index[p]], offsets[p], shapes[p][0], shapes[p][1], radii[p],
-                                                       thin_radii[p]) for p in range(P)])
-    d_probs = torch.empty(ctypes.sizeof(probs), dtype=torch.uint8, device=dev)
+    order, n_fit = launch_order(shapes, large_maps)
+    fields = [(offsets[p], moff[room_index[p]], offsets[p], shapes[p][0], shapes[p][1], radii[p], thin_radii[p]) for p in order]
     status = torch.empty(P, dtype=torch.int32, device=dev)
-    lib.call('simq_occupancy_maps', ptr(packed), ctypes.c_int64(packed.numel()), probs, P, ptr(d_probs), ptr(out[0]), ptr(out[1]),
-             ctypes.c_int64(min(out[0].numel(), out[1].numel())), ptr(out[2]), ctypes.c_int64(out[2].numel()), ptr(status), stream_ptr(dev))
+    call_entries(fields, n_fit, packed, out, status, dev)
+    if order != list(range(P)):                 # (the words back in problem order)
+        status = status[torch.as_tensor(np.argsort(order), dtype=torch.int64).to(dev)]
     return out, status, uniform, shapes
 
 
-def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, out=None):
+def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, out=None, large_maps=False):
     """The configuration spaces, thin configuration spaces and closest free cells of P occupancy maps in one launch, on the device.
 
     occupancy: P 2-D uint8 maps (C-contiguous numpy arrays or contiguous uint8 device tensors, read with a device copy), or one
@@ -112,9 +180,13 @@ def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, 
     write into, of those shapes (mixed shapes: uint8 of at least sum(rows_p * cols_p) elements twice and int32 of at least twice as
     many); every element is written.
 
+    A map with a side over MAX_DIM is refused (SimqError, nothing launched) unless large_maps is True.  Then the problems within
+    MAX_DIM x MAX_DIM go to simq_occupancy_maps as before and the others, sides up to LARGE_MAX_DIM, to simq_occupancy_maps_large with a
+    workspace allocated here (2 bytes a cell); both write their own ranges of the same outputs, and the results come in problem order.
+
     Raises ValueError for a wrong dtype, rank or contiguity, SimqError for what the library refuses (launching nothing) and for the
     problems whose configuration space has no free cell (their closest cells are undefined)."""
-    out, status, uniform, shapes = _enqueue(occupancy, room_masks, radius, thin_radius, room_index, out)
+    out, status, uniform, shapes = _enqueue(occupancy, room_masks, radius, thin_radius, room_index, out, large_maps)
     bad, codes = _batch.bad_problems(status)
     if bad.size:
         if (codes == 1).all():
@@ -127,8 +199,8 @@ def occupancy_maps(occupancy, room_masks, radius, thin_radius, room_index=None, 
                          _batch.views(out[2].view(-1), [(2,) + s for s in shapes]))
 
 
-def configuration_space(occupancy_map, room_mask, radius, thin_radius):
+def configuration_space(occupancy_map, room_mask, radius, thin_radius, large_maps=False):
     """The three results of OccupancyMap.update (envs.py:2453-2455) for one map, as numpy arrays: (configuration_space uint8
-    [rows, cols], cspace_thin uint8 [rows, cols], closest_cspace_indices int32 [2, rows, cols])."""
-    got = occupancy_maps([occupancy_map], [room_mask], radius, thin_radius)
+    [rows, cols], cspace_thin uint8 [rows, cols], closest_cspace_indices int32 [2, rows, cols]).  large_maps: as for occupancy_maps."""
+    got = occupancy_maps([occupancy_map], [room_mask], radius, thin_radius, large_maps=large_maps)
     return OccupancyMaps(*[t[0].cpu().numpy() for t in got])
