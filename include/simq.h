@@ -157,6 +157,16 @@ typedef struct simq_plan_options {
                                    * statements hold while every piece is at least 2^-126 in magnitude (operands from about 2^-103 up; what
                                    * happens below: DESIGN.md 4).  An Inf operand yields NaN (Inf - Inf in the split), not +-Inf as form 0.
                                    * Changes the round-off of those contractions (summation order and the dropped terms), nothing else. */
+    /* plain-bf16 plans: the element type of the INPUT */
+    int bf16_states;              /* 0.  1 = every entry point of this plan that takes states reads them as [batch][96][96][Cin] bf16 (uint16_t
+                                   * storage, NHWC, 2-byte aligned) behind its `const float*`: d_x of simq_forward / simq_forward_sync,
+                                   * simq_train_args.state / next_state, and the backward entries through the copy the grad-mode forward
+                                   * keeps (which is then a bf16 copy).  Only for plans whose first convolution runs stem_conv_bf16 -- precision
+                                   * SIMQ_PREC_BF16, stem_bf16 = 1 and 7 * num_input_channels <= 63 -- the creation of any other plan with
+                                   * the option fails: that convolution (and its weight gradient) rounds every fp32 input element to
+                                   * bf16 before anything else and nothing else reads the input, so a bf16 state that is the round-to-
+                                   * nearest-even of the fp32 state gives bit for bit what the fp32 state gives, in half the bytes.  The
+                                   * workspace of such a plan is never larger than the same plan's without the option. */
 } simq_plan_options;
 void simq_plan_options_default(simq_plan_options* options);
 int simq_plan_create_opts(int num_input_channels, int num_output_channels, int precision, const simq_plan_options* options,
@@ -218,7 +228,8 @@ int simq_workspace_tensor_ex(const simq_plan* plan, int batch, const char* name,
                              int* storage);
 
 /* ---- FCN.forward (networks.py:16-26) ---------------------------------------------------------
- * d_x      [batch][96][96][Cin] fp32 NHWC  (== the reference's HWC replay states, stacked)
+ * d_x      [batch][96][96][Cin] fp32 NHWC  (== the reference's HWC replay states, stacked); a plan with
+ *          simq_plan_options.bf16_states = 1 reads [batch][96][96][Cin] bf16 behind this pointer instead
  * d_q      [batch][Cout][96][96] fp32 NCHW
  * d_bnbuf  running stats; updated in place in TRAIN / TRAIN_NOGRAD modes (momentum 0.1,
  *          unbiased variance), read-only in EVAL.                                            */
@@ -229,6 +240,8 @@ int simq_forward(const simq_plan* plan, int mode, int batch, const float* d_para
  * d_workspace must be the one used by the matching simq_forward(mode=TRAIN) call.
  * d_dq     [batch][Cout][96][96] upstream gradient (dense).
  * d_grads  flat gradient buffer (param layout); OVERWRITTEN.
+ * (No backward entry takes states: the first convolution's weight gradient reads the copy the grad-mode forward left in the workspace --
+ * a bf16 copy, half the size, in a plan with simq_plan_options.bf16_states = 1.)
  * The matching forward must be a simq_forward / simq_forward_sync call: simq_train_step convolves the caller's minibatch IN PLACE and leaves
  * no copy of it in the workspace, so a backward entry point called on its own behind a simq_train_step would differentiate the first
  * convolution against whatever an earlier simq_forward left there (the Python host refuses that: FCN._train_workspace_for_backward). */
@@ -273,6 +286,7 @@ int simq_backward_onehot(const simq_plan* plan, int batch, const float* d_params
  * simq_comm_reduce_f64 is a ready-made `reduce` over a simq_comm (user = the communicator). */
 typedef int (*simq_reduce_fn)(void* user, double* d_buf, int64_t count, void* stream);
 typedef struct simq_sync { simq_reduce_fn reduce; void* user; int global_batch; int world_size; } simq_sync;
+/* (d_x as in simq_forward: bf16 states behind the pointer in a plan with simq_plan_options.bf16_states = 1) */
 int simq_forward_sync(const simq_plan* plan, int mode, int batch, const float* d_params, const void* d_wcache, float* d_bnbuf,
                       const float* d_x, float* d_q, void* d_workspace, void* stream, const simq_sync* sync);
 /* d_dq != NULL: dense upstream gradient (simq_backward_phase); d_dq == NULL: the one-hot form (simq_backward_onehot) */
@@ -316,7 +330,9 @@ int simq_clip_sgd_step(float* d_params, float* d_grads, float* d_momentum, int64
                        void* d_scratch, float* d_total_norm, void* stream);
 
 /* ---- replay minibatch gather (train.py:40-42,109,112) -------------------------------------------
- * d_ring [capacity][96][96][C] fp32; d_out[i] = d_ring[d_index[i]].                           */
+ * d_ring [capacity][96][96][C] fp32; d_out[i] = d_ring[d_index[i]].  item_floats a multiple of 4.
+ * The kernel moves bits, 16 bytes at a time: a ring of bf16 states (96 * 96 * C is even for every C, so an item is a whole number of
+ * 4-byte words) is gathered with item_floats = 96 * 96 * C / 2, the pointers standing for the bf16 arrays.                          */
 int simq_replay_gather(const float* d_ring, int64_t item_floats, const int64_t* d_index, int count,
                        float* d_out, void* stream);
 
@@ -325,7 +341,16 @@ int simq_replay_gather(const float* d_ring, int64_t item_floats, const int64_t* 
  * before anything is copied or launched (0 <= slot < pool_slots, none named twice, no written slot sharing a byte with d_src or
  * d_desc; 1 <= count <= 65535), then copied to d_desc (at least 8 * count bytes of device scratch, 8-byte aligned) on `stream`.
  * Any item size: rows move as 16-byte vectors where the two addresses allow it, float by float elsewhere.  A refusal writes
- * nothing. */
+ * nothing.  Bits are moved, not values: a pool of bf16 states takes item_floats = 96 * 96 * C / 2 (see simq_replay_gather). */
+
+/* ---- states fp32 <-> bf16 (simq_plan_options.bf16_states) ---------------------------------------------------------------
+ * simq_states_to_bf16: d_dst[i] = the bf16 nearest to d_src[i], ties to even -- the conversion the first convolution of a plain-bf16
+ * plan applies to an fp32 state: overflow goes to +-Inf, denormals and +-0 are kept, a NaN stays a NaN (its payload is not part of the
+ * contract).  simq_states_to_f32: the exact widening (the 16 bits become the high half of the float).  n >= 1 elements; fp32
+ * pointers 4-byte, bf16 pointers 2-byte aligned, the two arrays disjoint.  Eight elements move as 16-byte vectors where both addresses
+ * reach a 16-byte boundary together, one by one at the ends and where they never do. */
+int simq_states_to_bf16(const float* d_src, uint16_t* d_dst, int64_t n, void* stream);
+int simq_states_to_f32(const uint16_t* d_src, float* d_dst, int64_t n, void* stream);
 int simq_replay_scatter(const float* d_src, int64_t item_floats, const int64_t* slots, int count, float* d_pool, int64_t pool_slots,
                         void* d_desc, int64_t desc_bytes, void* stream);
 
@@ -347,7 +372,8 @@ typedef struct simq_train_args {
     const float* t_params; const void* t_wcache; float* t_bnbuf; void* t_ws;                                      /* target */
     const float* state; const float* next_state; const int64_t* action; const float* reward; const int32_t* nonfinal_pos;
                                  /* (read until the END of the call's stream work: the grad-mode forward convolves `state` in place and the first
-                                  * convolution's weight gradient reads it again -- no copy into the workspace) */
+                                  * convolution's weight gradient reads it again -- no copy into the workspace.  A plan with
+                                  * simq_plan_options.bf16_states = 1 reads [batch | num_nonfinal][96][96][Cin] bf16 behind both pointers) */
     float* q; float* q_next; float* q_tgt; float* dq;               /* [batch|num_nonfinal][Cout*96*96] scratch / outputs */
     float* nsv; float* vals; int64_t* best; float* q_sa; float* y; float* td; float* out4;
     void* opt_scratch; float* total_norm;
@@ -538,6 +564,14 @@ int simq_conv2d_fwd_stem_bf16(const float* d_x, const float* d_w_ohwi, uint16_t*
  * d_dw: [64][7][7][cin] fp32, overwritten.  d_scratch: min(512, ceil(batch * hin/2 * win/32 / 16)) * 64 * 49 * cin floats. */
 int simq_conv2d_wgrad_stem_bf16(const float* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
                                 float* d_scratch, void* stream);
+/* The same two operators over bf16 states -- d_x [batch][hin][win][cin] bf16, 2-byte aligned -- as a plan with
+ * simq_plan_options.bf16_states = 1 launches them: the same kernels with the element type of x as a template parameter, a lane's
+ * fragment one 16-byte load that assumes 2-byte alignment, the bf16 bits handed to the matrix core as they lie in memory.  Every other
+ * argument, the scratch sizes and the results' layout as above; on d_x = RNE(x) they return what the fp32-input operators return on x. */
+int simq_conv2d_fwd_stem_bf16_x16(const uint16_t* d_x, const float* d_w_ohwi, uint16_t* d_y, int batch, int hin, int win, int cin,
+                                  double* d_stats, void* d_scratch, void* stream);
+int simq_conv2d_wgrad_stem_bf16_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
+                                    float* d_scratch, void* stream);
 /* Weight gradient of the same convolution through the transform domain (dy / x transforms, 16 batched contractions over
  * the tiles, G^T dU G).  Additionally cin % 128 == 0 and cout % 128 == 0.  d_dw is overwritten.
  * the tiles, G^T dU G); uses F(4x4,3x3) when hin, win are multiples of 4 and batch*(hin/4)*(win/4) is a multiple of 16.
@@ -992,6 +1026,18 @@ int simq_local_state_images_slots(const simq_local_map* maps, int n_maps, const 
                                   int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels,
                                   int n_channels, const int64_t* slots, void* d_desc, int64_t desc_bytes, float* d_pool, int64_t pool_slots,
                                   void* stream);
+
+/* Both entries with bf16 images (a replay pool of bf16 states, simq_plan_options.bf16_states): the same descriptors, checks, kernel
+ * and d_desc sizes; d_out / d_pool hold bf16 elements (2-byte aligned, out_elems counts elements, a pool slot is 96 * 96 * C of them).
+ * The element stored is the fp32 value the fp32 entry stores -- a distance channel has its minimum subtracted in fp32 first -- rounded
+ * once to nearest even, with the conversion the first convolution of a plain-bf16 plan applies to an fp32 state. */
+int simq_local_state_images_bf16(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks, const simq_local_robot* robots,
+                                 int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels,
+                                 int n_channels, void* d_desc, int64_t desc_bytes, uint16_t* d_out, int64_t out_elems, void* stream);
+int simq_local_state_images_slots_bf16(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                                       const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                                       const simq_local_channel* channels, int n_channels, const int64_t* slots, void* d_desc,
+                                       int64_t desc_bytes, uint16_t* d_pool, int64_t pool_slots, void* stream);
 
 /* ---- global intention / history maps (Mapper._create_global_intention_or_history_map, envs.py:2301-2346, and the per-robot spatial
  * maps of Mapper._get_intention_channels, envs.py:2360-2366) ----------------------------------------------------------------------

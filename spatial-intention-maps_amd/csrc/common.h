@@ -248,6 +248,9 @@ int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, hipStream_t st
 int launch_stem_conv_bf16(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
 int stem_wgrad_bf16_slabs(int B, int H, int W);      // partial-sum slabs (64 * 49 * C floats each) the weight gradient needs as scratch
 int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream);
+// the same two kernels over bf16 states (simq_plan_options.bf16_states): x is [B][H][W][C] bf16, 2-byte aligned
+int launch_stem_conv_bf16_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
+int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream);
 int launch_stem_pool_bwd(const float* g, const float* pooled, const uint8_t* idx, float* dz, int B, int H, int W,
                          int C, hipStream_t stream, int g_bf16 = 0, const float* y = nullptr, const float* mean = nullptr,
                          const float* invstd = nullptr, double* red = nullptr, int y_bf16 = 0, int replicas = 1);   // red: fused BN-backward sums
@@ -310,6 +313,9 @@ int launch_replay_gather(const float* ring, int64_t item_floats, const int64_t* 
                          hipStream_t stream);
 int launch_replay_scatter(const float* src, int64_t item_floats, const int64_t* slots, int count, float* pool, int64_t pool_slots,
                           void* d_desc, int64_t desc_bytes, hipStream_t stream);
+// states fp32 <-> bf16 (round-to-nearest-even / the exact widening): simq_states_to_bf16 / simq_states_to_f32
+int launch_states_to_bf16(const float* src, uint16_t* dst, int64_t n, hipStream_t stream);
+int launch_states_to_f32(const uint16_t* src, float* dst, int64_t n, hipStream_t stream);
 
 // comm.hip: RCCL all-reduce on the communicator's own stream, ordered behind `producer` / awaited by `consumer`
 int comm_allreduce(simq_comm* c, void* buf, int64_t count, int dtype, hipStream_t producer);

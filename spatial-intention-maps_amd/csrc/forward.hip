@@ -98,8 +98,10 @@ int forward_impl(const Ctx& c, int mode, const float* d_x, float* d_q) {
     const Layout& L = c.L;
     const int B = c.B;
     // the input is kept only where a backward pass will read it again (the stem's weight gradient); the other forwards convolve d_x in place
+    // (a bf16_states plan: d_x holds bf16 elements and so does the copy)
+    const size_t x_elem = p->opt.bf16_states ? sizeof(uint16_t) : sizeof(float);
     if (mode == SIMQ_MODE_TRAIN && !c.x_ext)
-        SIMQ_CHECK_HIP(hipMemcpyAsync(c.f(L.x), d_x, (size_t)B * 96 * 96 * p->cin * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
+        SIMQ_CHECK_HIP(hipMemcpyAsync(c.f(L.x), d_x, (size_t)B * 96 * 96 * p->cin * x_elem, hipMemcpyDeviceToDevice, c.stream));
     if (mode != SIMQ_MODE_EVAL)
         SIMQ_CHECK_HIP(hipMemsetAsync(c.ws + L.red, 0, p->red_total * sizeof(double), c.stream));
     const int64_t rows = (int64_t)B * 576;
@@ -107,6 +109,11 @@ int forward_impl(const Ctx& c, int mode, const float* d_x, float* d_q) {
     Act x0; x0.f = (mode == SIMQ_MODE_TRAIN && !c.x_ext) ? c.f(L.x) : const_cast<float*>(d_x);
     const int stem16 = c.W.stem16 >= 0 ? 1 : 0;      // plain-bf16 plans: bf16 matrix cores, bf16 pre-BN output (stem_conv_bf16.hip)
     if (stem16) {
+        if (p->opt.bf16_states)     // (plan creation has made sure that such a plan takes this branch)
+            RC(launch_stem_conv_bf16_x16(reinterpret_cast<const uint16_t*>(x0.f), reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16),
+                                         reinterpret_cast<uint16_t*>(c.f(L.y0)), mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96,
+                                         p->cin, c.stream));
+        else
         RC(launch_stem_conv_bf16(x0.f, reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16), reinterpret_cast<uint16_t*>(c.f(L.y0)),
                                  mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96, p->cin, c.stream));
         if (mode != SIMQ_MODE_EVAL) RC(c.sync_reduce(c.red(p->stem_bn), 2 * (int64_t)p->stem_bn.C));

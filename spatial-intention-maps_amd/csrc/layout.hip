@@ -30,7 +30,8 @@ Layout make_layout(const simq_plan* p, int B) {
     int64_t off = 0;
     auto take = [&](int64_t bytes) { int64_t o = off; off = align_up(off + bytes, 256); return o; };
     const int64_t f = sizeof(float);
-    L.x = take((int64_t)B * 96 * 96 * p->cin * f);
+    // the grad-mode forward's copy of the minibatch, in the element type the plan's entry points read (bf16_states: bf16)
+    L.x = take((int64_t)B * 96 * 96 * p->cin * (p->opt.bf16_states ? (int64_t)sizeof(uint16_t) : f));
     L.y0 = take((int64_t)B * 48 * 48 * 64 * f);
     L.pooled = take((int64_t)B * 576 * 64 * f);
     L.idx = take((int64_t)B * 576 * 64);
@@ -206,6 +207,7 @@ void simq_plan_options_default(simq_plan_options* o) {
     o->wgrad_ksplit = 0; o->fwd_overlap = 2; o->wgrad_overlap = 4; o->plane_xcd = 1; o->wgrad_xcd_group = 1; o->tail_split = 0;
     o->early_target_after_block = 4;
     o->gemm_split = 1;
+    o->bf16_states = 0;
 }
 
 void simq_launch_opts_default(simq_launch_opts* o) {
@@ -248,6 +250,14 @@ int simq_plan_create_opts(int cin, int cout, int precision, const simq_plan_opti
     SIMQ_REQUIRE(precision >= SIMQ_PREC_FP32 && precision <= SIMQ_PREC_BF16, "plan_create: bad precision %d", precision);
     simq_plan* p = new simq_plan();
     p->cin = cin; p->cout = cout; p->precision = precision; p->opt = opt;
+    p->stem.cin = cin; p->stem.cout = 64; p->stem.k = 7; p->stem.stride = 2; p->stem.pad = 3;      // (what make_wlayout looks at; bd.conv sets it again)
+    if (opt.bf16_states != 0 && (opt.bf16_states != 1 || make_wlayout(p).stem16 < 0)) {
+        set_error("plan_create: bf16_states = %d needs a plan whose first convolution runs stem_conv_bf16: (1) precision SIMQ_PREC_BF16 "
+                  "(this plan: %d), (2) stem_bf16 = 1 (this plan: %d), (3) 7 * num_input_channels <= 63 (this plan: %d channels); every "
+                  "other plan keeps fp32 states", opt.bf16_states, precision, opt.stem_bf16, cin);
+        delete p;
+        return -1;
+    }
     Builder bd{p};
     bd.conv(p->stem, "resnet18.conv1", cin, 64, 7, 2, 3, false, false);
     bd.bn(p->stem_bn, "resnet18.bn1", 64);

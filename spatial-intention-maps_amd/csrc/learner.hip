@@ -190,6 +190,58 @@ __global__ void __launch_bounds__(256) replay_scatter_kernel(const float* __rest
     }
 }
 
+// ---- states fp32 <-> bf16 (simq_plan_options.bf16_states: a replay pool of bf16 states) ------------------------------------------------
+// to_bf16 is the conversion the stem kernels apply to an fp32 state, (__bf16)v: v_cvt_pk_bf16_f32 under the kernels' float mode (round to
+// nearest even, denormals kept, overflow to +-Inf, a NaN stays a NaN).  to_f32 is the exact widening: the 16 bits become the high half.
+// Groups of 8 elements move as 16-byte vectors (two float4 against one uint4) where BOTH addresses reach a 16-byte boundary after the
+// same number of elements; the elements before the first such group and behind the last, or all of them when the two addresses never
+// agree, move one by one.
+__device__ __forceinline__ uint32_t bf16_pair(float a, float b) {
+    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)b) << 16);
+}
+__device__ __forceinline__ float bf16_widen(uint32_t bits16) { return __builtin_bit_cast(float, bits16 << 16); }
+
+// elements before the vector body (n: no body) for a 4-byte-element pointer f and a 2-byte-element pointer h that advance together
+__device__ __forceinline__ int64_t states_head(const void* f, const void* h, int64_t n) {
+    const int64_t a = (int64_t)(((uintptr_t)f & 15) >> 2), b = (int64_t)(((uintptr_t)h & 15) >> 1);      // a: 0..3 floats, b: 0..7 halves past a boundary
+    if (((b - a) & 3) != 0) return n;
+    const int64_t head = (8 - b) & 7;
+    return head < n ? head : n;
+}
+
+__global__ void __launch_bounds__(256) states_to_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n) {
+    const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, lanes = (int64_t)gridDim.x * blockDim.x;
+    const int64_t head = states_head(src, dst, n), n8 = (n - head) / 8;
+    const float4* s4 = reinterpret_cast<const float4*>(src + head);
+    uint4* d4 = reinterpret_cast<uint4*>(dst + head);
+    for (int64_t i = lane; i < n8; i += lanes) {
+        const float4 lo = s4[2 * i], hi = s4[2 * i + 1];
+        d4[i] = make_uint4(bf16_pair(lo.x, lo.y), bf16_pair(lo.z, lo.w), bf16_pair(hi.x, hi.y), bf16_pair(hi.z, hi.w));
+    }
+    const int64_t body_end = head + n8 * 8, rest = head + (n - body_end);
+    for (int64_t i = lane; i < rest; i += lanes) {                       // the head, then the tail
+        const int64_t at = i < head ? i : body_end + (i - head);
+        dst[at] = __builtin_bit_cast(uint16_t, (__bf16)src[at]);
+    }
+}
+
+__global__ void __launch_bounds__(256) states_to_f32_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, int64_t n) {
+    const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, lanes = (int64_t)gridDim.x * blockDim.x;
+    const int64_t head = states_head(dst, src, n), n8 = (n - head) / 8;
+    const uint4* s4 = reinterpret_cast<const uint4*>(src + head);
+    float4* d4 = reinterpret_cast<float4*>(dst + head);
+    for (int64_t i = lane; i < n8; i += lanes) {
+        const uint4 v = s4[i];
+        d4[2 * i] = make_float4(bf16_widen(v.x & 0xffffu), bf16_widen(v.x >> 16), bf16_widen(v.y & 0xffffu), bf16_widen(v.y >> 16));
+        d4[2 * i + 1] = make_float4(bf16_widen(v.z & 0xffffu), bf16_widen(v.z >> 16), bf16_widen(v.w & 0xffffu), bf16_widen(v.w >> 16));
+    }
+    const int64_t body_end = head + n8 * 8, rest = head + (n - body_end);
+    for (int64_t i = lane; i < rest; i += lanes) {
+        const int64_t at = i < head ? i : body_end + (i - head);
+        dst[at] = bf16_widen(src[at]);
+    }
+}
+
 // ---- intention-prediction head (train.py:143-158, policies.py:97-117) ---------------------------------------------
 // BCEWithLogitsLoss (mean) and its gradient:  l = max(x,0) - x*t + log(1 + exp(-|x|)) ;  dl/dx = (sigmoid(x) - t) / N
 __global__ void __launch_bounds__(256) bce_logits_kernel(const float* __restrict__ x, const float* __restrict__ t, size_t n,
@@ -314,6 +366,24 @@ int launch_replay_gather(const float* ring, int64_t item_floats, const int64_t* 
     if (bx > 16) bx = 16;
     hipLaunchKernelGGL(replay_gather_kernel, dim3(bx, count), dim3(256), 0, stream, ring, item4, index, out);
     SIMQ_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_states_to_bf16(const float* src, uint16_t* dst, int64_t n, hipStream_t stream) {
+    int blocks = (int)((n / 8 + 255) / 256);
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(states_to_bf16_kernel, dim3(blocks), dim3(256), 0, stream, src, dst, n);
+    SIMQ_CHECK_LAUNCH();
+    note_launch("states_to_bf16");
+    return 0;
+}
+
+int launch_states_to_f32(const uint16_t* src, float* dst, int64_t n, hipStream_t stream) {
+    int blocks = (int)((n / 8 + 255) / 256);
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(states_to_f32_kernel, dim3(blocks), dim3(256), 0, stream, src, dst, n);
+    SIMQ_CHECK_LAUNCH();
+    note_launch("states_to_f32");
     return 0;
 }
 

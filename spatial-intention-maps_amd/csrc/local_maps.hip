@@ -48,10 +48,12 @@ struct SlotDesc : Desc {                          // simq_local_state_images_slo
 
 // where problem p's [96][96][C] image begins: the dense batch, or the problem's pool slot (NULL: a slot outside the pool -- the host has
 // refused those, this guards a table changed behind its back)
-__device__ __forceinline__ float* image_of(const Desc& d, float* out, unsigned p) {
+template <typename OT>
+__device__ __forceinline__ OT* image_of(const Desc& d, OT* out, unsigned p) {
     return out + (int64_t)p * kPix * d.C;
 }
-__device__ __forceinline__ float* image_of(const SlotDesc& d, float* pool, unsigned p) {
+template <typename OT>
+__device__ __forceinline__ OT* image_of(const SlotDesc& d, OT* pool, unsigned p) {
     const int64_t slot = d.slots[p];
     return slot >= 0 && slot < d.pool_slots ? pool + slot * ((int64_t)kPix * d.C) : nullptr;
 }
@@ -86,9 +88,16 @@ __device__ __forceinline__ float robot_value(const Desc& d, const simq_local_pro
     return acc;
 }
 
-// D: Desc (out is the [n][96][96][C] batch) or SlotDesc (out is the pool); everything but the image's base is the same code
-template <typename D>
-__global__ void __launch_bounds__(kThreads) local_state_kernel(D d, float* __restrict__ out) {
+// what is stored for the fp32 value v of one state element: v itself, or -- a pool of bf16 states (simq_plan_options.bf16_states) --
+// v rounded ONCE with the conversion the first convolution applies to an fp32 state, so that the bits in the pool are the bits that
+// convolution would have made of the fp32 state
+__device__ __forceinline__ void store_state(float* o, float v) { *o = v; }
+__device__ __forceinline__ void store_state(uint16_t* o, float v) { *o = __builtin_bit_cast(uint16_t, (__bf16)v); }
+
+// D: Desc (out is the [n][96][96][C] batch) or SlotDesc (out is the pool); OT: float, or uint16_t for bf16 states; everything but the
+// image's base and the last store is the same code
+template <typename D, typename OT>
+__global__ void __launch_bounds__(kThreads) local_state_kernel(D d, OT* __restrict__ out) {
     __shared__ int gidx[kPix];                    // gi * cols + gj of the local pixel, -1 outside the crop
     __shared__ float wave_min[kWaves];
     __shared__ float chan_min[SIMQ_LOCAL_MAX_CHANNELS];
@@ -128,7 +137,7 @@ __global__ void __launch_bounds__(kThreads) local_state_kernel(D d, float* __res
         __syncthreads();
     }
 
-    float* o = image_of(d, out, blockIdx.x);
+    OT* o = image_of(d, out, blockIdx.x);
     if constexpr (std::is_same<D, SlotDesc>::value)
         if (o == nullptr) return;                                        // (uniform over the workgroup)
     const int items = kPix * C;
@@ -151,7 +160,7 @@ __global__ void __launch_bounds__(kThreads) local_state_kernel(D d, float* __res
                 if (kind == SIMQ_LOCAL_OVERHEAD && !(v > 0.f)) v = m[g];
             }
         }
-        o[it] = v;
+        store_state(o + it, v);
     }
 }
 
@@ -264,75 +273,85 @@ extern "C" int64_t simq_local_state_desc_bytes(int n_maps, int n_robots, int n, 
            (int64_t)sizeof(simq_local_problem) * n + (int64_t)sizeof(simq_local_channel) * n * n_channels;
 }
 
-extern "C" int simq_local_state_images(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
-                                       const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
-                                       const simq_local_channel* channels, int n_channels, void* d_desc, int64_t desc_bytes, float* d_out,
-                                       int64_t out_floats, void* stream) {
-    const char* who = "local_state_images";
-    SIMQ_REQUIRE(problems && channels && d_desc && d_out, "local_state_images: NULL pointer");
-    if (int rc = check_counts(who, maps, n_maps, d_masks, n_masks, robots, n_robots, n, n_channels)) return rc;
-    SIMQ_REQUIRE(((uintptr_t)d_desc & 7) == 0 && ((uintptr_t)d_out & 3) == 0, "local_state_images: d_desc must be 8-byte and d_out 4-byte aligned");
-    const int64_t need_desc = simq_local_state_desc_bytes(n_maps, n_robots, n, n_channels);
-    SIMQ_REQUIRE(desc_bytes >= need_desc, "local_state_images: d_desc holds %lld bytes, the descriptors take %lld", (long long)desc_bytes,
-                 (long long)need_desc);
-    const int64_t need_out = (int64_t)n * kPix * n_channels;
-    SIMQ_REQUIRE(out_floats >= need_out, "local_state_images: d_out holds %lld floats, %d x 96 x 96 x %d images take %lld",
-                 (long long)out_floats, n, n_channels, (long long)need_out);
-    const int64_t out_bytes = need_out * 4;
-    SIMQ_REQUIRE(!overlaps(d_out, out_bytes, d_desc, need_desc), "local_state_images: d_out overlaps d_desc");
-    for (int k = 0; k < n_maps; ++k) {
-        if (int rc = check_map(who, maps[k], k)) return rc;
-        SIMQ_REQUIRE(!overlaps(d_out, out_bytes, maps[k].d_data, (int64_t)maps[k].rows * maps[k].cols * 4), "local_state_images: d_out overlaps map %d", k);
-    }
-    if (n_masks > 0 && d_masks)
-        SIMQ_REQUIRE(!overlaps(d_out, out_bytes, d_masks, (int64_t)n_masks * kPix * 4), "local_state_images: d_out overlaps the mask bank");
-    if (int rc = check_tables(who, maps, n_maps, n_masks, robots, n_robots, problems, n, channels, n_channels)) return rc;
-
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Desc d;
-    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, nullptr, d_desc, nullptr, s)) return rc;
-    local_state_kernel<Desc><<<n, kThreads, 0, s>>>(d, d_out);
-    SIMQ_CHECK_LAUNCH();
-    note_launch("local_state");
-    return 0;
-}
-
 extern "C" int64_t simq_local_state_slots_desc_bytes(int n_maps, int n_robots, int n, int n_channels) {
     const int64_t tables = simq_local_state_desc_bytes(n_maps, n_robots, n, n_channels);
     return tables < 0 ? -1 : tables + (int64_t)sizeof(int64_t) * n;
 }
 
-extern "C" int simq_local_state_images_slots(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
-                                             const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
-                                             const simq_local_channel* channels, int n_channels, const int64_t* slots, void* d_desc,
-                                             int64_t desc_bytes, float* d_pool, int64_t pool_slots, void* stream) {
-    const char* who = "local_state_images_slots";
-    SIMQ_REQUIRE(problems && channels && slots && d_desc && d_pool, "local_state_images_slots: NULL pointer");
+namespace {
+
+// the element word of the refusals: the fp32 entries keep the texts they have always had
+template <typename OT> struct StateElem;
+template <> struct StateElem<float> { static const char* plural() { return "floats"; } };
+template <> struct StateElem<uint16_t> { static const char* plural() { return "bf16 elements"; } };
+
+// simq_local_state_images / simq_local_state_images_bf16: one body, OT the element type of d_out
+template <typename OT>
+int state_images(const char* who, const char* family, const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                 const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels,
+                 int n_channels, void* d_desc, int64_t desc_bytes, OT* d_out, int64_t out_elems, void* stream) {
+    constexpr int kElem = (int)sizeof(OT);
+    SIMQ_REQUIRE(problems && channels && d_desc && d_out, "%s: NULL pointer", who);
     if (int rc = check_counts(who, maps, n_maps, d_masks, n_masks, robots, n_robots, n, n_channels)) return rc;
-    SIMQ_REQUIRE(pool_slots >= 1 && pool_slots <= ((int64_t)1 << 40) / (kPix * 4), "local_state_images_slots: pool_slots = %lld (1 .. 2^40 bytes of pool)",
+    SIMQ_REQUIRE(((uintptr_t)d_desc & 7) == 0 && ((uintptr_t)d_out & (kElem - 1)) == 0, "%s: d_desc must be 8-byte and d_out %d-byte aligned", who, kElem);
+    const int64_t need_desc = simq_local_state_desc_bytes(n_maps, n_robots, n, n_channels);
+    SIMQ_REQUIRE(desc_bytes >= need_desc, "%s: d_desc holds %lld bytes, the descriptors take %lld", who, (long long)desc_bytes,
+                 (long long)need_desc);
+    const int64_t need_out = (int64_t)n * kPix * n_channels;
+    SIMQ_REQUIRE(out_elems >= need_out, "%s: d_out holds %lld %s, %d x 96 x 96 x %d images take %lld", who,
+                 (long long)out_elems, StateElem<OT>::plural(), n, n_channels, (long long)need_out);
+    const int64_t out_bytes = need_out * kElem;
+    SIMQ_REQUIRE(!overlaps(d_out, out_bytes, d_desc, need_desc), "%s: d_out overlaps d_desc", who);
+    for (int k = 0; k < n_maps; ++k) {
+        if (int rc = check_map(who, maps[k], k)) return rc;
+        SIMQ_REQUIRE(!overlaps(d_out, out_bytes, maps[k].d_data, (int64_t)maps[k].rows * maps[k].cols * 4), "%s: d_out overlaps map %d", who, k);
+    }
+    if (n_masks > 0 && d_masks)
+        SIMQ_REQUIRE(!overlaps(d_out, out_bytes, d_masks, (int64_t)n_masks * kPix * 4), "%s: d_out overlaps the mask bank", who);
+    if (int rc = check_tables(who, maps, n_maps, n_masks, robots, n_robots, problems, n, channels, n_channels)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Desc d;
+    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, nullptr, d_desc, nullptr, s)) return rc;
+    local_state_kernel<Desc, OT><<<n, kThreads, 0, s>>>(d, d_out);
+    SIMQ_CHECK_LAUNCH();
+    note_launch(family);
+    return 0;
+}
+
+// simq_local_state_images_slots / simq_local_state_images_slots_bf16: pool slots of 96 * 96 * C elements of OT
+template <typename OT>
+int state_images_slots(const char* who, const char* family, const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                       const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                       const simq_local_channel* channels, int n_channels, const int64_t* slots, void* d_desc, int64_t desc_bytes, OT* d_pool,
+                       int64_t pool_slots, void* stream) {
+    constexpr int kElem = (int)sizeof(OT);
+    SIMQ_REQUIRE(problems && channels && slots && d_desc && d_pool, "%s: NULL pointer", who);
+    if (int rc = check_counts(who, maps, n_maps, d_masks, n_masks, robots, n_robots, n, n_channels)) return rc;
+    SIMQ_REQUIRE(pool_slots >= 1 && pool_slots <= ((int64_t)1 << 40) / (kPix * 4), "%s: pool_slots = %lld (1 .. 2^40 bytes of pool)", who,
                  (long long)pool_slots);
-    SIMQ_REQUIRE(((uintptr_t)d_desc & 7) == 0 && ((uintptr_t)d_pool & 3) == 0,
-                 "local_state_images_slots: d_desc must be 8-byte and d_pool 4-byte aligned");
+    SIMQ_REQUIRE(((uintptr_t)d_desc & 7) == 0 && ((uintptr_t)d_pool & (kElem - 1)) == 0,
+                 "%s: d_desc must be 8-byte and d_pool %d-byte aligned", who, kElem);
     const int64_t need_desc = simq_local_state_slots_desc_bytes(n_maps, n_robots, n, n_channels);
-    SIMQ_REQUIRE(desc_bytes >= need_desc, "local_state_images_slots: d_desc holds %lld bytes, the descriptors and the slot table take %lld",
+    SIMQ_REQUIRE(desc_bytes >= need_desc, "%s: d_desc holds %lld bytes, the descriptors and the slot table take %lld", who,
                  (long long)desc_bytes, (long long)need_desc);
     std::vector<int64_t> sorted;
     int64_t which = 0;
     const int bad = check_slots(slots, n, pool_slots, sorted, &which);
-    SIMQ_REQUIRE(bad != 1, "local_state_images_slots: slot %lld outside the pool of %lld", (long long)which, (long long)pool_slots);
-    SIMQ_REQUIRE(bad != 2, "local_state_images_slots: slot %lld is named twice", (long long)which);
+    SIMQ_REQUIRE(bad != 1, "%s: slot %lld outside the pool of %lld", who, (long long)which, (long long)pool_slots);
+    SIMQ_REQUIRE(bad != 2, "%s: slot %lld is named twice", who, (long long)which);
     // the pool as a whole may hold what the launch reads (a map in another slot): only the slots written must be clear of it
-    const int64_t item_bytes = (int64_t)kPix * n_channels * 4;
+    const int64_t item_bytes = (int64_t)kPix * n_channels * kElem;
     int64_t hit = written_slot_in(sorted, d_pool, item_bytes, pool_slots, d_desc, need_desc);
-    SIMQ_REQUIRE(hit == -1, "local_state_images_slots: slot %lld overlaps d_desc", (long long)hit);
+    SIMQ_REQUIRE(hit == -1, "%s: slot %lld overlaps d_desc", who, (long long)hit);
     for (int k = 0; k < n_maps; ++k) {
         if (int rc = check_map(who, maps[k], k)) return rc;
         hit = written_slot_in(sorted, d_pool, item_bytes, pool_slots, maps[k].d_data, (int64_t)maps[k].rows * maps[k].cols * 4);
-        SIMQ_REQUIRE(hit == -1, "local_state_images_slots: slot %lld overlaps map %d", (long long)hit, k);
+        SIMQ_REQUIRE(hit == -1, "%s: slot %lld overlaps map %d", who, (long long)hit, k);
     }
     if (n_masks > 0 && d_masks) {
         hit = written_slot_in(sorted, d_pool, item_bytes, pool_slots, d_masks, (int64_t)n_masks * kPix * 4);
-        SIMQ_REQUIRE(hit == -1, "local_state_images_slots: slot %lld overlaps the mask bank", (long long)hit);
+        SIMQ_REQUIRE(hit == -1, "%s: slot %lld overlaps the mask bank", who, (long long)hit);
     }
     if (int rc = check_tables(who, maps, n_maps, n_masks, robots, n_robots, problems, n, channels, n_channels)) return rc;
 
@@ -342,8 +361,42 @@ extern "C" int simq_local_state_images_slots(const simq_local_map* maps, int n_m
     if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, slots, d_desc, &slots_at, s)) return rc;
     d.slots = reinterpret_cast<const int64_t*>(slots_at);
     d.pool_slots = pool_slots;
-    local_state_kernel<SlotDesc><<<n, kThreads, 0, s>>>(d, d_pool);
+    local_state_kernel<SlotDesc, OT><<<n, kThreads, 0, s>>>(d, d_pool);
     SIMQ_CHECK_LAUNCH();
-    note_launch("local_state_slots");
+    note_launch(family);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int simq_local_state_images(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                                       const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                                       const simq_local_channel* channels, int n_channels, void* d_desc, int64_t desc_bytes, float* d_out,
+                                       int64_t out_floats, void* stream) {
+    return state_images<float>("local_state_images", "local_state", maps, n_maps, d_masks, n_masks, robots, n_robots, problems, n, channels,
+                               n_channels, d_desc, desc_bytes, d_out, out_floats, stream);
+}
+
+extern "C" int simq_local_state_images_bf16(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                                            const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                                            const simq_local_channel* channels, int n_channels, void* d_desc, int64_t desc_bytes,
+                                            uint16_t* d_out, int64_t out_elems, void* stream) {
+    return state_images<uint16_t>("local_state_images_bf16", "local_state_bf16", maps, n_maps, d_masks, n_masks, robots, n_robots, problems, n,
+                                  channels, n_channels, d_desc, desc_bytes, d_out, out_elems, stream);
+}
+
+extern "C" int simq_local_state_images_slots(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                                             const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                                             const simq_local_channel* channels, int n_channels, const int64_t* slots, void* d_desc,
+                                             int64_t desc_bytes, float* d_pool, int64_t pool_slots, void* stream) {
+    return state_images_slots<float>("local_state_images_slots", "local_state_slots", maps, n_maps, d_masks, n_masks, robots, n_robots, problems,
+                                     n, channels, n_channels, slots, d_desc, desc_bytes, d_pool, pool_slots, stream);
+}
+
+extern "C" int simq_local_state_images_slots_bf16(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                                                  const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                                                  const simq_local_channel* channels, int n_channels, const int64_t* slots, void* d_desc,
+                                                  int64_t desc_bytes, uint16_t* d_pool, int64_t pool_slots, void* stream) {
+    return state_images_slots<uint16_t>("local_state_images_slots_bf16", "local_state_slots_bf16", maps, n_maps, d_masks, n_masks, robots,
+                                        n_robots, problems, n, channels, n_channels, slots, d_desc, desc_bytes, d_pool, pool_slots, stream);
 }

@@ -1,5 +1,6 @@
 // libsimq: the learner's small kernels and the convolution / BatchNorm / bilinear operators on their own, as C-ABI entry points
 // (the per-kernel parity tests and tools/ call these; the plan walks call the launchers directly).
+#include "batch_abi.h"
 #include "plan.h"
 
 using namespace simq;
@@ -210,6 +211,39 @@ int simq_conv2d_wgrad_stem_bf16(const float* d_x, const uint16_t* d_dy, float* d
     SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16: bad argument");
     SIMQ_REQUIRE(stem_conv_bf16_eligible(hin, win, cin, 64, 7, 2, 3), "conv2d_wgrad_stem_bf16: geometry not supported (7 * cin <= 63, win %% 32 == 0)");
     return launch_stem_wgrad_bf16(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
+}
+
+// ... the same two operators over bf16 states (d_x [batch][hin][win][cin] bf16, 2-byte aligned): what a bf16_states plan launches
+int simq_conv2d_fwd_stem_bf16_x16(const uint16_t* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
+                                  void* d_scratch, void* stream) {
+    SIMQ_REQUIRE(d_x && d_w && d_y && d_scratch && batch >= 1, "conv2d_fwd_stem_bf16_x16: bad argument");
+    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_fwd_stem_bf16_x16: d_x must be 2-byte aligned");
+    SIMQ_REQUIRE(stem_conv_bf16_eligible(hin, win, cin, 64, 7, 2, 3), "conv2d_fwd_stem_bf16_x16: geometry not supported (7 * cin <= 63, win %% 32 == 0)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RC(launch_stem_weight_prep(d_w, static_cast<uint16_t*>(d_scratch), cin, st));
+    return launch_stem_conv_bf16_x16(d_x, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
+}
+
+int simq_conv2d_wgrad_stem_bf16_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin, float* d_scratch,
+                                    void* stream) {
+    SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16_x16: bad argument");
+    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_wgrad_stem_bf16_x16: d_x must be 2-byte aligned");
+    SIMQ_REQUIRE(stem_conv_bf16_eligible(hin, win, cin, 64, 7, 2, 3), "conv2d_wgrad_stem_bf16_x16: geometry not supported (7 * cin <= 63, win %% 32 == 0)");
+    return launch_stem_wgrad_bf16_x16(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
+}
+
+int simq_states_to_bf16(const float* d_src, uint16_t* d_dst, int64_t n, void* stream) {
+    SIMQ_REQUIRE(d_src && d_dst && n >= 1, "states_to_bf16: NULL pointer or n < 1");
+    SIMQ_REQUIRE(((uintptr_t)d_src & 3) == 0 && ((uintptr_t)d_dst & 1) == 0, "states_to_bf16: d_src must be 4-byte and d_dst 2-byte aligned");
+    SIMQ_REQUIRE(!simq::overlaps(d_src, n * 4, d_dst, n * 2), "states_to_bf16: d_dst overlaps d_src");
+    return launch_states_to_bf16(d_src, d_dst, n, static_cast<hipStream_t>(stream));
+}
+
+int simq_states_to_f32(const uint16_t* d_src, float* d_dst, int64_t n, void* stream) {
+    SIMQ_REQUIRE(d_src && d_dst && n >= 1, "states_to_f32: NULL pointer or n < 1");
+    SIMQ_REQUIRE(((uintptr_t)d_src & 1) == 0 && ((uintptr_t)d_dst & 3) == 0, "states_to_f32: d_src must be 2-byte and d_dst 4-byte aligned");
+    SIMQ_REQUIRE(!simq::overlaps(d_src, n * 2, d_dst, n * 4), "states_to_f32: d_dst overlaps d_src");
+    return launch_states_to_f32(d_src, d_dst, n, static_cast<hipStream_t>(stream));
 }
 
 int simq_conv2d_fwd_winograd4(const float* d_x, const float* d_w, const float* d_bias, float* d_y, int batch, int hin, int win,

@@ -24,13 +24,39 @@ namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // a 16-byte load the compiler may not assume aligned
+typedef uint16_t ushortx8_a2 __attribute__((ext_vector_type(8), aligned(2))); // ... of 8 bf16: the window starts at (2 ox - 3) * C ELEMENTS, odd for odd C
+
+// The element type of x (simq_plan_options.bf16_states): float -- a lane's fragment is 8 floats (two 16-byte loads), masked as floats and
+// rounded to bf16 -- or uint16_t -- the states ARE bf16: the fragment is ONE 16-byte load that may only assume 2-byte alignment,
+// masked as 16-bit words (0 = +0.0) and handed to the matrix core as the bits lie in memory (no arithmetic touches them: NaN payloads
+// and denormals pass).  Every index below counts ELEMENTS of x, never bytes, so the masks are the same code for both.
+template <typename XE> struct Frag;
+template <> struct Frag<float> {
+    typedef float E;
+    static __device__ __forceinline__ void load8(const float* src, float* v) {
+        const floatx4_a4 lo = *reinterpret_cast<const floatx4_a4*>(src), hi = *reinterpret_cast<const floatx4_a4*>(src + 4);
+        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
+        v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
+    }
+    static __device__ __forceinline__ __bf16 cvt(float v) { return (__bf16)v; }
+};
+template <> struct Frag<uint16_t> {
+    typedef uint16_t E;
+    static __device__ __forceinline__ void load8(const uint16_t* src, uint16_t* v) {
+        const ushortx8_a2 w = *reinterpret_cast<const ushortx8_a2*>(src);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = w[q];
+    }
+    static __device__ __forceinline__ __bf16 cvt(uint16_t v) { return __builtin_bit_cast(__bf16, v); }
+};
 
 constexpr int COUT = 64, R = 7, KROW = 64;            // K per filter row (7 * Cin <= 63 real)
 constexpr int WROW = R * KROW + 8;                     // LDS row of one output channel: 456 bf16 = 228 dwords (36 mod 64: conflict-free)
 constexpr int SMEM_W = COUT * WROW * 2;                // 58 368 B
 
+template <typename XE>
 struct StemArgs {
-    const float* x; const uint16_t* w16; uint16_t* y; double* stats;
+    const XE* x; const uint16_t* w16; uint16_t* y; double* stats;
     int B, H, W, C, Ho, Wo;
     unsigned x_bytes;
 };
@@ -38,7 +64,9 @@ struct StemArgs {
 constexpr int NWAVE = 9;                               // waves per block (they share the LDS copy of the weights): 9 x 512 blocks = one
                                                        // 16-pixel tile per wave and trip, 4.5 waves per SIMD hide each other's load latency
 
-__global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const StemArgs p) {
+template <typename XE>
+__global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const StemArgs<XE> p) {
+    typedef typename Frag<XE>::E E;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint16_t* wl = reinterpret_cast<uint16_t*>(smem);
     double* red = reinterpret_cast<double*>(smem + SMEM_W);          // [NWAVE][64][2]
@@ -81,7 +109,7 @@ __global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const Ste
         // per lane: pointer to the first float of its k-group at filter row 0 (may lie outside the tensor: rows above / below the image
         // are skipped before it is used); per k-step whether some lane's 8-float fragment touches the left / right padding (ballot)
         const int e_lo = (2 * (ox0 + fi) - 3) * p.C + kg * 8;
-        const float* prow = p.x + ((long)(b * p.H + 2 * oy - 3) * rowf + e_lo);
+        const XE* prow = p.x + ((long)(b * p.H + 2 * oy - 3) * rowf + e_lo);
         bool side[2], real[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
@@ -95,23 +123,21 @@ __global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const Ste
             if ((unsigned)iy >= (unsigned)p.H) continue;                                      // wave-uniform: a padding row
             // the first row of the first image and the last row of the last: a fragment may reach outside the tensor
             const bool tensor_edge = (b == 0 && iy == 0) || (b == p.B - 1 && iy == p.H - 1);   // wave-uniform
-            float v[2][8];
+            E v[2][8];
             // fragments of both k-steps: 8 consecutive floats of x each, straight from global memory (dword-aligned 16-byte loads: the
             // window starts at (2 ox - 3) * C floats), all four loads issued before the first mask
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
 #pragma unroll
-                for (int q = 0; q < 8; ++q) v[s][q] = 0.f;
+                for (int q = 0; q < 8; ++q) v[s][q] = E(0);
                 if (real[s]) {
-                    const float* src = prow + (ky * rowf + s * 32);
+                    const XE* src = prow + (ky * rowf + s * 32);
                     if (!tensor_edge) {
-                        const floatx4_a4 lo = *reinterpret_cast<const floatx4_a4*>(src), hi = *reinterpret_cast<const floatx4_a4*>(src + 4);
-                        v[s][0] = lo[0]; v[s][1] = lo[1]; v[s][2] = lo[2]; v[s][3] = lo[3];
-                        v[s][4] = hi[0]; v[s][5] = hi[1]; v[s][6] = hi[2]; v[s][7] = hi[3];
+                        Frag<XE>::load8(src, v[s]);
                     } else {
                         const long g0 = src - p.x;
 #pragma unroll
-                        for (int q = 0; q < 8; ++q) v[s][q] = (g0 + q >= 0 && g0 + q < total) ? src[q] : 0.f;
+                        for (int q = 0; q < 8; ++q) v[s][q] = (g0 + q >= 0 && g0 + q < total) ? src[q] : E(0);
                     }
                 }
             }
@@ -120,11 +146,11 @@ __global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const Ste
                 if (side[s]) {                                         // wave-uniform: some lane touches the left / right padding
                     const int e = e_lo + s * 32;
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) v[s][q] = ((unsigned)(e + q) < (unsigned)rowf) ? v[s][q] : 0.f;
+                    for (int q = 0; q < 8; ++q) v[s][q] = ((unsigned)(e + q) < (unsigned)rowf) ? v[s][q] : E(0);
                 }
                 bf16x8 af;
 #pragma unroll
-                for (int q = 0; q < 8; ++q) af[q] = (__bf16)v[s][q];
+                for (int q = 0; q < 8; ++q) af[q] = Frag<XE>::cvt(v[s][q]);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const bf16x8 bf = *reinterpret_cast<const bf16x8*>(wfrag + j * 16 * WROW + ky * KROW + s * 32);
@@ -186,12 +212,15 @@ constexpr int TROW = 40;                               // LDS row: 32 pixels + 8
 constexpr int WG_SMEM = (COUT + R * KROW) * TROW * 2;  // dyT + 7 x XT = 40 960 B
 constexpr int WG_WAVES = 8;
 
+template <typename XE>
 struct StemWgradArgs {
-    const float* x; const uint16_t* dy; float* partial;
+    const XE* x; const uint16_t* dy; float* partial;
     int B, H, W, C, Ho, Wo;
 };
 
-__global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const StemWgradArgs p) {
+template <typename XE>
+__global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const StemWgradArgs<XE> p) {
+    typedef typename Frag<XE>::E E;
     __shared__ __attribute__((aligned(16))) uint16_t lds[WG_SMEM / 2];
     uint16_t* dyT = lds;                                // [64][TROW]
     uint16_t* XT = lds + COUT * TROW;                   // [7][64][TROW]
@@ -226,7 +255,7 @@ __global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const
             const int grp = f & 7, i = (f >> 3) & 15, t = (f >> 7) & 1, ky = f >> 8;
             if (grp >= ngrp) continue;
             const int tile = chunk * 2 + t;
-            float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            E v[8] = {E(0), E(0), E(0), E(0), E(0), E(0), E(0), E(0)};
             if (tile < ntiles) {
                 const int ox0 = (tile % tiles_per_row) * 16;
                 const int r = tile / tiles_per_row;
@@ -236,21 +265,20 @@ __global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const
                     const int e = (2 * (ox0 + i) - 3) * p.C + grp * 8;                 // first float of the fragment inside the image row
                     const long g0 = (long)(b * p.H + iy) * rowf + e;
                     if (g0 >= 0 && g0 + 8 <= total) {
-                        const floatx4_a4 lo = *reinterpret_cast<const floatx4_a4*>(p.x + g0), hi = *reinterpret_cast<const floatx4_a4*>(p.x + g0 + 4);
-                        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
+                        Frag<XE>::load8(p.x + g0, v);
                     } else {
 #pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = (g0 + q >= 0 && g0 + q < total) ? p.x[g0 + q] : 0.f;
+                        for (int q = 0; q < 8; ++q) v[q] = (g0 + q >= 0 && g0 + q < total) ? p.x[g0 + q] : E(0);
                     }
                     if (e < 0 || e + 8 > rowf) {
 #pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = ((unsigned)(e + q) < (unsigned)rowf) ? v[q] : 0.f;   // left / right padding
+                        for (int q = 0; q < 8; ++q) v[q] = ((unsigned)(e + q) < (unsigned)rowf) ? v[q] : E(0);   // left / right padding
                     }
                 }
             }
             uint16_t* dst = XT + (ky * KROW + grp * 8) * TROW + t * 16 + i;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) dst[q * TROW] = __builtin_bit_cast(uint16_t, (__bf16)v[q]);
+            for (int q = 0; q < 8; ++q) dst[q * TROW] = __builtin_bit_cast(uint16_t, Frag<XE>::cvt(v[q]));
         }
         __syncthreads();
         // ---- wave ky: out[o][n] += sum over the 32 pixels of dyT[o][pix] * XT_ky[n][pix]
@@ -313,21 +341,34 @@ int stem_wgrad_bf16_slabs(int B, int H, int W) {
     return blocks;
 }
 
-// dy: bf16 [B][H/2][W/2][64];  dw: [64][7][7][C] fp32 (overwritten);  partial: stem_wgrad_bf16_slabs() * 64 * 49 * C floats
-int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream) {
+namespace {
+
+template <typename XE>
+int stem_wgrad_bf16_impl(const char* family, const XE* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream) {
     SIMQ_REQUIRE(stem_conv_bf16_eligible(H, W, C, COUT, R, 2, 3), "stem_wgrad_bf16: shape %dx%dx%d not covered", H, W, C);
-    SIMQ_REQUIRE(4.0 * B * H * W * C < 4294967000.0, "stem_wgrad_bf16: input too large");
-    StemWgradArgs p;
+    SIMQ_REQUIRE(4.0 * B * H * W * C < 4294967000.0, "stem_wgrad_bf16: input too large");     // (elements: the kernels index them with 31 bits to spare)
+    StemWgradArgs<XE> p;
     p.x = x; p.dy = dy; p.partial = partial;
     p.B = B; p.H = H; p.W = W; p.C = C; p.Ho = H / 2; p.Wo = W / 2;
     const int slabs = stem_wgrad_bf16_slabs(B, H, W);
-    note_launch("stem_wgrad_bf16");
-    hipLaunchKernelGGL(stem_wgrad_bf16_kernel, dim3(slabs), dim3(WG_WAVES * 64), 0, stream, p);
+    note_launch(family);
+    hipLaunchKernelGGL(stem_wgrad_bf16_kernel<XE>, dim3(slabs), dim3(WG_WAVES * 64), 0, stream, p);
     SIMQ_CHECK_LAUNCH();
     const int n = COUT * R * R * C;
     hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, partial, dw, n, slabs);
     SIMQ_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+// dy: bf16 [B][H/2][W/2][64];  dw: [64][7][7][C] fp32 (overwritten);  partial: stem_wgrad_bf16_slabs() * 64 * 49 * C floats
+int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream) {
+    return stem_wgrad_bf16_impl<float>("stem_wgrad_bf16", x, dy, dw, partial, B, H, W, C, stream);
+}
+// ... over bf16 states: x is [B][H][W][C] bf16
+int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream) {
+    return stem_wgrad_bf16_impl<uint16_t>("stem_wgrad_bf16_x16", x, dy, dw, partial, B, H, W, C, stream);
 }
 
 int stem_conv_bf16_wbytes() { return COUT * WROW * 2; }
@@ -342,28 +383,41 @@ int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, hipStream_t st
     return 0;
 }
 
-// y: bf16 [B][H/2][W/2][64];  stats: NULL or [2 * 64] doubles (accumulated into)
-int launch_stem_conv_bf16(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
+namespace {
+
+template <typename XE>
+int stem_conv_bf16_impl(const char* family, const XE* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
     SIMQ_REQUIRE(stem_conv_bf16_eligible(H, W, C, COUT, R, 2, 3), "stem_conv_bf16: shape %dx%dx%d not covered", H, W, C);
     const double xb = 4.0 * B * H * W * C;
     SIMQ_REQUIRE(xb < 4294967000.0, "stem_conv_bf16: input exceeds the 4 GiB buffer-addressing limit");
-    StemArgs p;
+    StemArgs<XE> p;
     p.x = x; p.w16 = w16; p.y = y; p.stats = stats;
     p.B = B; p.H = H; p.W = W; p.C = C; p.Ho = H / 2; p.Wo = W / 2;
-    p.x_bytes = (unsigned)xb;
+    p.x_bytes = (unsigned)(xb / 4.0 * sizeof(XE));
     const int ntiles = B * p.Ho * (p.Wo / 16);
     int blocks = (ntiles + NWAVE - 1) / NWAVE;
     if (blocks > 512) blocks = 512;                                   // two persistent blocks per CU
-    static bool attr_set = false;
+    static bool attr_set = false;                                     // (one per instantiation)
     const int smem = SMEM_W + NWAVE * COUT * 2 * (int)sizeof(double);
     if (!attr_set) {
-        SIMQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_conv_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        SIMQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_conv_bf16_kernel<XE>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_set = true;
     }
-    note_launch("stem_conv_bf16");
-    hipLaunchKernelGGL(stem_conv_bf16_kernel, dim3(blocks), dim3(NWAVE * 64), smem, stream, p);
+    note_launch(family);
+    hipLaunchKernelGGL(stem_conv_bf16_kernel<XE>, dim3(blocks), dim3(NWAVE * 64), smem, stream, p);
     SIMQ_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+// y: bf16 [B][H/2][W/2][64];  stats: NULL or [2 * 64] doubles (accumulated into)
+int launch_stem_conv_bf16(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
+    return stem_conv_bf16_impl<float>("stem_conv_bf16", x, w16, y, stats, B, H, W, C, stream);
+}
+// ... over bf16 states: x is [B][H][W][C] bf16
+int launch_stem_conv_bf16_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
+    return stem_conv_bf16_impl<uint16_t>("stem_conv_bf16_x16", x, w16, y, stats, B, H, W, C, stream);
 }
 
 }  // namespace simq

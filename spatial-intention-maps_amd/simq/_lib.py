@@ -48,7 +48,14 @@ class PlanOptions(ctypes.Structure):
         'struct_bytes', 'winograd', 'winograd_min_cc', 'winograd_f4_forward', 'winograd_f4_min_tiles', 'winograd_f4_grad',
         'winograd_f4_fwd_grad_min_cc', 'winograd_wgrad', 'winograd_wgrad_f4', 'stem_bf16', 'bf16_act_grads', 'keep_fp32_activations', 'fold_eval_bn_bf16',
         'fuse_bn_backward_sums', 'fuse_stem_backward_sums', 'fuse_bn1_apply', 'deterministic', 'bn1_mask_from_preact',
-        'wgrad_ksplit', 'fwd_overlap', 'wgrad_overlap', 'plane_xcd', 'wgrad_xcd_group', 'tail_split', 'early_target_after_block', 'gemm_split')]
+        'wgrad_ksplit', 'fwd_overlap', 'wgrad_overlap', 'plane_xcd', 'wgrad_xcd_group', 'tail_split', 'early_target_after_block', 'gemm_split',
+        'bf16_states')]
+
+
+# Fields of simq_plan_options that say what a plan's entry points READ rather than how the plan computes: accepted by Plan(options=...) like
+# every other field and reported as attributes of the Plan (Plan.bf16_states); Plan.options stays the table of forms, fusions and schedules
+# of the arithmetic.
+INPUT_FORMAT_OPTIONS = ('bf16_states',)
 
 
 class LaunchOpts(ctypes.Structure):
@@ -153,6 +160,10 @@ _SIGS = {
     'simq_conv2d_fwd_stem_f32': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     'simq_conv2d_fwd_stem_bf16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
     'simq_conv2d_wgrad_stem_bf16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    'simq_conv2d_fwd_stem_bf16_x16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    'simq_conv2d_wgrad_stem_bf16_x16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    'simq_states_to_bf16': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    'simq_states_to_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'simq_forward_sync': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'simq_backward_sync': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p]),
@@ -194,6 +205,10 @@ _SIGS = {
     'simq_local_state_slots_desc_bytes': (c_int64, [c_int, c_int, c_int, c_int]),
     'simq_local_state_images_slots': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                               c_int64, c_void_p, c_int64, c_void_p]),
+    'simq_local_state_images_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                             c_void_p, c_int64, c_void_p]),
+    'simq_local_state_images_slots_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                   c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_intention_desc_bytes': (c_int64, [c_int, c_int]),
     'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
@@ -326,7 +341,8 @@ class Plan:
         self.handle = h
         got = PlanOptions()
         check(_c.simq_plan_get_options(h, ctypes.byref(got)), 'simq_plan_get_options')
-        self.options = {n: getattr(got, n) for n, _ in PlanOptions._fields_[1:]}
+        self.options = {n: getattr(got, n) for n, _ in PlanOptions._fields_[1:] if n not in INPUT_FORMAT_OPTIONS}
+        self.bf16_states = int(got.bf16_states)      # 1: every entry point of this plan that takes states reads them as bf16 (include/simq.h)
         self.param_count = _c.simq_param_count(h)
         self.bnbuf_count = _c.simq_bnbuf_count(h)
         self.tensors = []     # (name, offset, shape(list), kind)

@@ -96,7 +96,7 @@ def to_host_ring(buf):
             return None
         key = (obs.store.data_ptr(), int(obs))
         if key not in cache:
-            cache[key] = obs.store[int(obs)].cpu().numpy()
+            cache[key] = _learner._host_f32(obs.store[int(obs)])      # (a bf16 ring: the exact widening -- the file holds float32 arrays)
         return cache[key]
 
     for rec in buf.buffer:
@@ -104,9 +104,10 @@ def to_host_ring(buf):
     return host
 
 
-def to_device_ring(host, num_input_channels=None, device=None, aliased=True, pool_slots=None):
+def to_device_ring(host, num_input_channels=None, device=None, aliased=True, pool_slots=None, dtype='fp32'):
     """Host ReplayBuffer (ours or one unpickled from a reference checkpoint) -> device ring with the same
-    capacity / position / record order, hence the same `random.sample` picks."""
+    capacity / position / record order, hence the same `random.sample` picks.  dtype='bf16': a ring of bf16 states -- the float32
+    arrays are rounded to nearest even on the way in, so a bf16 ring that was saved (exact widening) comes back bit-identical."""
     if isinstance(host, _learner.DeviceReplayBuffer):
         return host
     if num_input_channels is None:
@@ -117,9 +118,9 @@ def to_device_ring(host, num_input_channels=None, device=None, aliased=True, poo
         if pool_slots is None:
             distinct = {id(o) for r in host.buffer for o in (r.state, r.next_state) if o is not None}
             pool_slots = max(host.capacity + max(256, host.capacity // 4), len(distinct) + 256)
-        dev = _learner.AliasedDeviceReplayBuffer(host.capacity, num_input_channels, device=device, pool_slots=pool_slots)
+        dev = _learner.AliasedDeviceReplayBuffer(host.capacity, num_input_channels, device=device, pool_slots=pool_slots, dtype=dtype)
     else:
-        dev = _learner.DeviceReplayBuffer(host.capacity, num_input_channels, device=device)
+        dev = _learner.DeviceReplayBuffer(host.capacity, num_input_channels, device=device, dtype=dtype)
     n = len(host.buffer)
     full = n == host.capacity
     order = list(range(host.position, n)) + list(range(host.position)) if full else list(range(n))
@@ -183,9 +184,9 @@ def load_checkpoint(path, map_location=None):
     return torch.load(str(path), map_location=map_location, pickle_module=_PickleModule, weights_only=False)
 
 
-def resume(checkpoint, optimizers, num_input_channels=None, device=None, optimizers_intention=None, aliased=True):
+def resume(checkpoint, optimizers, num_input_channels=None, device=None, optimizers_intention=None, aliased=True, dtype='fp32'):
     """train.py:200-208 on the device path: restores the optimizers in place and returns
-    (start_timestep, episode, replay_buffers) with the rings uploaded into HBM."""
+    (start_timestep, episode, replay_buffers) with the rings uploaded into HBM (dtype: as to_device_ring's)."""
     if isinstance(checkpoint, (str, os.PathLike)):
         checkpoint = load_checkpoint(checkpoint)
     if len(checkpoint['optimizers']) != len(optimizers):
@@ -196,5 +197,5 @@ def resume(checkpoint, optimizers, num_input_channels=None, device=None, optimiz
     if optimizers_intention is not None:
         for opt, sd in zip(optimizers_intention, checkpoint['optimizers_intention']):
             opt.load_state_dict(sd)
-    rings = [to_device_ring(b, num_input_channels, device=device, aliased=aliased) for b in checkpoint['replay_buffers']]
+    rings = [to_device_ring(b, num_input_channels, device=device, aliased=aliased, dtype=dtype) for b in checkpoint['replay_buffers']]
     return checkpoint['timestep'], checkpoint['episode'], rings

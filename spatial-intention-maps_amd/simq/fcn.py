@@ -64,10 +64,41 @@ def is_handle(s):
     return getattr(s, 'pool', None) is not None and hasattr(s, 'slot')
 
 
-def states_batch(states, device):
+def to_bf16(x):
+    """A contiguous float32 device tensor as bfloat16, rounded to nearest even by simq_states_to_bf16 on the current stream (one launch,
+    no host rounding): the conversion the first convolution of a plain-bf16 plan applies to an fp32 state."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        raise SimqError('to_bf16 takes a contiguous float32 device tensor')
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    if x.numel():
+        lib.call('simq_states_to_bf16', ptr(x), ptr(out), x.numel(), stream_ptr(x.device))
+    return out
+
+
+def to_f32(x):
+    """A contiguous bfloat16 device tensor as float32: the exact widening (simq_states_to_f32, one launch on the current stream)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()):
+        raise SimqError('to_f32 takes a contiguous bfloat16 device tensor')
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.numel():
+        lib.call('simq_states_to_f32', ptr(x), ptr(out), x.numel(), stream_ptr(x.device))
+    return out
+
+
+def states_as(x, dtype):
+    """A device tensor of states in the element type `dtype` (torch.float32 / torch.bfloat16): itself, rounded, or widened."""
+    if x.dtype == dtype:
+        return x
+    return to_bf16(x.contiguous()) if dtype == torch.bfloat16 else to_f32(x.contiguous())
+
+
+def states_batch(states, device, dtype=None):
     """A list of HWC states -- ndarrays [96,96,C], device tensors [1,96,96,C], handles of AliasedDeviceReplayBuffer.reserve / adopt --
-    as one contiguous float32 [n,96,96,C] device tensor, every state at its position.  The handles of a pool are read with one
-    simq_replay_gather, behind the writes of their slots; ndarrays are uploaded as they always were."""
+    as one contiguous [n,96,96,C] device tensor, every state at its position.  The handles of a pool are read with one
+    simq_replay_gather, behind the writes of their slots; ndarrays are uploaded as they always were.
+    dtype: the element type the caller's net takes (FCN.state_dtype).  None: float32, unless every state is a handle of one pool --
+    then that pool's type, as gathered.  Pieces of another type are rounded (simq_states_to_bf16) or widened (simq_states_to_f32) on
+    the device."""
     rows, by_pool = {}, {}
     for k, s in enumerate(states):
         if is_handle(s):
@@ -75,10 +106,12 @@ def states_batch(states, device):
     for ks in by_pool.values():
         got = states[ks[0]].pool.gather_handles([states[k] for k in ks])
         if len(ks) == len(states):
-            return got
+            return got if dtype is None else states_as(got, dtype)
         rows.update({k: got[r:r + 1] for r, k in enumerate(ks)})
-    return torch.cat([rows[k] if k in rows else s if torch.is_tensor(s) else
-                      torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(device) for k, s in enumerate(states)]).contiguous()
+    want = torch.float32 if dtype is None else dtype
+    return torch.cat([states_as(rows[k] if k in rows else s if torch.is_tensor(s) else
+                                torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(device), want)
+                      for k, s in enumerate(states)]).contiguous()
 
 class FCN(torch.nn.Module):
     def __init__(self, num_input_channels=3, num_output_channels=1, device=None, dataparallel_keys=True, precision='fp32', options=None):
@@ -283,10 +316,27 @@ class FCN(torch.nn.Module):
             self._weights_event = torch.cuda.Event()
             self._weights_event.record(torch.cuda.current_stream(self.device_))
 
+    @property
+    def state_dtype(self):
+        """The element type this net's plan reads its states in: torch.bfloat16 with options={'bf16_states': 1}, else torch.float32."""
+        return torch.bfloat16 if self.plan.bf16_states else torch.float32
+
+    def as_states(self, x, what='simq.FCN'):
+        """x in this net's state type.  A bf16_states net takes bf16 tensors as they are and rounds fp32 tensors with one
+        simq_states_to_bf16 launch; a net without the option refuses bf16 tensors: whether to widen them is the caller's decision."""
+        if x.dtype == self.state_dtype:
+            return x
+        if x.dtype == torch.float32:
+            return to_bf16(x)
+        if x.dtype == torch.bfloat16:
+            raise SimqError("%s: bf16 states need a plan created with the option bf16_states (FCN(precision='bf16', options={'bf16_states': 1})); "
+                            "this net's plan reads fp32 states -- handing it x.float() is the caller's decision" % what)
+        raise SimqError('%s: states must be float32 or bfloat16, got %s' % (what, x.dtype))
+
     def _forward_raw(self, x_nhwc, mode, sync=None):
-        """x_nhwc [B,96,96,Cin] fp32 contiguous on device -> q [B,Cout,96,96].  sync: a simq.dist.SyncBN (global-minibatch
-        BatchNorm statistics in the train modes)."""
-        if x_nhwc.dtype != torch.float32 or not x_nhwc.is_contiguous() or x_nhwc.device != self.flat_params.device:
+        """x_nhwc [B,96,96,Cin] contiguous on device, fp32 or (bf16_states plans: taken as is) bf16 -> q [B,Cout,96,96].  sync: a
+        simq.dist.SyncBN (global-minibatch BatchNorm statistics in the train modes)."""
+        if x_nhwc.dtype not in (torch.float32, torch.bfloat16) or not x_nhwc.is_contiguous() or x_nhwc.device != self.flat_params.device:
             raise SimqError('simq.FCN: input must be a contiguous fp32 tensor on %s' % self.device_)
         B = x_nhwc.shape[0]
         if tuple(x_nhwc.shape[1:]) != (W, W, self.num_input_channels):
@@ -294,6 +344,7 @@ class FCN(torch.nn.Module):
                             % (W, W, self.num_input_channels, tuple(x_nhwc.shape)))
         if B < 1:
             raise SimqError('simq.FCN: empty batch')
+        x_nhwc = self.as_states(x_nhwc)
         self._order_behind_last_step()
         if mode == MODE_TRAIN:
             self._train_generation += 1
@@ -459,12 +510,11 @@ class FCN(torch.nn.Module):
             a, q = self.infer_argmax(states[0], need_q)
             return [a], [q]
         if any(is_handle(s) for s in states):
-            x = states_batch(states, self.device_)
+            x = states_batch(states, self.device_, self.state_dtype)
         elif all(not torch.is_tensor(s) for s in states):
             x = torch.from_numpy(np.stack([np.ascontiguousarray(s, dtype=np.float32) for s in states])).to(self.device_)
         else:
-            x = torch.cat([s if torch.is_tensor(s) else torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(self.device_)
-                           for s in states]).contiguous()
+            x = states_batch(states, self.device_, self.state_dtype)
         q = self.forward_nhwc(x)
         n = q[0].numel()
         idx = torch.empty(len(states), dtype=torch.int64, device=self.device_)
@@ -483,7 +533,7 @@ class FCN(torch.nn.Module):
         if self.training:
             raise SimqError('infer_argmax: the net must be in eval mode (policies.py:56)')
         # a device tensor [1,96,96,C] is taken as is (DQNIntentionPolicy hands over state + predicted map in HBM)
-        x = state_hwc if torch.is_tensor(state_hwc) else states_batch([state_hwc], self.device_) if is_handle(state_hwc) else \
+        x = state_hwc if torch.is_tensor(state_hwc) else states_batch([state_hwc], self.device_, self.state_dtype) if is_handle(state_hwc) else \
             torch.from_numpy(np.ascontiguousarray(state_hwc, dtype=np.float32)).unsqueeze(0).to(self.device_)
         q = self.forward_nhwc(x)
         a = self.argmax(q[0])

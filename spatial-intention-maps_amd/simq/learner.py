@@ -59,8 +59,10 @@ class ReplayBuffer:
 class DeviceBatch:
     """A sampled minibatch already resident in HBM (what DeviceReplayBuffer.sample returns).
 
-    state [B,96,96,C] f32 NHWC, action [B] i64, reward [B] f32 (device);
+    state [B,96,96,C] NHWC, action [B] i64, reward [B] f32 (device);
     next_state [N',96,96,C] (non-final only), nonfinal_pos [N'] i32 device, non_final_mask host bool list.
+    state / next_state are float32, or bfloat16 when the ring they were gathered from holds bf16 states (dtype='bf16'): a net
+    created with options={'bf16_states': 1} steps on those as they are, any other net refuses them (train_step).
     """
     __slots__ = ('state', 'action', 'reward', 'next_state', 'nonfinal_pos', 'non_final_mask', 'ready_event')
 
@@ -186,6 +188,23 @@ def _upload_packed(device, arrays, slots=4, upload_stream=True):
     return tuple(devbuf[o:o + a.nbytes].view(kinds[a.dtype]) for a, o in zip(arrays, offs))
 
 
+STATE_DTYPES = {'fp32': torch.float32, 'bf16': torch.bfloat16}
+
+
+def _state_dtype(dtype):
+    """dtype= of the device rings: 'fp32' (the reference's float32 states) or 'bf16' (states stored, gathered and convolved as
+    bf16 by nets created with options={'bf16_states': 1})."""
+    if not isinstance(dtype, str) or dtype not in STATE_DTYPES:
+        raise ValueError("dtype must be 'fp32' or 'bf16', got %r" % (dtype,))
+    return STATE_DTYPES[dtype]
+
+
+def _host_f32(row):
+    """A ring row as the float32 ndarray the reference keeps: a copy of an fp32 row, the exact widening of a bf16 row."""
+    row = row.cpu()
+    return (row.float() if row.dtype == torch.bfloat16 else row).numpy()
+
+
 class _DeviceObs:
     """One observation resident in an HBM ring slot, standing where the reference keeps the ndarray itself
     (`random.choice(replay_buffers[i].buffer).state`, train.py:294): converts to the [96,96,C] float32 array on demand
@@ -207,7 +226,7 @@ class _DeviceObs:
     def __array__(self, dtype=None, copy=None):
         if self.store.is_cuda:
             sync_uploads(self.store.device)    # (ring slots are written on the upload stream: _PinnedStaging.upload)
-        a = self.store[self.slot].cpu().numpy()
+        a = _host_f32(self.store[self.slot])
         return a if dtype is None else a.astype(dtype, copy=False)
 
     def __getitem__(self, key):
@@ -217,7 +236,8 @@ class _DeviceObs:
         return self.__array__()
 
     def device_row(self):
-        """The [96,96,C] row of the ring itself, for a reader on the current stream (simq.state_output_visualizations)."""
+        """The [96,96,C] row of the ring itself (bfloat16 in a ring of bf16 states), for a reader on the current stream
+        (simq.state_output_visualizations)."""
         if self.store.is_cuda:
             sync_uploads(self.store.device)
         return self.store[self.slot]
@@ -247,7 +267,7 @@ class _PoolObs(_DeviceObs):
         if not self.alive:
             raise SimqError('%r was discarded: its slot may hold another observation by now' % (self,))
         self.pool.sync_ring()                      # (the slot was written on whichever stream ran the mapper / the scatter)
-        a = self.store[self.slot].cpu().numpy()
+        a = _host_f32(self.store[self.slot])
         return a if dtype is None else a.astype(dtype, copy=False)
 
     def device_row(self):
@@ -289,19 +309,31 @@ class _PinnedStaging:
     uploaded with asynchronous H2D copies, so `push` returns as soon as the ndarray is staged and the environment can keep stepping
     while the copy (and the learner's kernels) run.  A slot is reused only after the copy that last read it has finished."""
 
-    def __init__(self, item_shape, device, slots=32, on_upload_stream=True):
+    def __init__(self, item_shape, device, slots=32, on_upload_stream=True, dtype=torch.float32):
         self.device = device
         self.on_upload_stream = bool(on_upload_stream)
         self.enabled = device.type == 'cuda' and torch.cuda.is_available()
         self.slots = slots
         self.pos = 0
+        self.dtype = dtype
         if self.enabled:
             self.buf = torch.empty((slots,) + tuple(item_shape), dtype=torch.float32).pin_memory()
             self.events = [None] * slots
+            # a ring of bf16 states: the observation travels as fp32 into device scratch slot i and is rounded from there into its ring
+            # slot on the same stream (simq_states_to_bf16: no host rounding); the slot's event stands behind the conversion
+            self.scratch = torch.empty((slots,) + tuple(item_shape), dtype=torch.float32, device=device) if dtype != torch.float32 else None
+
+    def _land(self, i, dst):
+        """pinned slot i -> ring row dst on the current stream."""
+        if self.scratch is None:
+            dst.copy_(self.buf[i], non_blocking=True)
+        else:
+            self.scratch[i].copy_(self.buf[i], non_blocking=True)
+            lib.call('simq_states_to_bf16', ptr(self.scratch[i]), ptr(dst), dst.numel(), stream_ptr(self.device))
 
     def upload(self, arr, dst):
         if not self.enabled:
-            dst.copy_(torch.as_tensor(arr))
+            dst.copy_(torch.as_tensor(arr))                    # (no device: torch's own round-to-nearest-even for a bf16 ring)
             return
         i = self.pos
         self.pos = (i + 1) % self.slots
@@ -314,12 +346,12 @@ class _PinnedStaging:
         up = _upload_stream(self.device) if self.on_upload_stream else None
         if up is not None:
             with torch.cuda.stream(up):
-                dst.copy_(self.buf[i], non_blocking=True)
+                self._land(i, dst)
                 ev = torch.cuda.Event()
                 ev.record(up)
             self.last_event = None
         else:
-            dst.copy_(self.buf[i], non_blocking=True)
+            self._land(i, dst)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
             self.last_event = ev                               # (a gather on another stream orders itself behind the ring's last write)
@@ -335,17 +367,25 @@ class DeviceReplayBuffer:
     `random.sample(self.buffer, B)` makes under the same seed (golden: tests/golden/sampler.npz).
     """
 
-    def __init__(self, capacity, num_input_channels, device=None, upload_stream=True):
+    def __init__(self, capacity, num_input_channels, device=None, upload_stream=True, dtype='fp32'):
+        """dtype: 'fp32', or 'bf16' -- the rings hold bfloat16 states (half the HBM, half the gathers' bytes): pushed ndarrays and fp32
+        tensors are rounded to nearest even on the device into their slot, gather / sample return bfloat16 tensors for a net created
+        with options={'bf16_states': 1}, and np.asarray(record.state) stays a float32 array (the exact widening)."""
+        self.dtype = _state_dtype(dtype)
         self.capacity = int(capacity)
         self.C = int(num_input_channels)
         self.device = torch.device('cuda' if device is None else device)
-        self.item = W * W * self.C
-        self.states = torch.empty((self.capacity, W, W, self.C), dtype=torch.float32, device=self.device)
-        self.next_states = torch.empty((self.capacity, W, W, self.C), dtype=torch.float32, device=self.device)
+        self._set_item()
+        self.states = torch.empty((self.capacity, W, W, self.C), dtype=self.dtype, device=self.device)
+        self.next_states = torch.empty((self.capacity, W, W, self.C), dtype=self.dtype, device=self.device)
         self._set_upload_mode(upload_stream)
-        self._staging = _PinnedStaging((W, W, self.C), self.device, on_upload_stream=self.ring_on_upload_stream)
+        self._staging = _PinnedStaging((W, W, self.C), self.device, on_upload_stream=self.ring_on_upload_stream, dtype=self.dtype)
         self.buffer = []
         self.position = 0
+
+    def _set_item(self):
+        # `item_floats` of simq_replay_gather / simq_replay_scatter, which move bits: 4-byte words per state (96 * 96 * C is even)
+        self.item = W * W * self.C if self.dtype == torch.float32 else W * W * self.C // 2
 
     def _set_upload_mode(self, upload_stream):
         """upload_stream: True (default) -- pushes, the per-batch index upload and the gathers all run on the device's upload stream, beside
@@ -425,10 +465,17 @@ class DeviceReplayBuffer:
         if not torch.is_tensor(obs) or not obs.is_cuda:
             return None
         row = obs[0] if obs.dim() == 4 and obs.shape[0] == 1 else obs
-        if row.dtype != torch.float32 or tuple(row.shape) != (W, W, self.C) or not row.is_contiguous() or row.device != self.states.device:
+        if row.dtype not in (torch.float32, self.dtype) or tuple(row.shape) != (W, W, self.C) or not row.is_contiguous() or row.device != self.states.device:
             raise SimqError('push: a device state must be a contiguous float32 [%d,%d,%d] (or [1,%d,%d,%d]) tensor on %s, got %s %s on %s'
                             % (W, W, self.C, W, W, self.C, self.states.device, obs.dtype, tuple(obs.shape), obs.device))
         return row
+
+    def _copy_row(self, obs, dst):
+        """Device row -> ring row on the current stream: a copy, or (an fp32 state into a ring of bf16 states) the rounding."""
+        if obs.dtype == dst.dtype:
+            dst.copy_(obs, non_blocking=True)
+        else:
+            lib.call('simq_states_to_bf16', ptr(obs), ptr(dst), dst.numel(), stream_ptr(self.device))
 
     def _put(self, obs, dst):
         """One observation into ring row `dst`: an ndarray through the pinned staging ring, a device tensor [96,96,C] / [1,96,96,C] by
@@ -443,11 +490,11 @@ class DeviceReplayBuffer:
             up = _upload_stream(self.device)
             up.wait_stream(cur)                                # (the tensor's producer runs on the caller's stream)
             with torch.cuda.stream(up):
-                dst.copy_(obs, non_blocking=True)
+                self._copy_row(obs, dst)
             obs.record_stream(up)
             self._staging.last_event = None
         else:
-            dst.copy_(obs, non_blocking=True)
+            self._copy_row(obs, dst)
             ev = torch.cuda.Event()
             ev.record(cur)
             self._staging.last_event = ev
@@ -473,8 +520,12 @@ class DeviceReplayBuffer:
                 self.push(states[i], actions[i], rewards[i], None if terminal[i] else next_states[i])
             return
         s0 = self.position
-        self.states[s0:s0 + n].copy_(torch.as_tensor(states))
-        self.next_states[s0:s0 + n].copy_(torch.as_tensor(next_states))
+        for ring, arr in ((self.states, states), (self.next_states, next_states)):
+            if self.dtype == torch.float32 or self.device.type != 'cuda':
+                ring[s0:s0 + n].copy_(torch.as_tensor(arr))
+            else:                                               # bf16 states: uploaded as fp32, rounded on the device into the ring
+                up = torch.as_tensor(arr, dtype=torch.float32).to(self.device).contiguous()
+                lib.call('simq_states_to_bf16', ptr(up), ptr(ring[s0:s0 + n]), up.numel(), stream_ptr(self.device))
         if self.device.type == 'cuda':
             self._bulk_event = torch.cuda.Event()
             self._bulk_event.record(torch.cuda.current_stream(self.device))
@@ -520,9 +571,9 @@ class DeviceReplayBuffer:
                 up.wait_event(ev_push)
             self._order_behind_writes(up)
             with torch.cuda.stream(up):
-                state = torch.empty((B, W, W, self.C), dtype=torch.float32, device=dev)
+                state = torch.empty((B, W, W, self.C), dtype=self.dtype, device=dev)
                 lib.call('simq_replay_gather', ptr(self.states), self.item, ptr(index), B, ptr(state), stream_ptr(dev))
-                next_state = torch.empty((len(nf), W, W, self.C), dtype=torch.float32, device=dev)
+                next_state = torch.empty((len(nf), W, W, self.C), dtype=self.dtype, device=dev)
                 if nf:
                     lib.call('simq_replay_gather', ptr(self.next_states), self.item, ptr(nindex), len(nf), ptr(next_state), stream_ptr(dev))
                 ready = torch.cuda.Event()
@@ -534,9 +585,9 @@ class DeviceReplayBuffer:
             return DeviceBatch(state, action, reward, next_state, pos, mask, ready)
         if self._write_events:
             self._order_behind_writes(torch.cuda.current_stream(dev))
-        state = torch.empty((B, W, W, self.C), dtype=torch.float32, device=dev)
+        state = torch.empty((B, W, W, self.C), dtype=self.dtype, device=dev)
         lib.call('simq_replay_gather', ptr(self.states), self.item, ptr(index), B, ptr(state), st)
-        next_state = torch.empty((len(nf), W, W, self.C), dtype=torch.float32, device=dev)
+        next_state = torch.empty((len(nf), W, W, self.C), dtype=self.dtype, device=dev)
         if nf:
             lib.call('simq_replay_gather', ptr(self.next_states), self.item, ptr(nindex), len(nf), ptr(next_state), st)
         self._note_read(torch.cuda.current_stream(dev))          # (a device write of a released slot waits for this gather: order_write)
@@ -555,16 +606,19 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
     pool_slots: observations the pool can hold (default capacity + 25 %, enough when pushes alias as the collector's do;
     independent state / next_state arrays need up to 2 * capacity)."""
 
-    def __init__(self, capacity, num_input_channels, device=None, pool_slots=None, upload_stream=True):
+    def __init__(self, capacity, num_input_channels, device=None, pool_slots=None, upload_stream=True, dtype='fp32'):
+        """dtype: as DeviceReplayBuffer's -- 'bf16' makes the pool bfloat16: the mapper writes rounded states straight into reserved
+        slots (simq_local_state_images_slots_bf16), adopt rounds fp32 tensors and scatters bf16 tensors as they are."""
+        self.dtype = _state_dtype(dtype)
         self.capacity = int(capacity)
         self.C = int(num_input_channels)
         self.device = torch.device('cuda' if device is None else device)
-        self.item = W * W * self.C
+        self._set_item()
         n = int(pool_slots) if pool_slots is not None else self.capacity + max(256, self.capacity // 4)
-        self.pool = torch.empty((n, W, W, self.C), dtype=torch.float32, device=self.device)
+        self.pool = torch.empty((n, W, W, self.C), dtype=self.dtype, device=self.device)
         self.states = self.next_states = self.pool          # both gathers of the base class read the one pool
         self._set_upload_mode(upload_stream)
-        self._staging = _PinnedStaging((W, W, self.C), self.device, on_upload_stream=self.ring_on_upload_stream)
+        self._staging = _PinnedStaging((W, W, self.C), self.device, on_upload_stream=self.ring_on_upload_stream, dtype=self.dtype)
         self._free = list(range(n - 1, -1, -1))
         self._ref = [0] * n
         self._recent = {}                                   # id(ndarray) -> (slot, ndarray): observations uploaded lately
@@ -670,12 +724,17 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
     def adopt(self, states):
         """Handles for the n states of a contiguous float32 device tensor [n, 96, 96, C] (a batch that did not come from the mapper:
         DQNIntentionPolicy's state + predicted map, a tensor another process sent): reserve(n) and one simq_replay_scatter on the
-        current stream.  States the mapper writes need no copy: reserve(n) and get_states(into=handles)."""
-        if not (torch.is_tensor(states) and states.dtype == torch.float32 and states.dim() == 4 and tuple(states.shape[1:]) == (W, W, self.C)
+        current stream.  States the mapper writes need no copy: reserve(n) and get_states(into=handles).
+        A pool of bf16 states takes a float32 tensor (rounded to nearest even by simq_states_to_bf16 first) or a bfloat16 tensor
+        (scattered as it is); a float32 pool takes float32 only."""
+        if not (torch.is_tensor(states) and states.dtype in (torch.float32, self.dtype) and states.dim() == 4 and tuple(states.shape[1:]) == (W, W, self.C)
                 and states.is_contiguous() and states.device == self.pool.device and states.shape[0] >= 1):
-            raise SimqError('adopt takes a contiguous float32 tensor [n >= 1, %d, %d, %d] on %s, got %s' % (
-                W, W, self.C, self.pool.device, '%s %s on %s' % (states.dtype, tuple(states.shape), states.device)
-                if torch.is_tensor(states) else type(states).__name__))
+            raise SimqError('adopt takes a contiguous %s tensor [n >= 1, %d, %d, %d] on %s, got %s' % (
+                'float32' if self.dtype == torch.float32 else 'float32 or bfloat16', W, W, self.C, self.pool.device,
+                '%s %s on %s' % (states.dtype, tuple(states.shape), states.device) if torch.is_tensor(states) else type(states).__name__))
+        if states.dtype != self.dtype:
+            from .fcn import to_bf16
+            states = to_bf16(states)
         handles = self.reserve(states.shape[0])
         try:
             self.write_slots('simq_replay_scatter', handles, lambda slots, d_desc: (
@@ -687,8 +746,8 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
         return handles
 
     def gather_handles(self, handles):
-        """The states of handles of this pool as one float32 device tensor [n, 96, 96, C] on the current stream (one
-        simq_replay_gather, behind the writes of the slots): what the policies step on."""
+        """The states of handles of this pool as one device tensor [n, 96, 96, C] of the pool's type (float32, or bfloat16 for
+        dtype='bf16') on the current stream (one simq_replay_gather, behind the writes of the slots): what the policies step on."""
         for h in handles:
             if not isinstance(h, _PoolObs) or h.pool is not self or not h.alive:
                 raise SimqError('gather_handles takes live handles of this pool, got %r' % (h,))
@@ -696,7 +755,7 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
         cur = torch.cuda.current_stream(dev)
         self._order_behind_writes(cur)
         index = torch.tensor([h.slot for h in handles], dtype=torch.int64, device=dev)
-        out = torch.empty((len(handles), W, W, self.C), dtype=torch.float32, device=dev)
+        out = torch.empty((len(handles), W, W, self.C), dtype=self.dtype, device=dev)
         lib.call('simq_replay_gather', ptr(self.pool), self.item, ptr(index), len(handles), ptr(out), stream_ptr(dev))
         self._note_read(cur)
         return out
@@ -973,6 +1032,24 @@ class PendingStep:
         return self._info
 
 
+def _batch_for_plan(policy_net, target_net, b):
+    """The minibatch in the element type the two nets' plans read, decided before anything is launched: a bf16 batch (a ring with
+    dtype='bf16') runs as it is on nets created with options={'bf16_states': 1} and is refused by any other; an fp32 batch for such nets is
+    rounded by two simq_states_to_bf16 launches on the current stream (it then carries no ready_event: its tensors were made here)."""
+    if policy_net.plan.bf16_states != target_net.plan.bf16_states:
+        raise SimqError("train: the policy net and the target net must agree on the plan option bf16_states (policy %d, target %d): both "
+                        "read the same minibatch" % (policy_net.plan.bf16_states, target_net.plan.bf16_states))
+    want = policy_net.state_dtype
+    if b.state.dtype == want and b.next_state.dtype == want:
+        return b
+    if torch.bfloat16 in (b.state.dtype, b.next_state.dtype) and want != torch.bfloat16:
+        raise SimqError("train: the minibatch holds bf16 states but the nets' plans lack the option bf16_states (create them as "
+                        "FCN(precision='bf16', options={'bf16_states': 1})); widening the batch with .float() is the caller's decision")
+    state = policy_net.as_states(b.state.contiguous(), 'train')
+    next_state = policy_net.as_states(b.next_state.contiguous(), 'train') if b.next_state.shape[0] else b.next_state.to(want)
+    return DeviceBatch(state, b.action, b.reward, next_state, b.nonfinal_pos, b.non_final_mask)
+
+
 def train_step(policy_net, target_net, batch, discount_factor, batch_size, lr, momentum, weight_decay,
                grad_norm_clipping, use_double_dqn=True, opt_state=None, process_group=None, global_batch=None,
                sync=True, comm=None, sync_bn=False, global_nonfinal=None, options=None):
@@ -1018,7 +1095,7 @@ def train_step(policy_net, target_net, batch, discount_factor, batch_size, lr, m
         raise SimqError('train_step: sync_bn needs a process group or a communicator (one process has nothing to synchronise)')
     if sync_bn and global_nonfinal is None:
         raise SimqError('train_step: sync_bn needs global_nonfinal (non-final next states of the whole minibatch)')
-    b = assemble_batch(batch, dev, allow_all_final=parallel)
+    b = _batch_for_plan(policy_net, target_net, assemble_batch(batch, dev, allow_all_final=parallel))
     B = b.state.shape[0]
     if b.next_state.shape[0] == 0 and not parallel:
         raise SimqError('train: batch has no non-final next state (the reference raises at train.py:112 too)')
@@ -1125,7 +1202,7 @@ def _train_step_fused(policy_net, target_net, b, discount_factor, gB, lr, moment
     Nn_real, Nn = Nn, max(Nn, 1)          # (all-terminal shard: the scratch tensors keep one row, the library is told 0)
     n = policy_net.num_output_channels * W * W
     for t, c in ((b.state, policy_net.num_input_channels), (b.next_state, policy_net.num_input_channels)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape[1:]) != (W, W, c):
+        if t.dtype != policy_net.state_dtype or not t.is_contiguous() or tuple(t.shape[1:]) != (W, W, c):
             raise SimqError('train: states must be contiguous fp32 [B,%d,%d,%d] (NHWC), got %s' % (W, W, c, tuple(t.shape)))
     policy_net._ensure_weights()
     target_net._ensure_weights()
@@ -1147,7 +1224,7 @@ def _train_step_fused(policy_net, target_net, b, discount_factor, gB, lr, moment
     a.comm = comm.handle if comm is not None else None
     a.sync_bn = 1 if (sync_bn and comm is not None) else 0
     a.global_nonfinal = int(global_nonfinal) if global_nonfinal is not None else Nn_real
-    next_state = b.next_state if Nn_real else torch.empty((1, W, W, policy_net.num_input_channels), **f32)
+    next_state = b.next_state if Nn_real else torch.empty((1, W, W, policy_net.num_input_channels), dtype=policy_net.state_dtype, device=dev)
     nonfinal_pos = b.nonfinal_pos if Nn_real else torch.zeros(1, dtype=torch.int32, device=dev)
     a.use_double_dqn, a.first_step = int(bool(use_double_dqn)), 0 if st_opt.initialised else 1
     a.gamma, a.lr, a.momentum, a.weight_decay = float(discount_factor), lr, momentum, weight_decay
@@ -1350,6 +1427,9 @@ def train_intention_step(intention_net, batch, lr, momentum, weight_decay, opt_s
     intention_net._order_behind_last_step()
     if isinstance(batch, DeviceBatch):
         full = batch.state
+        if full.dtype == torch.bfloat16:     # a ring of bf16 states: the BCE target (the last channel) and the split are fp32 arithmetic, so the
+            from .fcn import to_f32          # batch is widened exactly first -- the step is the fp32 step on the rounded states
+            full = to_f32(full.contiguous())
     else:
         full = torch.from_numpy(np.stack(batch.state)).to(dev, non_blocking=True)
     B, C = full.shape[0], full.shape[3]

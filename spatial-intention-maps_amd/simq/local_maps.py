@@ -186,7 +186,8 @@ def local_state_images(maps, channels, poses, robots=None, masks=None, out=None,
     (one pair, or P pairs).
     out: a contiguous float32 device tensor [P, 96, 96, C] to write into -- a slice of a replay ring's `states`, a batch buffer.
     into: instead of `out`, P handles of one AliasedDeviceReplayBuffer (reserve(P)) whose states have C channels: state p is written
-    into the pool slot of into[p] (simq_local_state_images_slots), inside the pool's stream order, and the handles are returned.
+    into the pool slot of into[p] (simq_local_state_images_slots), inside the pool's stream order, and the handles are returned.  A
+    pool of bf16 states (dtype='bf16') receives the fp32 state rounded once to nearest even (simq_local_state_images_slots_bf16).
 
     Raises SimqError, launching nothing, when the 136 x 136 crop around a robot or the stamp of a robot leaves its map (the reference
     would silently wrap or clip the slice), and for any other descriptor the library refuses."""
@@ -217,7 +218,9 @@ def write_into(pool, handles, args):
     """simq_local_state_images_slots for _prepare(into=)'s arguments: the slot table and the scratch come from the pool, which puts the
     launch into its stream order."""
     n_maps, n_robots, P, C = args[1], args[5], args[7], args[9]
-    pool.write_slots('simq_local_state_images_slots', handles, lambda slots, d_desc: args[:10] + (
+    # (a pool of bf16 states: the entry that rounds every element once as it stores it)
+    entry = 'simq_local_state_images_slots_bf16' if pool.pool.dtype == torch.bfloat16 else 'simq_local_state_images_slots'
+    pool.write_slots(entry, handles, lambda slots, d_desc: args[:10] + (
         slots, ptr(d_desc), ctypes.c_int64(d_desc.numel()), ptr(pool.pool), ctypes.c_int64(pool.pool.shape[0]), stream_ptr(pool.pool.device)),
         lib.c.simq_local_state_slots_desc_bytes(n_maps, n_robots, P, C))
 

@@ -873,7 +873,8 @@ class BatchedMapper:
         tensor [P, 96, 96, C] to write into -- a batch buffer, a slice of a replay ring's `states`; every element is written.
         into: instead of `out`, P handles of one AliasedDeviceReplayBuffer (ring.reserve(P)) for states of C channels: state p is
         written where it will be sampled from, the pool slot of into[p], and the handles are returned -- for TransitionTracker,
-        the policies' step_many and ring.push, which all take them where they take an ndarray.
+        the policies' step_many and ring.push, which all take them where they take an ndarray.  A pool of bf16 states
+        (AliasedDeviceReplayBuffer(..., dtype='bf16')) receives each state rounded once to nearest even (simq_local_state_images_slots_bf16).
 
         The distance images and the states are one launch each; the drawn maps one launch per room shape among the named mappers
         (simq_intention_maps draws maps of one shape).  Raises ValueError for a wrong robot count or `out`; SimqError, after the

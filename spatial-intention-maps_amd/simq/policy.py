@@ -45,7 +45,10 @@ class DQNPolicy:
             num_output_channels = arch.get_num_output_channels(robot_type)
             policy_nets.append(FCN(num_input_channels=self.cfg.num_input_channels,
                                    num_output_channels=num_output_channels, device=self.device,
-                                   precision=getattr(self.cfg, 'simq_precision', 'fp32')))
+                                   precision=getattr(self.cfg, 'simq_precision', 'fp32'),
+                                   # simq_plan_options overrides of the Q-networks, e.g. {'bf16_states': 1} for a run on bf16 replay pools:
+                                   # such nets step on handles of a bf16 pool as they are and round anything fp32 on the device
+                                   options=getattr(self.cfg, 'simq_plan_options', None)))
         return policy_nets
 
     build_network = build_policy_nets      # BASELINE.json's name for the same call
@@ -145,7 +148,9 @@ class DQNIntentionPolicy(DQNPolicy):
         """One HWC state [96,96,C-1] (ndarray, replay pool handle, or a device tensor [1,96,96,C-1]) -> device tensors
         (state_with_intention [1,96,96,C], sigmoid map [96,96])."""
         net = self.intention_nets[i]
-        x = s if torch.is_tensor(s) else states_batch([s], self.device) if is_handle(s) else \
+        # (fp32 arithmetic on the state itself -- sigmoid_concat: a handle of a bf16 pool is widened exactly first, simq_states_to_f32,
+        # and the results are the fp32 results on the rounded state)
+        x = s if torch.is_tensor(s) else states_batch([s], self.device, torch.float32) if is_handle(s) else \
             torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(self.device)
         logit = net.forward_nhwc(x)
         C = x.shape[3]
@@ -178,7 +183,7 @@ class DQNIntentionPolicy(DQNPolicy):
             return super().step(state, exploration_eps=exploration_eps, debug=debug)
         if self.train:                                                                      # drop the ground-truth map
             # (a pool handle is read on the device and loses its last channel there; an ndarray on the host, as always)
-            state = [[None if s is None else states_batch([s], self.device)[..., :-1].contiguous() if is_handle(s) else s[:, :, :-1]
+            state = [[None if s is None else states_batch([s], self.device, torch.float32)[..., :-1].contiguous() if is_handle(s) else s[:, :, :-1]
                       for s in g] for g in state]
         state = self.step_intention(state, debug=debug, _device=not debug)
         if debug:
@@ -209,7 +214,7 @@ class DQNIntentionPolicy(DQNPolicy):
                 net.eval()                                                                 # policies.py:101
                 xs = [states[e][i][j] for e, j in live]
                 if any(is_handle(s) for s in xs):                                          # pool handles: the batch is formed in HBM
-                    x = states_batch(xs, self.device)
+                    x = states_batch(xs, self.device, torch.float32)   # (handles of a bf16 pool: widened exactly, as in _predict)
                     if self.train:
                         x = x[..., :-1].contiguous()
                 else:

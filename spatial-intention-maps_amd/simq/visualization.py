@@ -49,6 +49,9 @@ def _on_device(x, dev, what, rank):
     """A contiguous float32 tensor on `dev`: a device tensor as it is (read in place), anything on the host uploaded."""
     if hasattr(x, 'device_row'):                 # an observation of a replay ring (a record's state, a pool handle): its row, in place
         x = x.device_row()
+        if x.dtype == torch.bfloat16:            # a ring of bf16 states: widened exactly (simq_states_to_f32), then everything as for fp32 --
+            from .fcn import to_f32              # the panels are the fp32 panels of the rounded state
+            x = to_f32(x.contiguous())
     if isinstance(x, np.ndarray):
         if x.dtype != np.float32:
             raise ValueError('%s must be float32, got %s' % (what, x.dtype))
