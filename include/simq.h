@@ -89,7 +89,9 @@ typedef struct simq_plan_options {
     int winograd_wgrad;           /* 1: weight gradients of the Winograd layers through the transform domain */
     int winograd_wgrad_f4;        /* 1: ... in F(4x4,3x3) where the tile count allows */
     /* bf16 plans: storage */
-    int stem_bf16;                /* 1: first convolution + its weight gradient on the bf16 matrix cores */
+    int stem_bf16;                /* 1: first convolution + its weight gradient on the bf16 matrix cores where 7 * num_input_channels <= 63;
+                                   * 2: as 1, and the wide-row form of both kernels where 64 <= 7 * num_input_channels <= 95 (10..13 channels,
+                                   * DESIGN 26); 0: the fp32 kernels.  Any other value is refused */
     int bf16_act_grads;           /* 1: activation gradients between the residual blocks' kernels travel as bf16 */
     int keep_fp32_activations;    /* 0: post-BN activations exist as bf16 planes only; 1 keeps fp32 copies (simq_workspace_tensor readers) */
     int fold_eval_bn_bf16;        /* 1: eval-mode BatchNorm folded into the convolution epilogues (one rounding instead of two) */
@@ -162,7 +164,8 @@ typedef struct simq_plan_options {
                                    * storage, NHWC, 2-byte aligned) behind its `const float*`: d_x of simq_forward / simq_forward_sync,
                                    * simq_train_args.state / next_state, and the backward entries through the copy the grad-mode forward
                                    * keeps (which is then a bf16 copy).  Only for plans whose first convolution runs stem_conv_bf16 -- precision
-                                   * SIMQ_PREC_BF16, stem_bf16 = 1 and 7 * num_input_channels <= 63 -- the creation of any other plan with
+                                   * SIMQ_PREC_BF16, stem_bf16 = 1 and 7 * num_input_channels <= 63, or stem_bf16 = 2 and <= 95 (the wide-row
+                                   * form) -- the creation of any other plan with
                                    * the option fails: that convolution (and its weight gradient) rounds every fp32 input element to
                                    * bf16 before anything else and nothing else reads the input, so a bf16 state that is the round-to-
                                    * nearest-even of the fp32 state gives bit for bit what the fp32 state gives, in half the bytes.  The
@@ -550,7 +553,8 @@ int simq_conv2d_wgrad_bnrelu_in(const float* d_y_pre, const float* d_in_scale, c
                                 int batch, int hin, int win, int cin, int cout, int r, int s, int stride, int pad, int form,
                                 float* d_scratch, void* stream, const simq_launch_opts* opts);
 /* The encoder's first convolution (reference resnet.py:94: 7x7, stride 2, pad 3, cin -> 64, no bias) on the bf16 matrix cores with
- * the operands gathered straight from the fp32 NHWC input -- the form plain-bf16 plans use (stem_conv_bf16.hip).  7 * cin <= 63,
+ * the operands gathered straight from the fp32 NHWC input -- the form plain-bf16 plans use (stem_conv_bf16.hip).  7 * cin <= 63 (the
+ * *_wide entries below take 64 <= 7 * cin <= 95),
  * win a multiple of 32, hin even.  d_y: bf16 [batch][hin/2][win/2][64] (pre-BatchNorm, rounded once from the fp32 accumulators);
  * d_stats: NULL or [2*64] zeroed (sum | sum of squares of the UNROUNDED outputs); d_scratch: 58 368 bytes (bf16 weight layout). */
 /* ... and in exact fp32 (v_mfma_f32_16x16x4_f32 fed by 16-byte runs of the NHWC input; what fp32 / split-bf16 plans run): 7 * cin <= 64,
@@ -572,6 +576,26 @@ int simq_conv2d_fwd_stem_bf16_x16(const uint16_t* d_x, const float* d_w_ohwi, ui
                                   double* d_stats, void* d_scratch, void* stream);
 int simq_conv2d_wgrad_stem_bf16_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
                                     float* d_scratch, void* stream);
+/* The wide-row forms of the four operators above: 64 <= 7 * cin <= 95 (cin 10..13), the same kernels with three k-steps of the matrix
+ * core per filter row instead of two -- what a plain-bf16 plan with simq_plan_options.stem_bf16 = 2 launches for such an input (the
+ * narrow entries keep refusing cin >= 10, these refuse everything else).  Arguments, results and their layout as above, except
+ * d_scratch of the forward: simq_conv2d_fwd_stem_bf16_wide_scratch_bytes() bytes (87 040: bf16 weight rows of 7 * 96 + 8), and
+ * d_scratch of the weight gradient: simq_conv2d_wgrad_stem_bf16_slabs(batch, hin, win, cin, -1) * 64 * 49 * cin floats. */
+int64_t simq_conv2d_fwd_stem_bf16_wide_scratch_bytes(void);
+int simq_conv2d_fwd_stem_bf16_wide(const float* d_x, const float* d_w_ohwi, uint16_t* d_y, int batch, int hin, int win, int cin,
+                                   double* d_stats, void* d_scratch, void* stream);
+int simq_conv2d_wgrad_stem_bf16_wide(const float* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
+                                     float* d_scratch, void* stream);
+int simq_conv2d_fwd_stem_bf16_wide_x16(const uint16_t* d_x, const float* d_w_ohwi, uint16_t* d_y, int batch, int hin, int win, int cin,
+                                       double* d_stats, void* d_scratch, void* stream);
+int simq_conv2d_wgrad_stem_bf16_wide_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
+                                         float* d_scratch, void* stream);
+/* Partial-sum slabs (64 * 49 * cin floats each) the stem weight gradient, narrow or wide, uses for this batch when its scratch holds
+ * capacity_bytes: min(what the batch asks for -- the formula at simq_conv2d_wgrad_stem_bf16 --, capacity_bytes / slab bytes); 0 when not
+ * even one slab fits (the launch then refuses), capacity_bytes < 0: no limit, which is what the eight standalone entries assume of
+ * d_scratch.  (The blocks are persistent, so any count >= 1 covers the batch.  A plan keeps the slabs in a dead workspace slot of
+ * batch * 1 179 648 bytes: that holds the 9 * batch slabs asked for up to cin = 10 and fewer beyond.)  -1 on a bad argument. */
+int simq_conv2d_wgrad_stem_bf16_slabs(int batch, int hin, int win, int cin, int64_t capacity_bytes);
 /* Weight gradient of the same convolution through the transform domain (dy / x transforms, 16 batched contractions over
  * the tiles, G^T dU G).  Additionally cin % 128 == 0 and cout % 128 == 0.  d_dw is overwritten.
  * the tiles, G^T dU G); uses F(4x4,3x3) when hin, win are multiples of 4 and batch*(hin/4)*(win/4) is a multiple of 16.
@@ -1271,7 +1295,7 @@ int simq_profile_start(void);
 int simq_profile_stop(double* out, int max_kinds);
 /* ... and a launch log (always on): every launcher names the kernel FAMILY that took a launch -- "igemm_bf16_img_whole" / "_half" (image
  * tile), "igemm_bf16_c64", "igemm_bf16_pp", "igemm_bf16_dma", "igemm_bf16_reg", "wgrad_bf16_img", "wgrad_bf16_pp", "wgrad_bf16_reg",
- * "stem_conv_bf16", "stem_wgrad_bf16", "bn_apply16", "bn_bwd_apply16[_mask_from_y]", "gemm_f32_batched", "igemm_f32", "conv_img_f32",
+ * "stem_conv_bf16", "stem_wgrad_bf16", "stem_conv_bf16_wide[_x16]", "stem_wgrad_bf16_wide[_x16]", "bn_apply16", "bn_bwd_apply16[_mask_from_y]", "gemm_f32_batched", "igemm_f32", "conv_img_f32",
  * "stem_conv_f32", "winograd_f2" / "winograd_f4" [_wgrad], "wgrad_f32" [_batched] ... (csrc: note_launch).  simq_launch_count: launches
  * of one family since the last reset (0 for a name that never ran); simq_launch_counts: "name=count;..." of every family that ran.
  * The parity tests use it to assert that the kernels a batch size is meant to select DID run. */

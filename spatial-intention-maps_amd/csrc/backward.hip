@@ -318,10 +318,19 @@ int backward_impl(const Ctx& c, const float* d_dq, int phase, const OneHotGrad* 
     RC(trace(TL.stem.dz, T0, (int64_t)B * 2304 * 64 * 4));
     RC(bn_bwd(c, p->stem_bn, T0, nullptr, c.f(L.y0), T1, nullptr, (int64_t)B * 2304, !no_stem_fuse, nullptr, y0_bf16));   // (pre-BN output: fp32, or bf16 from stem_conv_bf16)
     RC(trace(TL.stem.dy0, stem16 ? (const void*)T1.pl.hi : (const void*)T1.f, (int64_t)B * 2304 * 64 * (stem16 ? 2 : 4)));
-    if (stem16 && p->opt.bf16_states)                // (bf16 states: the caller's minibatch, or the forward's bf16 copy of it)
-        RC(launch_stem_wgrad_bf16_x16(reinterpret_cast<const uint16_t*>(x0.f), T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream));
-    else if (stem16)                                 // (T0 = dz is dead behind bn_bwd: it holds the partial-sum slabs)
-        RC(launch_stem_wgrad_bf16(x0.f, T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream));
+    // (T0 = dz is dead behind bn_bwd: it holds the partial-sum slabs.  A slot is smax floats and 9 B slabs of 64 * 49 * Cin floats fit it
+    // up to Cin = 10 only: the launch takes as many slabs as the slot holds and refuses when it holds none)
+    const int64_t slab_cap = smax * (int64_t)sizeof(float);
+    if (stem16 && c.W.stem_wide && p->opt.bf16_states)
+        RC(launch_stem_wgrad_bf16_wide_x16(reinterpret_cast<const uint16_t*>(x0.f), T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream,
+                                           slab_cap));
+    else if (stem16 && c.W.stem_wide)
+        RC(launch_stem_wgrad_bf16_wide(x0.f, T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream, slab_cap));
+    else if (stem16 && p->opt.bf16_states)           // (bf16 states: the caller's minibatch, or the forward's bf16 copy of it)
+        RC(launch_stem_wgrad_bf16_x16(reinterpret_cast<const uint16_t*>(x0.f), T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream,
+                                      slab_cap));
+    else if (stem16)
+        RC(launch_stem_wgrad_bf16(x0.f, T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream, slab_cap));
     else
         RC(conv_wgrad(c, p->stem, x0, T1, 96, InBn(), true));
     if (late_join) RC(join());

@@ -246,11 +246,25 @@ int launch_stem_conv_f32(const float* x, const float* w_ohwi, float* y, double* 
 bool stem_conv_bf16_eligible(int H, int W, int C, int cout, int k, int stride, int pad);
 int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, hipStream_t stream);
 int launch_stem_conv_bf16(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
-int stem_wgrad_bf16_slabs(int B, int H, int W);      // partial-sum slabs (64 * 49 * C floats each) the weight gradient needs as scratch
-int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream);
+int stem_wgrad_bf16_slabs(int B, int H, int W);      // partial-sum slabs (64 * 49 * C floats each) the weight gradient asks for as scratch
+// ... and uses when its scratch holds partial_bytes (< 0: as much as it asks for); 0 = not even one slab fits (the launch refuses)
+int stem_wgrad_bf16_slabs_cap(int B, int H, int W, int C, int64_t partial_bytes);
+int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                           int64_t partial_bytes = -1);
 // the same two kernels over bf16 states (simq_plan_options.bf16_states): x is [B][H][W][C] bf16, 2-byte aligned
 int launch_stem_conv_bf16_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
-int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream);
+int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                               int64_t partial_bytes = -1);
+// the wide-row forms of all of them, 64 <= 7 * C <= 95 (simq_plan_options.stem_bf16 = 2): three k-steps per filter row, weight rows of 96
+int stem_conv_bf16_wide_wbytes();
+bool stem_conv_bf16_wide_eligible(int H, int W, int C, int cout, int k, int stride, int pad);
+int launch_stem_weight_prep_wide(const float* w, uint16_t* w16, int C, hipStream_t stream);
+int launch_stem_conv_bf16_wide(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
+int launch_stem_conv_bf16_wide_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
+int launch_stem_wgrad_bf16_wide(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                                int64_t partial_bytes = -1);
+int launch_stem_wgrad_bf16_wide_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                                    int64_t partial_bytes = -1);
 int launch_stem_pool_bwd(const float* g, const float* pooled, const uint8_t* idx, float* dz, int B, int H, int W,
                          int C, hipStream_t stream, int g_bf16 = 0, const float* y = nullptr, const float* mean = nullptr,
                          const float* invstd = nullptr, double* red = nullptr, int y_bf16 = 0, int replicas = 1);   // red: fused BN-backward sums

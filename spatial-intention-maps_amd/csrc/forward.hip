@@ -108,7 +108,16 @@ int forward_impl(const Ctx& c, int mode, const float* d_x, float* d_q) {
     // stem: conv 7x7 s2 -> BN -> ReLU -> maxpool 3x3 s2   (resnet.py:94-97); always the fp32 kernel (Cin is 3..10)
     Act x0; x0.f = (mode == SIMQ_MODE_TRAIN && !c.x_ext) ? c.f(L.x) : const_cast<float*>(d_x);
     const int stem16 = c.W.stem16 >= 0 ? 1 : 0;      // plain-bf16 plans: bf16 matrix cores, bf16 pre-BN output (stem_conv_bf16.hip)
-    if (stem16) {
+    if (stem16 && c.W.stem_wide) {                   // 64 <= 7 * Cin <= 95 under stem_bf16 = 2: the wide-row form of the same kernel
+        if (p->opt.bf16_states)
+            RC(launch_stem_conv_bf16_wide_x16(reinterpret_cast<const uint16_t*>(x0.f), reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16),
+                                              reinterpret_cast<uint16_t*>(c.f(L.y0)), mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96,
+                                              p->cin, c.stream));
+        else
+            RC(launch_stem_conv_bf16_wide(x0.f, reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16), reinterpret_cast<uint16_t*>(c.f(L.y0)),
+                                          mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96, p->cin, c.stream));
+        if (mode != SIMQ_MODE_EVAL) RC(c.sync_reduce(c.red(p->stem_bn), 2 * (int64_t)p->stem_bn.C));
+    } else if (stem16) {
         if (p->opt.bf16_states)     // (plan creation has made sure that such a plan takes this branch)
             RC(launch_stem_conv_bf16_x16(reinterpret_cast<const uint16_t*>(x0.f), reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16),
                                          reinterpret_cast<uint16_t*>(c.f(L.y0)), mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96,

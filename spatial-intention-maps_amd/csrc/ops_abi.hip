@@ -232,6 +232,52 @@ int simq_conv2d_wgrad_stem_bf16_x16(const uint16_t* d_x, const uint16_t* d_dy, f
     return launch_stem_wgrad_bf16_x16(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
 }
 
+// ... and the wide-row forms of the four, 64 <= 7 * cin <= 95 (what a plan with simq_plan_options.stem_bf16 = 2 launches at 10..13 channels)
+#define SIMQ_WIDE_GEOMETRY(name) \
+    SIMQ_REQUIRE(stem_conv_bf16_wide_eligible(hin, win, cin, 64, 7, 2, 3), name ": geometry not supported (64 <= 7 * cin <= 95, win %% 32 == 0)")
+
+int64_t simq_conv2d_fwd_stem_bf16_wide_scratch_bytes(void) { return stem_conv_bf16_wide_wbytes(); }
+
+int simq_conv2d_wgrad_stem_bf16_slabs(int batch, int hin, int win, int cin, int64_t capacity_bytes) {
+    SIMQ_REQUIRE(batch >= 1 && hin >= 2 && win >= 32 && cin >= 1, "conv2d_wgrad_stem_bf16_slabs: bad argument");
+    return stem_wgrad_bf16_slabs_cap(batch, hin, win, cin, capacity_bytes);
+}
+
+int simq_conv2d_fwd_stem_bf16_wide(const float* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
+                                   void* d_scratch, void* stream) {
+    SIMQ_REQUIRE(d_x && d_w && d_y && d_scratch && batch >= 1, "conv2d_fwd_stem_bf16_wide: bad argument");
+    SIMQ_WIDE_GEOMETRY("conv2d_fwd_stem_bf16_wide");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RC(launch_stem_weight_prep_wide(d_w, static_cast<uint16_t*>(d_scratch), cin, st));
+    return launch_stem_conv_bf16_wide(d_x, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
+}
+
+int simq_conv2d_wgrad_stem_bf16_wide(const float* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin, float* d_scratch,
+                                     void* stream) {
+    SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16_wide: bad argument");
+    SIMQ_WIDE_GEOMETRY("conv2d_wgrad_stem_bf16_wide");
+    return launch_stem_wgrad_bf16_wide(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
+}
+
+int simq_conv2d_fwd_stem_bf16_wide_x16(const uint16_t* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
+                                       void* d_scratch, void* stream) {
+    SIMQ_REQUIRE(d_x && d_w && d_y && d_scratch && batch >= 1, "conv2d_fwd_stem_bf16_wide_x16: bad argument");
+    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_fwd_stem_bf16_wide_x16: d_x must be 2-byte aligned");
+    SIMQ_WIDE_GEOMETRY("conv2d_fwd_stem_bf16_wide_x16");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RC(launch_stem_weight_prep_wide(d_w, static_cast<uint16_t*>(d_scratch), cin, st));
+    return launch_stem_conv_bf16_wide_x16(d_x, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
+}
+
+int simq_conv2d_wgrad_stem_bf16_wide_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
+                                         float* d_scratch, void* stream) {
+    SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16_wide_x16: bad argument");
+    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_wgrad_stem_bf16_wide_x16: d_x must be 2-byte aligned");
+    SIMQ_WIDE_GEOMETRY("conv2d_wgrad_stem_bf16_wide_x16");
+    return launch_stem_wgrad_bf16_wide_x16(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
+}
+#undef SIMQ_WIDE_GEOMETRY
+
 int simq_states_to_bf16(const float* d_src, uint16_t* d_dst, int64_t n, void* stream) {
     SIMQ_REQUIRE(d_src && d_dst && n >= 1, "states_to_bf16: NULL pointer or n < 1");
     SIMQ_REQUIRE(((uintptr_t)d_src & 3) == 0 && ((uintptr_t)d_dst & 1) == 0, "states_to_bf16: d_src must be 4-byte and d_dst 2-byte aligned");

@@ -132,7 +132,10 @@ Layout make_layout(const simq_plan* p, int B);      // layout.hip
 // Weight cache (caller-owned, one per parameter set): derived copies of the convolution weights that only change when
 // the parameters do -- fp32: flipped/transposed weights for dgrad; matrix-core precisions: bf16 planes of the weights
 // and of their flipped/transposed form.  Filled by simq_weights_prepare.
-struct WLayout { int64_t wt = -1, wpl = -1, wtpl = -1, wu = -1, stem16 = -1, total = 0; };
+struct WLayout {
+    int64_t wt = -1, wpl = -1, wtpl = -1, wu = -1, stem16 = -1, total = 0;
+    bool stem_wide = false;      // stem16 >= 0 holds the wide-row layout (64 <= 7 * Cin <= 95, stem_bf16 = 2): the walks launch the *_wide kernels
+};
 WLayout make_wlayout(const simq_plan* p);            // layout.hip
 
 struct Act {          // a tensor some convolution reads: fp32 view + (matrix-core precisions) its bf16 planes

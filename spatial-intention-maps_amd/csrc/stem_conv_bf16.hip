@@ -1,4 +1,4 @@
-// First convolution of the encoder (reference resnet.py:94: conv 7x7, stride 2, pad 3, Cin = 3..9 -> 64, no bias) on the bf16 matrix
+// First convolution of the encoder (reference resnet.py:94: conv 7x7, stride 2, pad 3, Cin = 3..9 (wide-row form: 10..13) -> 64, no bias) on the bf16 matrix
 // cores, for plain-bf16 plans.  The implicit-GEMM kernels need Cin % 32 == 0; with 3..9 input channels the fp32 kernel gathers its
 // operands one float at a time (169 us at B = 128: 55 TF/s).  What this kernel uses instead:
 //
@@ -14,6 +14,8 @@
 //     block (fp32 per lane -> fp64 per block) are pushed with atomics ONCE per block.
 //   * Output: the pre-BatchNorm map as bf16 (like every other matrix-core convolution of a plain-bf16 plan; statistics from the fp32
 //     accumulators).
+//   * Cin = 10..13 (7*Cin = 70..91: simq_plan_options.stem_bf16 = 2): the same kernels with THREE k-steps per filter row
+//     (K = 96, rows of 680 elements in LDS, one block of 16 waves per CU); the figures above are for Cin <= 9.
 #include <cstdint>
 
 #include "common.h"
@@ -23,6 +25,7 @@ namespace simq {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 typedef float floatx4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // a 16-byte load the compiler may not assume aligned
 typedef uint16_t ushortx8_a2 __attribute__((ext_vector_type(8), aligned(2))); // ... of 8 bf16: the window starts at (2 ox - 3) * C ELEMENTS, odd for odd C
 
@@ -50,9 +53,25 @@ template <> struct Frag<uint16_t> {
     static __device__ __forceinline__ __bf16 cvt(uint16_t v) { return __builtin_bit_cast(__bf16, v); }
 };
 
-constexpr int COUT = 64, R = 7, KROW = 64;            // K per filter row (7 * Cin <= 63 real)
-constexpr int WROW = R * KROW + 8;                     // LDS row of one output channel: 456 bf16 = 228 dwords (36 mod 64: conflict-free)
-constexpr int SMEM_W = COUT * WROW * 2;                // 58 368 B
+// Every kernel below carries the number of k-steps KS of a filter row as a template parameter:
+//   KS = 2  the narrow form, 7 * Cin <= 63   (Cin 1..9):   KROW = 64, what every default plan launches
+//   KS = 3  the wide-row form, 64 <= 7 * Cin <= 95 (Cin 10..13): KROW = 96 (simq_plan_options.stem_bf16 = 2, the *_wide entries)
+constexpr int COUT = 64, R = 7;
+template <int KS> struct Row {
+    static constexpr int KROW = 32 * KS;               // K per filter row: 64 (7 * Cin <= 63 real) | 96 (7 * Cin <= 95 real)
+    // LDS row of one output channel.  KS = 2: 456 bf16 = 228 dwords (36 mod 64: conflict-free).  KS = 3: 680 bf16 = 340 dwords = 20 mod 64:
+    // a ds_read_b128 serves 16 lanes (fi = 0..15, one kg) per pass, lane fi starts at bank 20 fi mod 64 = 0 20 40 60 16 36 56 12 32 52 8
+    // 28 48 4 24 44 -- sixteen different multiples of 4, four banks each: all 64 banks once, conflict-free (20 / 4 = 5 is odd)
+    static constexpr int WROW = R * KROW + 8;
+    static constexpr int SMEM_W = COUT * WROW * 2;     // 58 368 B | 87 040 B
+    // waves per block (they share the LDS copy of the weights).  KS = 2: 9 x 512 blocks = one 16-pixel tile per wave and trip, two blocks
+    // a CU, 4.5 waves per SIMD hide each other's load latency.  KS = 3: 87 KB of weights + statistics scratch no longer fit a CU's 160 KB
+    // twice: ONE block of 16 waves (1024 threads, 4 waves per SIMD, 128 registers a lane) per CU -- the weights are staged once per CU
+    // and x is read once (blocks owning half of the output channels would read x twice)
+    static constexpr int NWAVE = KS == 2 ? 9 : 16;
+    static constexpr int BLOCKS_PER_CU = KS == 2 ? 2 : 1;
+    static constexpr int TILES = 2 * KS;               // 16-column tiles of a filter row in the weight gradient
+};
 
 template <typename XE>
 struct StemArgs {
@@ -61,12 +80,10 @@ struct StemArgs {
     unsigned x_bytes;
 };
 
-constexpr int NWAVE = 9;                               // waves per block (they share the LDS copy of the weights): 9 x 512 blocks = one
-                                                       // 16-pixel tile per wave and trip, 4.5 waves per SIMD hide each other's load latency
-
-template <typename XE>
-__global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const StemArgs<XE> p) {
+template <typename XE, int KS>
+__global__ void __launch_bounds__(Row<KS>::NWAVE * 64, Row<KS>::BLOCKS_PER_CU) stem_conv_bf16_kernel(const StemArgs<XE> p) {
     typedef typename Frag<XE>::E E;
+    constexpr int KROW = Row<KS>::KROW, WROW = Row<KS>::WROW, SMEM_W = Row<KS>::SMEM_W, NWAVE = Row<KS>::NWAVE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint16_t* wl = reinterpret_cast<uint16_t*>(smem);
     double* red = reinterpret_cast<double*>(smem + SMEM_W);          // [NWAVE][64][2]
@@ -110,12 +127,30 @@ __global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const Ste
         // are skipped before it is used); per k-step whether some lane's 8-float fragment touches the left / right padding (ballot)
         const int e_lo = (2 * (ox0 + fi) - 3) * p.C + kg * 8;
         const XE* prow = p.x + ((long)(b * p.H + 2 * oy - 3) * rowf + e_lo);
-        bool side[2], real[2];
+        bool side[KS], real[KS];
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < KS; ++s) {
             const int e = e_lo + s * 32;
-            real[s] = s * 32 + kg * 8 < kreal;                       // k-groups entirely behind the 7*Cin real values are not loaded
+            // k-groups entirely behind the 7*Cin real values are not loaded (KS = 3: 7*Cin >= 64, the first two steps are real in every lane)
+            real[s] = (KS == 3 && s < 2) || s * 32 + kg * 8 < kreal;
             side[s] = __builtin_amdgcn_ballot_w64((e < 0 || e + 8 > rowf) && real[s]) != 0;
+        }
+        // KS = 3: what a lane keeps of a fragment is one interval [qlo, qhi) of its 8 elements -- the left padding cuts in front, the right
+        // padding and the end of the 7 * Cin real values behind.  The elements behind the real values of a partly real k-group (always in
+        // the third step: 7 * Cin >= 64) are x values of the NEXT pixel; their weights are zero, but 0 * NaN is NaN, so they are cleared
+        // to +0 like the padding and a NaN / Inf there reaches no output the convolution does not give it to (rules 1 and 2).
+        // The interval is kept as four dword masks over the packed bf16 fragment per k-step, in vector registers: the 24 selects of the
+        // narrow form's shape hold 24 loop-invariant lane masks in scalar registers, which three k-steps no longer have (spills)
+        unsigned keep[KS][4];
+        if constexpr (KS == 3) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const int e = e_lo + s * 32;
+                const int qlo = max(0, -e), qhi = min(min(8, rowf - e), kreal - (s * 32 + kg * 8));
+#pragma unroll
+                for (int d = 0; d < 4; ++d)
+                    keep[s][d] = ((2 * d >= qlo && 2 * d < qhi) ? 0xffffu : 0u) | ((2 * d + 1 >= qlo && 2 * d + 1 < qhi) ? 0xffff0000u : 0u);
+            }
         }
 #pragma unroll 1
         for (int ky = 0; ky < R; ++ky) {
@@ -123,34 +158,51 @@ __global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const Ste
             if ((unsigned)iy >= (unsigned)p.H) continue;                                      // wave-uniform: a padding row
             // the first row of the first image and the last row of the last: a fragment may reach outside the tensor
             const bool tensor_edge = (b == 0 && iy == 0) || (b == p.B - 1 && iy == p.H - 1);   // wave-uniform
-            E v[2][8];
-            // fragments of both k-steps: 8 consecutive floats of x each, straight from global memory (dword-aligned 16-byte loads: the
-            // window starts at (2 ox - 3) * C floats), all four loads issued before the first mask
+            E v[KS][8];
+            // fragments of all k-steps: 8 consecutive floats of x each, straight from global memory (dword-aligned 16-byte loads: the
+            // window starts at (2 ox - 3) * C floats), all loads issued before the first mask.  (KS = 3: real[2] differs between the
+            // lanes of a wave -- at Cin = 10 only k-group 0 of the third step holds real values -- so its loads are lane-divergent.)
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < KS; ++s) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[s][q] = E(0);
                 if (real[s]) {
                     const XE* src = prow + (ky * rowf + s * 32);
                     if (!tensor_edge) {
                         Frag<XE>::load8(src, v[s]);
-                    } else {
+                    } else if constexpr (KS == 2) {
                         const long g0 = src - p.x;
 #pragma unroll
                         for (int q = 0; q < 8; ++q) v[s][q] = (g0 + q >= 0 && g0 + q < total) ? src[q] : E(0);
+                    } else {
+                        // An element outside the tensor lies left of the first row of the first image (e + q < 0) or right of the last row
+                        // of the last (e + q >= rowf), where the keep masks clear it whatever was loaded: its ADDRESS is clamped into the
+                        // tensor (v_max / v_min, no lane mask) and the load is unconditional.  Element indices fit 31 bits (the launcher
+                        // checks).
+                        const int g0 = (int)(src - p.x), last = (int)total - 1;
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) v[s][q] = p.x[min(max(g0 + q, 0), last)];
                     }
                 }
             }
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < KS; ++s) {
+                if constexpr (KS == 2) {
                 if (side[s]) {                                         // wave-uniform: some lane touches the left / right padding
                     const int e = e_lo + s * 32;
 #pragma unroll
                     for (int q = 0; q < 8; ++q) v[s][q] = ((unsigned)(e + q) < (unsigned)rowf) ? v[s][q] : E(0);
                 }
+                }
                 bf16x8 af;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) af[q] = Frag<XE>::cvt(v[s][q]);
+                if constexpr (KS == 3) {                               // (a cleared element is +0.0 whatever it held, a NaN included)
+                    uintx4 ab = __builtin_bit_cast(uintx4, af);
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) ab[d] &= keep[s][d];
+                    af = __builtin_bit_cast(bf16x8, ab);
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const bf16x8 bf = *reinterpret_cast<const bf16x8*>(wfrag + j * 16 * WROW + ky * KROW + s * 32);
@@ -187,8 +239,10 @@ __global__ void __launch_bounds__(NWAVE * 64, 2) stem_conv_bf16_kernel(const Ste
     }
 }
 
-// w [64][7][7][C] fp32 (OHWI) -> w16 [64][WROW] bf16: element ky * 64 + kx * C + c, zeros elsewhere
+// w [64][7][7][C] fp32 (OHWI) -> w16 [64][WROW] bf16: element ky * KROW + kx * C + c, zeros elsewhere
+template <int KS>
 __global__ void stem_weight_prep_kernel(const float* __restrict__ w, uint16_t* __restrict__ w16, int C) {
+    constexpr int KROW = Row<KS>::KROW, WROW = Row<KS>::WROW;
     const int total = COUT * WROW;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int o = i / WROW, e = i - o * WROW;
@@ -208,8 +262,10 @@ __global__ void stem_weight_prep_kernel(const float* __restrict__ w, uint16_t* _
 // 4 + 4 ds_read_b128 fragments, 16 MFMAs (64 x 64 outputs over k = 32 pixels).  Blocks are persistent; every block leaves its 64 x 7 x 7C
 // partial sums in a scratch slab and a second launch adds the slabs in a fixed order (deterministic; atomics over 15 680 addresses
 // from 512 blocks would be neither that nor fast).
+// The wide form (KS = 3): XT_ky is [96 n][32 pix] (LDS 58 880 B), wave ky contracts 64 x 96 -- six column tiles, 96 accumulator registers, one
+// block per CU -- and a (pixel, filter row) has 12 k-groups, so the staging loop's slot index is divided, not shifted.
 constexpr int TROW = 40;                               // LDS row: 32 pixels + 8 pad (80 B: conflict-free ds_read_b128 over 16 rows)
-constexpr int WG_SMEM = (COUT + R * KROW) * TROW * 2;  // dyT + 7 x XT = 40 960 B
+template <int KS> constexpr int wg_smem() { return (COUT + R * Row<KS>::KROW) * TROW * 2; }   // dyT + 7 x XT = 40 960 B | 58 880 B
 constexpr int WG_WAVES = 8;
 
 template <typename XE>
@@ -218,12 +274,13 @@ struct StemWgradArgs {
     int B, H, W, C, Ho, Wo;
 };
 
-template <typename XE>
-__global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const StemWgradArgs<XE> p) {
+template <typename XE, int KS>
+__global__ void __launch_bounds__(WG_WAVES * 64, Row<KS>::BLOCKS_PER_CU) stem_wgrad_bf16_kernel(const StemWgradArgs<XE> p) {
     typedef typename Frag<XE>::E E;
-    __shared__ __attribute__((aligned(16))) uint16_t lds[WG_SMEM / 2];
+    constexpr int KROW = Row<KS>::KROW, NT = Row<KS>::TILES, NG = 4 * KS;   // columns, column tiles and k-groups of a filter row
+    __shared__ __attribute__((aligned(16))) uint16_t lds[wg_smem<KS>() / 2];
     uint16_t* dyT = lds;                                // [64][TROW]
-    uint16_t* XT = lds + COUT * TROW;                   // [7][64][TROW]
+    uint16_t* XT = lds + COUT * TROW;                   // [7][KROW][TROW]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rowf = p.W * p.C, kreal = R * p.C;
@@ -233,11 +290,11 @@ __global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const
     const int ntiles = p.B * p.Ho * tiles_per_row;
     const int nchunks = (ntiles + 1) / 2;
     const int fi = lane & 15, kg = lane >> 4;
-    floatx4 acc[4][4];
+    floatx4 acc[4][NT];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NT; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
 
     for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         // ---- stage dyT: 32 pixels x 64 channels; lane -> (pixel, 8-channel group), 16-byte load, 8 scattered 2-byte stores
@@ -251,8 +308,14 @@ __global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const
             for (int q = 0; q < 8; ++q) dyT[(cg * 8 + q) * TROW + pix] = (uint16_t)(q & 1 ? w[q >> 1] >> 16 : w[q >> 1] & 0xffffu);
         }
         // ---- stage XT: slots (ky, tile, pixel, k-group); only the k-groups with real values (the others feed discarded columns)
-        for (int f = tid; f < R * 2 * 16 * 8; f += WG_WAVES * 64) {
-            const int grp = f & 7, i = (f >> 3) & 15, t = (f >> 7) & 1, ky = f >> 8;
+        for (int f = tid; f < R * 2 * 16 * NG; f += WG_WAVES * 64) {
+            int grp, i, t, ky;
+            if constexpr (KS == 2) {
+                grp = f & 7; i = (f >> 3) & 15; t = (f >> 7) & 1; ky = f >> 8;
+            } else {
+                const unsigned pix = (unsigned)f / NG;                  // 12 k-groups: no power of two
+                grp = (int)((unsigned)f - pix * NG); i = pix & 15; t = (pix >> 4) & 1; ky = (int)(pix >> 5);
+            }
             if (grp >= ngrp) continue;
             const int tile = chunk * 2 + t;
             E v[8] = {E(0), E(0), E(0), E(0), E(0), E(0), E(0), E(0)};
@@ -283,16 +346,23 @@ __global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const
         __syncthreads();
         // ---- wave ky: out[o][n] += sum over the 32 pixels of dyT[o][pix] * XT_ky[n][pix]
         if (wave < R) {
-            bf16x8 af[4], bf[4];
+            bf16x8 af[4], bf[NT];
+            if constexpr (KS == 2) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                af[j] = *reinterpret_cast<const bf16x8*>(dyT + (j * 16 + fi) * TROW + kg * 8);
-                bf[j] = *reinterpret_cast<const bf16x8*>(XT + (wave * KROW + j * 16 + fi) * TROW + kg * 8);
+                for (int j = 0; j < 4; ++j) {
+                    af[j] = *reinterpret_cast<const bf16x8*>(dyT + (j * 16 + fi) * TROW + kg * 8);
+                    bf[j] = *reinterpret_cast<const bf16x8*>(XT + (wave * KROW + j * 16 + fi) * TROW + kg * 8);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) af[j] = *reinterpret_cast<const bf16x8*>(dyT + (j * 16 + fi) * TROW + kg * 8);
+#pragma unroll
+                for (int j = 0; j < NT; ++j) bf[j] = *reinterpret_cast<const bf16x8*>(XT + (wave * KROW + j * 16 + fi) * TROW + kg * 8);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
         }
         __syncthreads();
     }
@@ -302,7 +372,7 @@ __global__ void __launch_bounds__(WG_WAVES * 64, 2) stem_wgrad_bf16_kernel(const
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < NT; ++j)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int o = i * 16 + 4 * kg + r, n = j * 16 + fi;
@@ -341,18 +411,46 @@ int stem_wgrad_bf16_slabs(int B, int H, int W) {
     return blocks;
 }
 
+// ... when the scratch it is given holds capacity_bytes (< 0: as much as it asks for): never more slabs than fit, 0 when not even one
+// does.  (A workspace slot holds B * 1 179 648 bytes and 9 B slabs of 12 544 C bytes fit it up to C = 10 and no further: DESIGN 26.)
+int stem_wgrad_bf16_slabs_cap(int B, int H, int W, int C, int64_t capacity_bytes) {
+    int slabs = stem_wgrad_bf16_slabs(B, H, W);
+    if (capacity_bytes >= 0 && C >= 1) {
+        const int64_t fit = capacity_bytes / ((int64_t)COUT * R * R * C * (int64_t)sizeof(float));
+        if (fit < slabs) slabs = (int)fit;
+    }
+    return slabs;
+}
+
+bool stem_conv_bf16_eligible(int H, int W, int C, int cout, int k, int stride, int pad) {
+    return cout == COUT && k == R && stride == 2 && pad == 3 && C >= 1 && R * C <= Row<2>::KROW - 1 && H % 2 == 0 && W % 32 == 0;
+}
+
+// the wide-row form: 64 <= 7 * C <= 95
+bool stem_conv_bf16_wide_eligible(int H, int W, int C, int cout, int k, int stride, int pad) {
+    return cout == COUT && k == R && stride == 2 && pad == 3 && R * C >= Row<2>::KROW && R * C <= Row<3>::KROW - 1 && H % 2 == 0 && W % 32 == 0;
+}
+
 namespace {
 
-template <typename XE>
-int stem_wgrad_bf16_impl(const char* family, const XE* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream) {
-    SIMQ_REQUIRE(stem_conv_bf16_eligible(H, W, C, COUT, R, 2, 3), "stem_wgrad_bf16: shape %dx%dx%d not covered", H, W, C);
-    SIMQ_REQUIRE(4.0 * B * H * W * C < 4294967000.0, "stem_wgrad_bf16: input too large");     // (elements: the kernels index them with 31 bits to spare)
+template <int KS> bool eligible_ks(int H, int W, int C) {
+    return KS == 2 ? stem_conv_bf16_eligible(H, W, C, COUT, R, 2, 3) : stem_conv_bf16_wide_eligible(H, W, C, COUT, R, 2, 3);
+}
+
+template <typename XE, int KS>
+int stem_wgrad_bf16_impl(const char* family, const XE* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                         int64_t partial_bytes) {
+    SIMQ_REQUIRE(eligible_ks<KS>(H, W, C), "%s: shape %dx%dx%d not covered", family, H, W, C);
+    SIMQ_REQUIRE(4.0 * B * H * W * C < 4294967000.0, "%s: input too large", family);     // (elements: the kernels index them with 31 bits to spare)
     StemWgradArgs<XE> p;
     p.x = x; p.dy = dy; p.partial = partial;
     p.B = B; p.H = H; p.W = W; p.C = C; p.Ho = H / 2; p.Wo = W / 2;
-    const int slabs = stem_wgrad_bf16_slabs(B, H, W);
+    // blocks are persistent over the chunks, so any slab count covers the batch: as many as the scratch holds, at most what the batch asks for
+    const int slabs = stem_wgrad_bf16_slabs_cap(B, H, W, C, partial_bytes);
+    SIMQ_REQUIRE(slabs >= 1, "%s: the partial-sum scratch holds %lld bytes, one slab of %d input channels takes %d", family, (long long)partial_bytes, C,
+                 COUT * R * R * C * (int)sizeof(float));
     note_launch(family);
-    hipLaunchKernelGGL(stem_wgrad_bf16_kernel<XE>, dim3(slabs), dim3(WG_WAVES * 64), 0, stream, p);
+    hipLaunchKernelGGL((stem_wgrad_bf16_kernel<XE, KS>), dim3(slabs), dim3(WG_WAVES * 64), 0, stream, p);
     SIMQ_CHECK_LAUNCH();
     const int n = COUT * R * R * C;
     hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((n + 63) / 64), dim3(256), 0, stream, partial, dw, n, slabs);
@@ -362,49 +460,63 @@ int stem_wgrad_bf16_impl(const char* family, const XE* x, const uint16_t* dy, fl
 
 }  // namespace
 
-// dy: bf16 [B][H/2][W/2][64];  dw: [64][7][7][C] fp32 (overwritten);  partial: stem_wgrad_bf16_slabs() * 64 * 49 * C floats
-int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_wgrad_bf16_impl<float>("stem_wgrad_bf16", x, dy, dw, partial, B, H, W, C, stream);
+// dy: bf16 [B][H/2][W/2][64];  dw: [64][7][7][C] fp32 (overwritten);  partial: stem_wgrad_bf16_slabs_cap(.., partial_bytes) * 64 * 49 * C floats
+int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream, int64_t partial_bytes) {
+    return stem_wgrad_bf16_impl<float, 2>("stem_wgrad_bf16", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
 }
 // ... over bf16 states: x is [B][H][W][C] bf16
-int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_wgrad_bf16_impl<uint16_t>("stem_wgrad_bf16_x16", x, dy, dw, partial, B, H, W, C, stream);
+int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                               int64_t partial_bytes) {
+    return stem_wgrad_bf16_impl<uint16_t, 2>("stem_wgrad_bf16_x16", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
+}
+// ... and the wide-row forms (64 <= 7 * C <= 95)
+int launch_stem_wgrad_bf16_wide(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                                int64_t partial_bytes) {
+    return stem_wgrad_bf16_impl<float, 3>("stem_wgrad_bf16_wide", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
+}
+int launch_stem_wgrad_bf16_wide_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                                    int64_t partial_bytes) {
+    return stem_wgrad_bf16_impl<uint16_t, 3>("stem_wgrad_bf16_wide_x16", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
 }
 
-int stem_conv_bf16_wbytes() { return COUT * WROW * 2; }
-
-bool stem_conv_bf16_eligible(int H, int W, int C, int cout, int k, int stride, int pad) {
-    return cout == COUT && k == R && stride == 2 && pad == 3 && C >= 1 && R * C <= KROW - 1 && H % 2 == 0 && W % 32 == 0;
-}
+int stem_conv_bf16_wbytes() { return COUT * Row<2>::WROW * 2; }
+int stem_conv_bf16_wide_wbytes() { return COUT * Row<3>::WROW * 2; }
 
 int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, hipStream_t stream) {
-    hipLaunchKernelGGL(stem_weight_prep_kernel, dim3(32), dim3(256), 0, stream, w, w16, C);
+    hipLaunchKernelGGL(stem_weight_prep_kernel<2>, dim3(32), dim3(256), 0, stream, w, w16, C);
+    SIMQ_CHECK_LAUNCH();
+    return 0;
+}
+int launch_stem_weight_prep_wide(const float* w, uint16_t* w16, int C, hipStream_t stream) {
+    hipLaunchKernelGGL(stem_weight_prep_kernel<3>, dim3(32), dim3(256), 0, stream, w, w16, C);
     SIMQ_CHECK_LAUNCH();
     return 0;
 }
 
 namespace {
 
-template <typename XE>
+template <typename XE, int KS>
 int stem_conv_bf16_impl(const char* family, const XE* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
-    SIMQ_REQUIRE(stem_conv_bf16_eligible(H, W, C, COUT, R, 2, 3), "stem_conv_bf16: shape %dx%dx%d not covered", H, W, C);
+    constexpr int NWAVE = Row<KS>::NWAVE;
+    SIMQ_REQUIRE(eligible_ks<KS>(H, W, C), "%s: shape %dx%dx%d not covered", family, H, W, C);
     const double xb = 4.0 * B * H * W * C;
-    SIMQ_REQUIRE(xb < 4294967000.0, "stem_conv_bf16: input exceeds the 4 GiB buffer-addressing limit");
+    SIMQ_REQUIRE(xb < 4294967000.0, "%s: input exceeds the 4 GiB buffer-addressing limit", family);
     StemArgs<XE> p;
     p.x = x; p.w16 = w16; p.y = y; p.stats = stats;
     p.B = B; p.H = H; p.W = W; p.C = C; p.Ho = H / 2; p.Wo = W / 2;
     p.x_bytes = (unsigned)(xb / 4.0 * sizeof(XE));
     const int ntiles = B * p.Ho * (p.Wo / 16);
     int blocks = (ntiles + NWAVE - 1) / NWAVE;
-    if (blocks > 512) blocks = 512;                                   // two persistent blocks per CU
+    const int max_blocks = 256 * Row<KS>::BLOCKS_PER_CU;              // persistent blocks: two per CU (narrow), one per CU (wide)
+    if (blocks > max_blocks) blocks = max_blocks;
     static bool attr_set = false;                                     // (one per instantiation)
-    const int smem = SMEM_W + NWAVE * COUT * 2 * (int)sizeof(double);
+    const int smem = Row<KS>::SMEM_W + NWAVE * COUT * 2 * (int)sizeof(double);
     if (!attr_set) {
-        SIMQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_conv_bf16_kernel<XE>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        SIMQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stem_conv_bf16_kernel<XE, KS>), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_set = true;
     }
     note_launch(family);
-    hipLaunchKernelGGL(stem_conv_bf16_kernel<XE>, dim3(blocks), dim3(NWAVE * 64), smem, stream, p);
+    hipLaunchKernelGGL((stem_conv_bf16_kernel<XE, KS>), dim3(blocks), dim3(NWAVE * 64), smem, stream, p);
     SIMQ_CHECK_LAUNCH();
     return 0;
 }
@@ -413,11 +525,18 @@ int stem_conv_bf16_impl(const char* family, const XE* x, const uint16_t* w16, ui
 
 // y: bf16 [B][H/2][W/2][64];  stats: NULL or [2 * 64] doubles (accumulated into)
 int launch_stem_conv_bf16(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_conv_bf16_impl<float>("stem_conv_bf16", x, w16, y, stats, B, H, W, C, stream);
+    return stem_conv_bf16_impl<float, 2>("stem_conv_bf16", x, w16, y, stats, B, H, W, C, stream);
 }
 // ... over bf16 states: x is [B][H][W][C] bf16
 int launch_stem_conv_bf16_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_conv_bf16_impl<uint16_t>("stem_conv_bf16_x16", x, w16, y, stats, B, H, W, C, stream);
+    return stem_conv_bf16_impl<uint16_t, 2>("stem_conv_bf16_x16", x, w16, y, stats, B, H, W, C, stream);
+}
+// ... and the wide-row forms (64 <= 7 * C <= 95; w16 in the layout of launch_stem_weight_prep_wide)
+int launch_stem_conv_bf16_wide(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
+    return stem_conv_bf16_impl<float, 3>("stem_conv_bf16_wide", x, w16, y, stats, B, H, W, C, stream);
+}
+int launch_stem_conv_bf16_wide_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
+    return stem_conv_bf16_impl<uint16_t, 3>("stem_conv_bf16_wide_x16", x, w16, y, stats, B, H, W, C, stream);
 }
 
 }  // namespace simq

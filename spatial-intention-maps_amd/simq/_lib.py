@@ -162,6 +162,12 @@ _SIGS = {
     'simq_conv2d_wgrad_stem_bf16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     'simq_conv2d_fwd_stem_bf16_x16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
     'simq_conv2d_wgrad_stem_bf16_x16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    'simq_conv2d_fwd_stem_bf16_wide_scratch_bytes': (c_int64, []),
+    'simq_conv2d_wgrad_stem_bf16_slabs': (c_int, [c_int, c_int, c_int, c_int, c_int64]),
+    'simq_conv2d_fwd_stem_bf16_wide': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    'simq_conv2d_wgrad_stem_bf16_wide': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    'simq_conv2d_fwd_stem_bf16_wide_x16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    'simq_conv2d_wgrad_stem_bf16_wide_x16': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     'simq_states_to_bf16': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'simq_states_to_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     'simq_forward_sync': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
