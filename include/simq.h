@@ -469,6 +469,58 @@ int simq_bce_with_logits(const float* d_logits, const float* d_target, int64_t n
 int simq_split_last_channel(const float* d_x, float* d_head, float* d_last, int64_t pixels, int channels, void* stream);
 int simq_sigmoid_concat(const float* d_state, const float* d_logit, float* d_out, float* d_prob, int64_t pixels, int channels, void* stream);
 
+/* ---- the same three over typed states: bf16 replay pools end to end --------------------------------------------------------
+ * Element types are flags: 0 fp32, 1 bf16.  fp32 arrays 4-byte, bf16 arrays 2-byte aligned; every array a call writes is disjoint from
+ * every other array of the call (checked).  1 <= pixels <= 2^30.  Where every array of a call is 16-byte aligned, whole tiles of 256
+ * pixels move as 16-byte vectors on both sides (256 * C elements are a whole number of them for every C); the last partial tile, and
+ * everything when some array is not 16-byte aligned or a tile exceeds 64 KB, moves element by element -- same values either way.
+ * simq_intention_split: d_state [pixels][channels] -> d_head [pixels][channels-1] and d_last [pixels] fp32 (may be NULL), 2 <= channels <=
+ *   4096.  Same type: bits are moved (NaN payloads kept); fp32 -> bf16: simq_states_to_bf16's conversion; bf16 -> fp32 (and d_last of a bf16
+ *   state): the exact widening.
+ * simq_bce_with_logits_state: simq_bce_with_logits with the target read IN PLACE from the last channel of d_state (d_state[p * channels +
+ *   channels - 1], a bf16 state widened exactly): the same terms and the same gradient expression, element for element.  The loss sum is
+ *   reproducible: per-block fp64 partial sums go to d_scratch (simq_bce_state_scratch_bytes() bytes, 8-byte aligned) and a second small
+ *   launch adds them in block order -- no atomics.
+ * simq_sigmoid_concat_x: simq_sigmoid_concat with the element types of d_state [pixels][channels] and d_out [pixels][channels+1] chosen
+ *   independently; a bf16 d_out receives the sigmoid rounded as simq_states_to_bf16 rounds (what the Q-network's first convolution would do
+ *   to the fp32 value); d_prob (may be NULL) stays fp32.  1 <= channels <= 4095. */
+int simq_intention_split(const void* d_state, int state_bf16, void* d_head, int head_bf16, float* d_last, int64_t pixels, int channels, void* stream);
+int64_t simq_bce_state_scratch_bytes(void);
+int simq_bce_with_logits_state(const float* d_logits, const void* d_state, int state_bf16, int64_t pixels, int channels, float* d_dlogits,
+                               double* d_loss_sum, void* d_scratch, void* stream);
+int simq_sigmoid_concat_x(const void* d_state, int state_bf16, const float* d_logit, void* d_out, int out_bf16, float* d_prob, int64_t pixels,
+                          int channels, void* stream);
+
+/* ---- the whole intention supervision step in one call (reference train.train_intention, train.py:143-158, lines 145-153) ----------------
+ * On `stream`, sequenced by the library as simq_train_step is: simq_intention_split of `state` into `head` (in the element type the plan
+ * reads: bf16 with simq_plan_options.bf16_states, else fp32; a bf16 `state` for a plan without the option is widened by the split) and,
+ * when `target` is given, the ground-truth map into it; train-mode forward that convolves `head` in place (no copy into the workspace);
+ * simq_bce_with_logits_state on `state`; copy of *loss_sum to loss_host; backward from the dense `dlogits` with `head` as the first
+ * convolution's input, weight gradients on `side_stream` when one is given; momentum SGD without clipping; refresh of the weight cache.
+ * The plan has one output channel and channels - 1 input channels; 1 <= batch <= 4096; the weight cache must be current on entry.
+ * `state` and `head` are read until the END of the call's stream work.  *loss_sum is the SUM of the batch * 96 * 96 terms (the host divides).
+ * There is no `comm` field: data-parallel intention steps keep the separate calls (simq.learner.train_intention_step without `fused`). */
+typedef struct simq_intention_args {
+    const simq_plan* plan;
+    int struct_bytes;            /* sizeof(simq_intention_args) of the caller's header: checked, a struct of another version is refused */
+    int batch, channels;         /* channels: of `state` (the plan reads channels - 1) */
+    int state_bf16;              /* element type of `state`: 0 fp32, 1 bf16 */
+    int first_step;              /* 1: the momentum buffer is initialised by this step */
+    float lr, momentum, weight_decay;
+    float* params; void* wcache; float* bnbuf; float* grads; float* momentum_buf; void* ws_train;
+    const void* state;           /* [batch][96][96][channels] */
+    void* head;                  /* [batch][96][96][channels-1] in the plan's state type: written, then convolved in place */
+    float* logits; float* dlogits;   /* [batch][96][96] */
+    float* target;               /* NULL, or [batch][96][96] fp32: receives the ground-truth map (the last channel of `state`) */
+    double* loss_sum; void* bce_scratch;   /* one double; simq_bce_state_scratch_bytes() bytes */
+    void* opt_scratch; float* total_norm;  /* as simq_train_args (total_norm may be NULL) */
+    double* loss_host;           /* NULL, or one double of PINNED host memory: *loss_sum is copied there on the plan's copy stream right behind
+                                  * the BCE launch; the host calls simq_train_loss_wait(plan) instead of synchronising the stream.  The wait is
+                                  * per plan: an intention net has its own, a TD step's pending copy is not disturbed. */
+    void* stream; void* side_stream;
+} simq_intention_args;
+int simq_train_intention_step(const simq_intention_args* a);
+
 /* layout helpers for callers that hold NCHW tensors (apply_transform, policies.py:44-45) */
 int simq_nchw_to_nhwc(const float* d_in, float* d_out, int batch, int channels, int hw, void* stream);
 int simq_nhwc_to_nchw(const float* d_in, float* d_out, int batch, int channels, int hw, void* stream);

@@ -323,6 +323,14 @@ int launch_clip_sgd(float* p, float* g, float* m, int64_t count, float max_norm,
 int launch_bce_logits(const float* x, const float* t, int64_t n, float* dx, double* loss_sum, hipStream_t stream);
 int launch_split_last_channel(const float* x, float* head, float* last, int64_t pixels, int C, hipStream_t stream);
 int launch_sigmoid_concat(const float* state, const float* logit, float* out, float* prob, int64_t pixels, int Cs, hipStream_t stream);
+// intention.hip: the same three over typed states (state_bf16 / head_bf16 / out_bf16: 0 fp32, 1 bf16); bce_state reads its target from the
+// last channel of `state` in place and sums the loss through `scratch` (bce_state_scratch_bytes()) without atomics
+int launch_intention_split(const void* state, int state_bf16, void* head, int head_bf16, float* last, int64_t pixels, int C, hipStream_t stream);
+int launch_sigmoid_concat_x(const void* state, int state_bf16, const float* logit, void* out, int out_bf16, float* prob, int64_t pixels, int Cs,
+                            hipStream_t stream);
+int launch_bce_state(const float* x, const void* state, int state_bf16, int64_t n, int C, float* dx, double* loss_sum, void* scratch,
+                     hipStream_t stream);
+int64_t bce_state_scratch_bytes();
 int launch_replay_gather(const float* ring, int64_t item_floats, const int64_t* index, int count, float* out,
                          hipStream_t stream);
 int launch_replay_scatter(const float* src, int64_t item_floats, const int64_t* slots, int count, float* pool, int64_t pool_slots,

@@ -64,6 +64,67 @@ int simq_sigmoid_concat(const float* d_state, const float* d_logit, float* d_out
     return launch_sigmoid_concat(d_state, d_logit, d_out, d_prob, pixels, channels, static_cast<hipStream_t>(stream));
 }
 
+// ---- the same three over typed states (intention.hip) ----
+#define SIMQ_TYPE_FLAG(name, v) SIMQ_REQUIRE((v) == 0 || (v) == 1, name ": element type %d (0 fp32, 1 bf16)", (v))
+
+int simq_intention_split(const void* d_state, int state_bf16, void* d_head, int head_bf16, float* d_last, int64_t pixels, int channels, void* stream) {
+    SIMQ_REQUIRE(d_state && d_head, "intention_split: NULL pointer");
+    SIMQ_TYPE_FLAG("intention_split", state_bf16);
+    SIMQ_TYPE_FLAG("intention_split", head_bf16);
+    SIMQ_REQUIRE(channels >= 2 && channels <= 4096, "intention_split: channels = %d (2 .. 4096: a head of at least one channel)", channels);
+    SIMQ_REQUIRE(pixels >= 1 && pixels <= ((int64_t)1 << 30), "intention_split: pixels = %lld (1 .. 2^30)", (long long)pixels);
+    const int64_t sb = state_bf16 ? 2 : 4, hb = head_bf16 ? 2 : 4;
+    SIMQ_REQUIRE(((uintptr_t)d_state & (sb - 1)) == 0 && ((uintptr_t)d_head & (hb - 1)) == 0 && ((uintptr_t)d_last & 3) == 0,
+                 "intention_split: fp32 arrays must be 4-byte, bf16 arrays 2-byte aligned");
+    const int64_t ns = pixels * channels * sb, nh = pixels * (channels - 1) * hb, nl = d_last ? pixels * 4 : 0;
+    SIMQ_REQUIRE(!simq::overlaps(d_state, ns, d_head, nh), "intention_split: d_head overlaps d_state");
+    SIMQ_REQUIRE(!d_last || (!simq::overlaps(d_state, ns, d_last, nl) && !simq::overlaps(d_head, nh, d_last, nl)),
+                 "intention_split: d_last overlaps d_state or d_head");
+    return launch_intention_split(d_state, state_bf16, d_head, head_bf16, d_last, pixels, channels, static_cast<hipStream_t>(stream));
+}
+
+int64_t simq_bce_state_scratch_bytes(void) { return bce_state_scratch_bytes(); }
+
+int simq_bce_with_logits_state(const float* d_logits, const void* d_state, int state_bf16, int64_t pixels, int channels, float* d_dlogits,
+                               double* d_loss_sum, void* d_scratch, void* stream) {
+    SIMQ_REQUIRE(d_logits && d_state && d_loss_sum && d_scratch, "bce_with_logits_state: NULL pointer");
+    SIMQ_TYPE_FLAG("bce_with_logits_state", state_bf16);
+    SIMQ_REQUIRE(channels >= 1 && channels <= 4096, "bce_with_logits_state: channels = %d (1 .. 4096)", channels);
+    SIMQ_REQUIRE(pixels >= 1 && pixels <= ((int64_t)1 << 30), "bce_with_logits_state: pixels = %lld (1 .. 2^30)", (long long)pixels);
+    const int64_t sb = state_bf16 ? 2 : 4;
+    SIMQ_REQUIRE(((uintptr_t)d_state & (sb - 1)) == 0 && ((uintptr_t)d_logits & 3) == 0 && ((uintptr_t)d_dlogits & 3) == 0 &&
+                 ((uintptr_t)d_loss_sum & 7) == 0 && ((uintptr_t)d_scratch & 7) == 0,
+                 "bce_with_logits_state: fp32 arrays must be 4-byte, bf16 arrays 2-byte, d_loss_sum and d_scratch 8-byte aligned");
+    const int64_t ns = pixels * channels * sb, nx = pixels * 4, nscr = bce_state_scratch_bytes();
+    SIMQ_REQUIRE(!d_dlogits || (!simq::overlaps(d_state, ns, d_dlogits, nx) && !simq::overlaps(d_logits, nx, d_dlogits, nx)),
+                 "bce_with_logits_state: d_dlogits overlaps d_state or d_logits");
+    for (const void* w : {(const void*)d_loss_sum, (const void*)d_scratch}) {
+        const int64_t nw = w == d_scratch ? nscr : 8;
+        SIMQ_REQUIRE(!simq::overlaps(d_state, ns, w, nw) && !simq::overlaps(d_logits, nx, w, nw) && (!d_dlogits || !simq::overlaps(d_dlogits, nx, w, nw)),
+                     "bce_with_logits_state: d_loss_sum / d_scratch overlaps an array");
+    }
+    SIMQ_REQUIRE(!simq::overlaps(d_loss_sum, 8, d_scratch, nscr), "bce_with_logits_state: d_loss_sum overlaps d_scratch");
+    return launch_bce_state(d_logits, d_state, state_bf16, pixels, channels, d_dlogits, d_loss_sum, d_scratch, static_cast<hipStream_t>(stream));
+}
+
+int simq_sigmoid_concat_x(const void* d_state, int state_bf16, const float* d_logit, void* d_out, int out_bf16, float* d_prob, int64_t pixels,
+                          int channels, void* stream) {
+    SIMQ_REQUIRE(d_state && d_logit && d_out, "sigmoid_concat_x: NULL pointer");
+    SIMQ_TYPE_FLAG("sigmoid_concat_x", state_bf16);
+    SIMQ_TYPE_FLAG("sigmoid_concat_x", out_bf16);
+    SIMQ_REQUIRE(channels >= 1 && channels <= 4095, "sigmoid_concat_x: channels = %d (1 .. 4095 state channels)", channels);
+    SIMQ_REQUIRE(pixels >= 1 && pixels <= ((int64_t)1 << 30), "sigmoid_concat_x: pixels = %lld (1 .. 2^30)", (long long)pixels);
+    const int64_t sb = state_bf16 ? 2 : 4, ob = out_bf16 ? 2 : 4;
+    SIMQ_REQUIRE(((uintptr_t)d_state & (sb - 1)) == 0 && ((uintptr_t)d_out & (ob - 1)) == 0 && ((uintptr_t)d_logit & 3) == 0 && ((uintptr_t)d_prob & 3) == 0,
+                 "sigmoid_concat_x: fp32 arrays must be 4-byte, bf16 arrays 2-byte aligned");
+    const int64_t ns = pixels * channels * sb, no = pixels * (channels + 1) * ob, nx = pixels * 4;
+    SIMQ_REQUIRE(!simq::overlaps(d_state, ns, d_out, no) && !simq::overlaps(d_logit, nx, d_out, no), "sigmoid_concat_x: d_out overlaps d_state or d_logit");
+    SIMQ_REQUIRE(!d_prob || (!simq::overlaps(d_state, ns, d_prob, nx) && !simq::overlaps(d_logit, nx, d_prob, nx) && !simq::overlaps(d_out, no, d_prob, nx)),
+                 "sigmoid_concat_x: d_prob overlaps another array");
+    return launch_sigmoid_concat_x(d_state, state_bf16, d_logit, d_out, out_bf16, d_prob, pixels, channels, static_cast<hipStream_t>(stream));
+}
+#undef SIMQ_TYPE_FLAG
+
 int simq_replay_gather(const float* d_ring, int64_t item_floats, const int64_t* d_index, int count, float* d_out, void* stream) {
     return launch_replay_gather(d_ring, item_floats, d_index, count, d_out, static_cast<hipStream_t>(stream));
 }

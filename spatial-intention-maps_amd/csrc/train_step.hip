@@ -1,5 +1,6 @@
 // libsimq: the whole TD step of train.py:108-141 as one library call (simq_train_step) -- three forwards, TD target + Huber loss,
-// backward (with the two gradient all-reduces of the data-parallel form), clip + SGD, weight-cache refresh.
+// backward (with the two gradient all-reduces of the data-parallel form), clip + SGD, weight-cache refresh.  And the intention
+// supervision step of train.py:143-158 the same way (simq_train_intention_step).
 #include "plan.h"
 
 using namespace simq;
@@ -9,7 +10,8 @@ namespace {
 // copy_on: a stream of the CALLER's to run the copy on instead of the plan's copy stream -- simq_train_step hands over the third stream when
 // the caller named one: it is idle from the end of the forward phase to the next step, and the caller has TESTED that it does not share the
 // launch stream's hardware queue (simq_train_args.third_stream), which nobody can say of a stream the library creates
-int loss_copy(const simq_plan* plan, const float* d_out4, float* h_out4, hipStream_t producer, bool own_stream, hipStream_t copy_on = nullptr) {
+// bytes: 4 floats of simq_train_step's out4, one double of simq_train_intention_step's loss sum
+int loss_copy(const simq_plan* plan, const void* d_out4, void* h_out4, size_t bytes, hipStream_t producer, bool own_stream, hipStream_t copy_on = nullptr) {
     PlanStreams* c = nullptr;
     int dev = 0;
     RC(plan_streams(plan, &c, &dev));
@@ -34,7 +36,7 @@ int loss_copy(const simq_plan* plan, const float* d_out4, float* h_out4, hipStre
         SIMQ_CHECK_HIP(hipEventRecord(c->copy_ready, producer));
         SIMQ_CHECK_HIP(hipStreamWaitEvent(s, c->copy_ready, 0));
     }
-    SIMQ_CHECK_HIP(hipMemcpyAsync(h_out4, d_out4, 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    SIMQ_CHECK_HIP(hipMemcpyAsync(h_out4, d_out4, bytes, hipMemcpyDeviceToHost, s));
     SIMQ_CHECK_HIP(hipEventRecord(c->copy_done, s));
     c->copy_pending = true;
     return 0;
@@ -179,7 +181,7 @@ int simq_train_step(const simq_train_args* a) {
     RC(launch_td_huber(a->q, B, n, a->action, a->reward, a->nsv, a->gamma, 1.0f / (float)a->global_batch, a->q_sa, a->y, a->td,
                        a->out4, a->dq, main));                                                                       // train.py:115,126-129
     if (a->loss_host && !a->comm)                                                          // train.py:137-139: the loss is final here
-        RC(loss_copy(p, a->out4, a->loss_host, main, true, (three && a->third_stream) ? static_cast<hipStream_t>(a->third_stream) : nullptr));
+        RC(loss_copy(p, a->out4, a->loss_host, 4 * sizeof(float), main, true, (three && a->third_stream) ? static_cast<hipStream_t>(a->third_stream) : nullptr));
     if (a->comm) {
         // data parallel: the four loss sums are summed over the ranks HERE, not behind the last gradient bucket, and copied to the host on the
         // communicator's stream right behind that all-reduce -- a caller that waits for the loss (simq_train_loss_wait) gets it when the forwards
@@ -187,7 +189,7 @@ int simq_train_step(const simq_train_args* a) {
         // 1-rank communicator on one GPU (profiles/r06_ab_early_target_delay_dp.txt): with the loss behind bucket 2 the host stood still for the
         // whole backward pass and the data-parallel form was 6.5 % slower than the plain step.
         RC(comm_allreduce(a->comm, a->out4, 4, SIMQ_COMM_F32, main));
-        if (a->loss_host) RC(loss_copy(p, a->out4, a->loss_host, comm_stream(a->comm), false));
+        if (a->loss_host) RC(loss_copy(p, a->out4, a->loss_host, 4 * sizeof(float), comm_stream(a->comm), false));
     }
     const float gscale = 1.0f / (float)a->global_batch;
     auto backward = [&](int phase) {                                                                                 // train.py:131-132
@@ -213,6 +215,46 @@ int simq_train_step(const simq_train_args* a) {
     if (ps) ps->late_recorded = late_block >= 0;
     RC(launch_clip_sgd(a->params, a->grads, a->momentum_buf, p->nparams, a->max_norm, a->lr, a->momentum, a->weight_decay,
                        a->first_step, a->opt_scratch, a->total_norm, main));                                         // train.py:133-135
+    return simq_weights_prepare(p, a->params, a->wcache, main);
+}
+
+// The intention supervision step of train.py:145-153 on the caller's stream: split, train-mode forward on the head in place, BCE against the
+// last state channel, loss copy, backward from the dense dlogits, momentum SGD without clipping, weight-cache refresh.
+int simq_train_intention_step(const simq_intention_args* a) {
+    SIMQ_REQUIRE(a && a->plan, "train_intention_step: NULL argument");
+    SIMQ_REQUIRE(a->struct_bytes == (int)sizeof(simq_intention_args), "train_intention_step: simq_intention_args.struct_bytes = %d, this library's "
+                 "struct has %d bytes", a->struct_bytes, (int)sizeof(simq_intention_args));
+    SIMQ_REQUIRE(a->params && a->wcache && a->bnbuf && a->grads && a->momentum_buf && a->ws_train && a->state && a->head && a->logits && a->dlogits &&
+                 a->loss_sum && a->bce_scratch && a->opt_scratch, "train_intention_step: NULL buffer");
+    const simq_plan* p = a->plan;
+    SIMQ_REQUIRE(a->state_bf16 == 0 || a->state_bf16 == 1, "train_intention_step: state_bf16 = %d (0 fp32, 1 bf16)", a->state_bf16);
+    SIMQ_REQUIRE(a->channels >= 2 && p->cout == 1 && p->cin == a->channels - 1, "train_intention_step: states of %d channels need a plan with %d "
+                 "input channels and one output channel (this plan: %d in, %d out)", a->channels, a->channels - 1, p->cin, p->cout);
+    SIMQ_REQUIRE(a->batch >= 1 && a->batch <= 4096, "train_intention_step: batch=%d out of range (1 .. 4096)", a->batch);
+    hipStream_t main = static_cast<hipStream_t>(a->stream), side = static_cast<hipStream_t>(a->side_stream);
+    const int B = a->batch, head_bf16 = p->opt.bf16_states ? 1 : 0;
+    const int64_t pixels = (int64_t)B * 96 * 96;
+    hipEvent_t ev_wfork = nullptr, ev_wjoin = nullptr, ev_wdone0 = nullptr, ev_wdone1 = nullptr;
+    if (side) {          // the fork / join events of the weight gradients beside the backward walk: the plan's, as in simq_train_step
+        PlanStreams* ps = nullptr;
+        int dev = 0;
+        RC(plan_streams(p, &ps, &dev));
+        SIMQ_REQUIRE(ps, "train_intention_step: device index %d out of range", dev);
+        if (!ps->step_ev[0]) {
+            std::lock_guard<std::mutex> lk(p->mu);
+            for (int i = 0; i < 7; ++i) SIMQ_CHECK_HIP(hipEventCreateWithFlags(&ps->step_ev[i], hipEventDisableTiming));
+        }
+        ev_wfork = ps->step_ev[2]; ev_wjoin = ps->step_ev[3]; ev_wdone0 = ps->step_ev[4]; ev_wdone1 = ps->step_ev[5];
+    }
+    RC(simq_intention_split(a->state, a->state_bf16, a->head, head_bf16, a->target, pixels, a->channels, main));              // train.py:145-146
+    const float* head = static_cast<const float*>(a->head);
+    RC(forward_sync_inplace(p, B, a->params, a->wcache, a->bnbuf, head, a->logits, a->ws_train, main, nullptr));               // train.py:148
+    RC(simq_bce_with_logits_state(a->logits, a->state, a->state_bf16, pixels, a->channels, a->dlogits, a->loss_sum, a->bce_scratch, main));   // :149-150
+    if (a->loss_host) RC(loss_copy(p, a->loss_sum, a->loss_host, sizeof(double), main, true));                                // train.py:155 (.item())
+    RC(backward_sync_side(p, B, a->params, a->wcache, a->dlogits, nullptr, nullptr, nullptr, 1.f, a->grads, a->ws_train, 0, main, nullptr, side,
+                          ev_wfork, ev_wjoin, ev_wdone0, ev_wdone1, head));                                                    // train.py:151-152
+    RC(launch_clip_sgd(a->params, a->grads, a->momentum_buf, p->nparams, 0.f, a->lr, a->momentum, a->weight_decay, a->first_step, a->opt_scratch,
+                       a->total_norm, main));                                                                                  // train.py:153
     return simq_weights_prepare(p, a->params, a->wcache, main);
 }
 

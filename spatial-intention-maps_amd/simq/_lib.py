@@ -84,6 +84,14 @@ class TrainArgs(ctypes.Structure):
                     'opt_scratch', 'total_norm', 'stream', 'side_stream')] + [('global_nonfinal', c_int), ('struct_bytes', c_int), ('comm', c_void_p), ('loss_host', c_void_p), ('target_stream', c_void_p), ('third_stream', c_void_p)]
 
 
+class IntentionArgs(ctypes.Structure):
+    """simq_intention_args of include/simq.h (the whole intention supervision step in one library call)."""
+    _fields_ = [('plan', c_void_p), ('struct_bytes', c_int), ('batch', c_int), ('channels', c_int), ('state_bf16', c_int), ('first_step', c_int),
+                ('lr', c_float), ('momentum', c_float), ('weight_decay', c_float)] + [(n, c_void_p) for n in (
+                    'params', 'wcache', 'bnbuf', 'grads', 'momentum_buf', 'ws_train', 'state', 'head', 'logits', 'dlogits', 'target',
+                    'loss_sum', 'bce_scratch', 'opt_scratch', 'total_norm', 'loss_host', 'stream', 'side_stream')]
+
+
 _SIGS = {
     'simq_version': (c_int, []),
     'simq_build_flags': (c_int, []),
@@ -129,6 +137,11 @@ _SIGS = {
     'simq_bce_with_logits': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     'simq_split_last_channel': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'simq_sigmoid_concat': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    'simq_intention_split': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    'simq_bce_state_scratch_bytes': (c_int64, []),
+    'simq_bce_with_logits_state': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'simq_sigmoid_concat_x': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    'simq_train_intention_step': (c_int, [c_void_p]),
     'simq_replay_gather': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     'simq_replay_scatter': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_nchw_to_nhwc': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import arch, dist as sdist
-from ._lib import MODE_EVAL, MODE_TRAIN, MODE_TRAIN_NOGRAD, SimqError, TrainArgs, lib, ptr, stream_ptr
+from ._lib import MODE_EVAL, MODE_TRAIN, MODE_TRAIN_NOGRAD, IntentionArgs, SimqError, TrainArgs, lib, ptr, stream_ptr
 from .fcn import FCN
 from .tracker import TransitionTracker  # noqa: F401  (train.py:47-68; lives in its own torch-free module for the collector workers)
 
@@ -1404,11 +1404,23 @@ def train(cfg, policy_net, target_net, optimizer, batch, transform_fn, discount_
 
 
 def train_intention_step(intention_net, batch, lr, momentum, weight_decay, opt_state=None, process_group=None,
-                         global_batch=None, sync=True, comm=None, _on_launch_stream=False):
+                         global_batch=None, sync=True, comm=None, _on_launch_stream=False, fused=None, keep_target=False):
     """One intention-map supervision step (train.py:143-158) on the device: split the ground-truth map (last state
     channel) off the replay states, train-mode forward of FCN(C-1, 1), BCE-with-logits + its gradient in one kernel,
     backward, momentum SGD (no clipping on this path).  Returns {'loss_intention': float} or, with sync=False, the
-    device double holding the summed loss."""
+    device double holding the summed loss.
+
+    fused: None -- getattr(intention_net, 'fused_step', False).  False: the separate calls below, sequenced here (a bf16 DeviceBatch is
+    widened first).  True: the whole step is ONE library call (simq_train_intention_step) that takes an fp32 or bf16 batch as it is --
+    one typed split into the element type the net's plan reads, the target read in place from the batch -- and the loss comes back through
+    pinned memory (simq_train_loss_wait) instead of an .item() behind backward + SGD: sync='defer' returns a PendingIntentionStep whose
+    result() waits for that copy only.  Single process only: `process_group` / `comm` are refused.  keep_target (fused): the ground-truth
+    map is also written out and kept in intention_net._last['target'], as the separate calls always do."""
+    if fused is None:
+        fused = bool(getattr(intention_net, 'fused_step', False))
+    if fused and (process_group is not None or comm is not None):
+        raise SimqError('train_intention: the fused step (simq_train_intention_step) is single-process: it takes no process_group / comm -- '
+                        'data-parallel intention steps run with fused=False')
     if not isinstance(intention_net, FCN):
         raise SimqError('simq.train_intention needs a simq.FCN network (got %s); there is no torch fallback'
                         % type(intention_net).__name__)
@@ -1423,11 +1435,12 @@ def train_intention_step(intention_net, batch, lr, momentum, weight_decay, opt_s
         if isinstance(batch, DeviceBatch):
             batch.state.record_stream(ls.launch)
         with torch.cuda.stream(ls.launch):
-            return train_intention_step(intention_net, batch, lr, momentum, weight_decay, opt_state, process_group, global_batch, sync, comm, True)
+            return train_intention_step(intention_net, batch, lr, momentum, weight_decay, opt_state, process_group, global_batch, sync, comm, True,
+                                        fused, keep_target)
     intention_net._order_behind_last_step()
     if isinstance(batch, DeviceBatch):
         full = batch.state
-        if full.dtype == torch.bfloat16:     # a ring of bf16 states: the BCE target (the last channel) and the split are fp32 arithmetic, so the
+        if full.dtype == torch.bfloat16 and not fused:     # a ring of bf16 states: the BCE target (the last channel) and the split are fp32 arithmetic, so the
             from .fcn import to_f32          # batch is widened exactly first -- the step is the fp32 step on the rounded states
             full = to_f32(full.contiguous())
     else:
@@ -1439,6 +1452,8 @@ def train_intention_step(intention_net, batch, lr, momentum, weight_decay, opt_s
     gB = B if global_batch is None else int(global_batch)
     st = stream_ptr(dev)
     st_opt = opt_state if opt_state is not None else _opt_state(intention_net, None)
+    if fused:
+        return _train_intention_step_fused(intention_net, full, lr, momentum, weight_decay, st_opt, sync, ls, keep_target)
     x = torch.empty((B, W, W, C - 1), dtype=torch.float32, device=dev)
     target = torch.empty((B, W, W), dtype=torch.float32, device=dev)
     lib.call('simq_split_last_channel', ptr(full), ptr(x), ptr(target), B * W * W, C, st)          # train.py:145-146
@@ -1474,6 +1489,80 @@ def train_intention_step(intention_net, batch, lr, momentum, weight_decay, opt_s
     if sync == 'defer':
         return _PendingIntention(loss_sum, gB, torch.cuda.current_stream(dev))
     return {'loss_intention': float(loss_sum.item()) / (gB * W * W)}                                  # train.py:155-156
+
+
+def _train_intention_step_fused(net, full, lr, momentum, weight_decay, st_opt, sync, ls, keep_target):
+    """train_intention_step through simq_train_intention_step: split, forward, BCE, loss copy, backward, SGD and the weight-cache refresh
+    sequenced inside the library on the current stream (weight gradients on the learner's side stream)."""
+    dev = net.device_
+    B, C = full.shape[0], full.shape[3]
+    if full.dtype not in (torch.float32, torch.bfloat16) or not full.is_contiguous() or tuple(full.shape[1:3]) != (W, W) or full.device != net.flat_params.device:
+        raise SimqError('train_intention: states must be contiguous fp32 or bf16 [B,%d,%d,C] (NHWC) on %s, got %s %s'
+                        % (W, W, dev, full.dtype, tuple(full.shape)))
+    if not 1 <= B <= 4096:
+        raise SimqError('train_intention: batch of %d transitions (1 .. 4096)' % B)
+    net._ensure_weights()
+    main = torch.cuda.current_stream(dev)
+    ls.bind(main)
+    f32 = dict(dtype=torch.float32, device=dev)
+    head = torch.empty((B, W, W, C - 1), dtype=net.state_dtype, device=dev)
+    logits, dlogits = torch.empty((B, 1, W, W), **f32), torch.empty((B, 1, W, W), **f32)
+    target = torch.empty((B, W, W), **f32) if keep_target else None
+    loss_sum = torch.empty(1, dtype=torch.float64, device=dev)
+    scratch = getattr(net, '_bce_scratch', None)
+    if scratch is None:
+        scratch = net._bce_scratch = torch.empty(int(lib.c.simq_bce_state_scratch_bytes()), dtype=torch.uint8, device=dev)
+    a = IntentionArgs()
+    a.struct_bytes = ctypes.sizeof(IntentionArgs)
+    a.plan = net.plan.handle
+    a.batch, a.channels, a.state_bf16 = B, C, int(full.dtype == torch.bfloat16)
+    a.first_step = 0 if st_opt.initialised else 1
+    a.lr, a.momentum, a.weight_decay = lr, momentum, weight_decay
+    tensors = dict(params=net.flat_params, wcache=net.wcache, bnbuf=net.bn_buffers, grads=net.flat_grads, momentum_buf=st_opt.momentum,
+                   ws_train=net._workspace('train', B), state=full, head=head, logits=logits, dlogits=dlogits, target=target,
+                   loss_sum=loss_sum, bce_scratch=scratch, opt_scratch=st_opt.scratch, total_norm=st_opt.total_norm)
+    for k, t in tensors.items():
+        setattr(a, k, None if t is None else t.data_ptr())
+    a.stream, a.side_stream = main.cuda_stream, ls.side.cuda_stream
+    loss_host = None
+    if sync:
+        # train.py:155 (loss.item()) without synchronising the stream: see _train_step_fused
+        loss_host = getattr(net, '_loss_host64', None)
+        if loss_host is None:
+            loss_host = net._loss_host64 = torch.empty(1, dtype=torch.float64).pin_memory()
+        a.loss_host = loss_host.data_ptr()
+    lib.call('simq_train_intention_step', ctypes.byref(a))
+    # bookkeeping the separate calls do on the Python side
+    net._train_generation += 1
+    for k in net.num_batches_tracked:
+        net.num_batches_tracked[k] += 1
+    net.weights_dirty = False                 # the library refreshed the weight cache behind the SGD update
+    net._weights_stamp += 1
+    st_opt.initialised = True
+    net._last = {'logits': logits, 'head': head, 'loss_sum': loss_sum}
+    if keep_target:
+        net._last['target'] = target
+    net._train_input_inplace = True           # the head was convolved in place: the workspace holds no copy of it (FCN._backward_* refuse)
+    net._mark_step(main)
+    if not sync:
+        return loss_sum
+    pending = PendingIntentionStep(net.plan, loss_host, B)
+    return pending if sync == 'defer' else pending.result()
+
+
+class PendingIntentionStep:
+    """What the fused train_intention_step(sync='defer') returns: result() waits for the copy of the loss sum (issued right behind the BCE
+    launch) and returns train_intention()'s dict."""
+    __slots__ = ('_plan', '_host', '_gB', '_info')
+
+    def __init__(self, plan, host, gB):
+        self._plan, self._host, self._gB, self._info = plan, host, gB, None
+
+    def result(self):
+        if self._info is None:
+            lib.call('simq_train_loss_wait', self._plan.handle)
+            self._info = {'loss_intention': float(self._host.item()) / (self._gB * W * W)}          # train.py:155-156
+        return self._info
 
 
 class _PendingIntention:

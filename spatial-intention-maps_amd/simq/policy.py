@@ -13,7 +13,7 @@ import torch
 
 from . import arch
 from ._lib import SimqError, lib, ptr, stream_ptr
-from .fcn import FCN, is_handle, states_batch
+from .fcn import FCN, is_handle, states_as, states_batch
 
 
 class DQNPolicy:
@@ -141,15 +141,53 @@ class DQNIntentionPolicy(DQNPolicy):
             print("=> loaded intention network '{}'".format(self.cfg.policy_path))
 
     def build_intention_nets(self):                                                         # policies.py:89-95
-        return [FCN(num_input_channels=self.cfg.num_input_channels - 1, num_output_channels=1, device=self.device,
-                    precision=getattr(self.cfg, 'simq_precision', 'fp32')) for _ in range(self.num_robot_groups)]
+        # cfg.simq_intention_plan_options: simq_plan_options overrides of the intention nets ({'bf16_states': 1} on bf16 replay pools);
+        # cfg.simq_intention_fused: simq.train_intention runs their supervision step as one library call (simq_train_intention_step)
+        nets = [FCN(num_input_channels=self.cfg.num_input_channels - 1, num_output_channels=1, device=self.device,
+                    precision=getattr(self.cfg, 'simq_precision', 'fp32'),
+                    options=getattr(self.cfg, 'simq_intention_plan_options', None)) for _ in range(self.num_robot_groups)]
+        for net in nets:
+            net.fused_step = bool(getattr(self.cfg, 'simq_intention_fused', False))
+        return nets
+
+    def _typed(self, i, states):
+        """Whether group i's states take the typed path: some state is bf16 (a handle of a bf16 pool, a bfloat16 tensor), or the
+        intention net or the Q-network reads bf16 states.  Then nothing is widened to fp32 on the way: the batch is gathered in the pool's
+        type, loses its ground-truth channel in one simq_intention_split into the intention net's type, and one simq_sigmoid_concat_x
+        writes state + predicted map in the Q-network's type.  fp32 states and fp32 nets: the calls this class always made."""
+        bf = torch.bfloat16
+        return (self.intention_nets[i].state_dtype == bf or self.policy_nets[i].state_dtype == bf
+                or any((is_handle(s) and s.pool.dtype == bf) or (torch.is_tensor(s) and s.dtype == bf) for s in states))
+
+    def _typed_input(self, i, xs, drop_last):
+        """Typed path: the states xs as one batch [n,96,96,C or C-1] in the intention net's type (drop_last: without the ground-truth map)."""
+        net = self.intention_nets[i]
+        x = xs[0] if len(xs) == 1 and torch.is_tensor(xs[0]) else states_batch(xs, self.device)
+        if not drop_last:
+            return states_as(x.contiguous(), net.state_dtype)
+        n, W, C = x.shape[0], arch.STATE_WIDTH, x.shape[3]
+        head = torch.empty((n, W, W, C - 1), dtype=net.state_dtype, device=self.device)
+        lib.call('simq_intention_split', ptr(x.contiguous()), int(x.dtype == torch.bfloat16), ptr(head), int(head.dtype == torch.bfloat16), None,
+                 n * W * W, C, stream_ptr(self.device))
+        return head
+
+    def _concat(self, i, x, logit, prob=None):
+        """Typed path: concat(x, sigmoid(logit)) in the Q-network's type."""
+        n, W, C = x.shape[0], arch.STATE_WIDTH, x.shape[3]
+        out = torch.empty((n, W, W, C + 1), dtype=self.policy_nets[i].state_dtype, device=self.device)
+        lib.call('simq_sigmoid_concat_x', ptr(x), int(x.dtype == torch.bfloat16), ptr(logit), ptr(out), int(out.dtype == torch.bfloat16), ptr(prob),
+                 n * W * W, C, stream_ptr(self.device))
+        return out
 
     def _predict(self, i, s):
         """One HWC state [96,96,C-1] (ndarray, replay pool handle, or a device tensor [1,96,96,C-1]) -> device tensors
         (state_with_intention [1,96,96,C], sigmoid map [96,96])."""
         net = self.intention_nets[i]
-        # (fp32 arithmetic on the state itself -- sigmoid_concat: a handle of a bf16 pool is widened exactly first, simq_states_to_f32,
-        # and the results are the fp32 results on the rounded state)
+        if self._typed(i, [s]):
+            x = self._typed_input(i, [s], False)
+            prob = torch.empty((arch.STATE_WIDTH, arch.STATE_WIDTH), dtype=torch.float32, device=self.device)
+            return self._concat(i, x, net.forward_nhwc(x), prob), prob
+        # (fp32 arithmetic on the state itself -- sigmoid_concat)
         x = s if torch.is_tensor(s) else states_batch([s], self.device, torch.float32) if is_handle(s) else \
             torch.from_numpy(np.ascontiguousarray(s, dtype=np.float32)).unsqueeze(0).to(self.device)
         logit = net.forward_nhwc(x)
@@ -169,7 +207,8 @@ class DQNIntentionPolicy(DQNPolicy):
                 for j, s in enumerate(g):
                     if s is not None:
                         out, prob = self._predict(i, s)
-                        state_intention[i][j] = out if _device else out[0].cpu().numpy()
+                        # (a bf16 state + map of the typed path leaves the device widened exactly: the reference's float32 array)
+                        state_intention[i][j] = out if _device else out[0].float().cpu().numpy()
                         if debug:
                             output_intention[i][j] = prob.cpu().numpy()
                 if self.train:
@@ -182,9 +221,12 @@ class DQNIntentionPolicy(DQNPolicy):
         if self.train and use_ground_truth_intention:
             return super().step(state, exploration_eps=exploration_eps, debug=debug)
         if self.train:                                                                      # drop the ground-truth map
-            # (a pool handle is read on the device and loses its last channel there; an ndarray on the host, as always)
-            state = [[None if s is None else states_batch([s], self.device, torch.float32)[..., :-1].contiguous() if is_handle(s) else s[:, :, :-1]
-                      for s in g] for g in state]
+            # (a pool handle is read on the device and loses its last channel there; an ndarray on the host, as always.  Typed path: one
+            # simq_intention_split per state, from the pool's type into the intention net's)
+            typed = [self._typed(i, [s for s in g if s is not None]) for i, g in enumerate(state)]
+            state = [[None if s is None else self._typed_input(i, [s], True) if typed[i] else
+                      states_batch([s], self.device, torch.float32)[..., :-1].contiguous() if is_handle(s) else s[:, :, :-1]
+                      for s in g] for i, g in enumerate(state)]
         state = self.step_intention(state, debug=debug, _device=not debug)
         if debug:
             state, info_intention = state
@@ -213,6 +255,14 @@ class DQNIntentionPolicy(DQNPolicy):
                 net = self.intention_nets[i]
                 net.eval()                                                                 # policies.py:101
                 xs = [states[e][i][j] for e, j in live]
+                if self._typed(i, xs):                                                     # nothing widened: see _typed
+                    x = self._typed_input(i, xs, self.train)
+                    out = self._concat(i, x, net.forward_nhwc(x))
+                    for k, (e, j) in enumerate(live):
+                        pred[e][i][j] = out[k:k + 1]
+                    if self.train:
+                        net.train()
+                    continue
                 if any(is_handle(s) for s in xs):                                          # pool handles: the batch is formed in HBM
                     x = states_batch(xs, self.device, torch.float32)   # (handles of a bf16 pool: widened exactly, as in _predict)
                     if self.train:
