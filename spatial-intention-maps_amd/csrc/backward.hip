@@ -321,16 +321,8 @@ int backward_impl(const Ctx& c, const float* d_dq, int phase, const OneHotGrad* 
     // (T0 = dz is dead behind bn_bwd: it holds the partial-sum slabs.  A slot is smax floats and 9 B slabs of 64 * 49 * Cin floats fit it
     // up to Cin = 10 only: the launch takes as many slabs as the slot holds and refuses when it holds none)
     const int64_t slab_cap = smax * (int64_t)sizeof(float);
-    if (stem16 && c.W.stem_wide && p->opt.bf16_states)
-        RC(launch_stem_wgrad_bf16_wide_x16(reinterpret_cast<const uint16_t*>(x0.f), T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream,
-                                           slab_cap));
-    else if (stem16 && c.W.stem_wide)
-        RC(launch_stem_wgrad_bf16_wide(x0.f, T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream, slab_cap));
-    else if (stem16 && p->opt.bf16_states)           // (bf16 states: the caller's minibatch, or the forward's bf16 copy of it)
-        RC(launch_stem_wgrad_bf16_x16(reinterpret_cast<const uint16_t*>(x0.f), T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream,
-                                      slab_cap));
-    else if (stem16)
-        RC(launch_stem_wgrad_bf16(x0.f, T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream, slab_cap));
+    if (c.W.stem_ks)                                 // (bf16 states: the caller's minibatch, or the forward's bf16 copy of it)
+        RC(launch_stem_wgrad_bf16(c.stem_x(x0.f), c.W.stem_ks, T1.pl.hi, c.grads + p->stem.w_off, T0, B, 96, 96, p->cin, c.stream, slab_cap));
     else
         RC(conv_wgrad(c, p->stem, x0, T1, 96, InBn(), true));
     if (late_join) RC(join());

@@ -236,35 +236,25 @@ int launch_head_bn_relu_conv3(const float* y, const BnRef& bn, const float* w3, 
 int launch_stem_pool_fwd(const float* y, const BnRef& bn, float* pooled, uint8_t* idx, int B, int H, int W, int C,
                          hipStream_t stream, Planes pl = Planes(), int y_bf16 = 0);
 // dz[b,y,x,c] (pre-relu BN output grad at HxW) from pooled-grad g at (H/2)x(W/2)
-// first convolution on the bf16 matrix cores, operands gathered straight from the fp32 NHWC input (stem_conv_bf16.hip)
-int stem_conv_bf16_wbytes();
 // stem_conv_f32.hip: the same convolution in exact fp32 on the matrix cores (fp32 / split-bf16 plans), weights straight from the OHWI parameters
 // conv_img_f32.hip: image-tile fp32 3x3 convolution of the 64-input-channel layers; 1 = taken, 0 = shape not covered, < 0 error
 int try_conv_img_f32(const float* x, const float* w, float* y, const ConvGeom& g, const ConvEpilogue& e, hipStream_t stream, const InBn& in = InBn());
 bool stem_conv_f32_eligible(int H, int W, int C, int cout, int k, int stride, int pad);
 int launch_stem_conv_f32(const float* x, const float* w_ohwi, float* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
-bool stem_conv_bf16_eligible(int H, int W, int C, int cout, int k, int stride, int pad);
-int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, hipStream_t stream);
-int launch_stem_conv_bf16(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
+// stem_conv_bf16.hip: the first convolution and its weight gradient on the bf16 matrix cores, operands gathered straight from the NHWC input.
+// Two things select among the kernels' forms, both as values:
+//   the input as the plan reads it: [B][H][W][C] fp32, or bf16 (simq_plan_options.bf16_states, 2-byte aligned)
+struct StemX { const void* p; bool bf16; };
+//   ks, the k-steps per filter row: 2 (7 * C <= 63), 3 (the wide-row form, 64 <= 7 * C <= 95: simq_plan_options.stem_bf16 = 2), 0 = not served
+int stem_conv_bf16_ksteps(int H, int W, int C, int cout, int k, int stride, int pad);
+int stem_conv_bf16_wbytes(int ks);                   // bytes of the prepared weights
+int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, int ks, hipStream_t stream);
+int launch_stem_conv_bf16(StemX x, int ks, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
 int stem_wgrad_bf16_slabs(int B, int H, int W);      // partial-sum slabs (64 * 49 * C floats each) the weight gradient asks for as scratch
 // ... and uses when its scratch holds partial_bytes (< 0: as much as it asks for); 0 = not even one slab fits (the launch refuses)
 int stem_wgrad_bf16_slabs_cap(int B, int H, int W, int C, int64_t partial_bytes);
-int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+int launch_stem_wgrad_bf16(StemX x, int ks, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
                            int64_t partial_bytes = -1);
-// the same two kernels over bf16 states (simq_plan_options.bf16_states): x is [B][H][W][C] bf16, 2-byte aligned
-int launch_stem_conv_bf16_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
-int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
-                               int64_t partial_bytes = -1);
-// the wide-row forms of all of them, 64 <= 7 * C <= 95 (simq_plan_options.stem_bf16 = 2): three k-steps per filter row, weight rows of 96
-int stem_conv_bf16_wide_wbytes();
-bool stem_conv_bf16_wide_eligible(int H, int W, int C, int cout, int k, int stride, int pad);
-int launch_stem_weight_prep_wide(const float* w, uint16_t* w16, int C, hipStream_t stream);
-int launch_stem_conv_bf16_wide(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
-int launch_stem_conv_bf16_wide_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream);
-int launch_stem_wgrad_bf16_wide(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
-                                int64_t partial_bytes = -1);
-int launch_stem_wgrad_bf16_wide_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
-                                    int64_t partial_bytes = -1);
 int launch_stem_pool_bwd(const float* g, const float* pooled, const uint8_t* idx, float* dz, int B, int H, int W,
                          int C, hipStream_t stream, int g_bf16 = 0, const float* y = nullptr, const float* mean = nullptr,
                          const float* invstd = nullptr, double* red = nullptr, int y_bf16 = 0, int replicas = 1);   // red: fused BN-backward sums

@@ -27,14 +27,15 @@ int conv_fwd(const Ctx& c, const ConvL& cv, const Act& x, float* y, const ConvGe
 }
 
 // conv (+bias); in train modes its epilogue accumulates the BatchNorm batch statistics of `bn`
-int conv_bn(const Ctx& c, const ConvL& cv, const BnL& bn, int mode, const Act& x, float* y, int hin, const InBn& in = InBn()) {
+// (`reduce` = false: the caller hands the statistics over itself -- the stem, whose other kernels do not come through here)
+int conv_bn(const Ctx& c, const ConvL& cv, const BnL& bn, int mode, const Act& x, float* y, int hin, const InBn& in = InBn(), bool reduce = true) {
     ConvGeom g = geom(c.p, cv, c.B, hin);
     ConvEpilogue e;
     if (cv.b_off >= 0) e.bias = c.params + cv.b_off;
     if (mode != SIMQ_MODE_EVAL) e.stats = c.red(bn);
     e.y_bf16 = c.ybf(cv);
     RC(conv_fwd(c, cv, x, y, g, e, mode != SIMQ_MODE_TRAIN, in));
-    if (mode != SIMQ_MODE_EVAL) RC(c.sync_reduce(c.red(bn), 2 * (int64_t)bn.C));     // SyncBN: [sum | sum of squares] over all ranks
+    if (reduce && mode != SIMQ_MODE_EVAL) RC(c.sync_reduce(c.red(bn), 2 * (int64_t)bn.C));     // SyncBN: [sum | sum of squares] over all ranks
     return 0;
 }
 
@@ -107,33 +108,18 @@ int forward_impl(const Ctx& c, int mode, const float* d_x, float* d_q) {
     const int64_t rows = (int64_t)B * 576;
     // stem: conv 7x7 s2 -> BN -> ReLU -> maxpool 3x3 s2   (resnet.py:94-97); always the fp32 kernel (Cin is 3..10)
     Act x0; x0.f = (mode == SIMQ_MODE_TRAIN && !c.x_ext) ? c.f(L.x) : const_cast<float*>(d_x);
-    const int stem16 = c.W.stem16 >= 0 ? 1 : 0;      // plain-bf16 plans: bf16 matrix cores, bf16 pre-BN output (stem_conv_bf16.hip)
-    if (stem16 && c.W.stem_wide) {                   // 64 <= 7 * Cin <= 95 under stem_bf16 = 2: the wide-row form of the same kernel
-        if (p->opt.bf16_states)
-            RC(launch_stem_conv_bf16_wide_x16(reinterpret_cast<const uint16_t*>(x0.f), reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16),
-                                              reinterpret_cast<uint16_t*>(c.f(L.y0)), mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96,
-                                              p->cin, c.stream));
-        else
-            RC(launch_stem_conv_bf16_wide(x0.f, reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16), reinterpret_cast<uint16_t*>(c.f(L.y0)),
-                                          mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96, p->cin, c.stream));
-        if (mode != SIMQ_MODE_EVAL) RC(c.sync_reduce(c.red(p->stem_bn), 2 * (int64_t)p->stem_bn.C));
-    } else if (stem16) {
-        if (p->opt.bf16_states)     // (plan creation has made sure that such a plan takes this branch)
-            RC(launch_stem_conv_bf16_x16(reinterpret_cast<const uint16_t*>(x0.f), reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16),
-                                         reinterpret_cast<uint16_t*>(c.f(L.y0)), mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96,
-                                         p->cin, c.stream));
-        else
-        RC(launch_stem_conv_bf16(x0.f, reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16), reinterpret_cast<uint16_t*>(c.f(L.y0)),
-                                 mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96, p->cin, c.stream));
-        if (mode != SIMQ_MODE_EVAL) RC(c.sync_reduce(c.red(p->stem_bn), 2 * (int64_t)p->stem_bn.C));
+    const int stem16 = c.W.stem_ks ? 1 : 0;          // plain-bf16 plans: bf16 matrix cores, bf16 pre-BN output (stem_conv_bf16.hip)
+    double* stem_stats = mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr;
+    if (c.W.stem_ks) {                               // (a bf16_states plan always takes this branch: plan creation has made sure)
+        RC(launch_stem_conv_bf16(c.stem_x(x0.f), c.W.stem_ks, reinterpret_cast<const uint16_t*>(c.wc + c.W.stem16),
+                                 reinterpret_cast<uint16_t*>(c.f(L.y0)), stem_stats, B, 96, 96, p->cin, c.stream));
     } else if (stem_conv_f32_eligible(96, 96, p->cin, p->stem.cout, p->stem.k, p->stem.stride, p->stem.pad)) {
         // fp32 / split-bf16 plans: exact-fp32 matrix-core kernel fed by 16-byte runs of the NHWC input (stem_conv_f32.hip)
-        RC(launch_stem_conv_f32(x0.f, c.params + p->stem.w_off, c.f(L.y0), mode != SIMQ_MODE_EVAL ? c.red(p->stem_bn) : nullptr, B, 96, 96,
-                                p->cin, c.stream));
-        if (mode != SIMQ_MODE_EVAL) RC(c.sync_reduce(c.red(p->stem_bn), 2 * (int64_t)p->stem_bn.C));
+        RC(launch_stem_conv_f32(x0.f, c.params + p->stem.w_off, c.f(L.y0), stem_stats, B, 96, 96, p->cin, c.stream));
     } else {
-        RC(conv_bn(c, p->stem, p->stem_bn, mode, x0, c.f(L.y0), 96));
+        RC(conv_bn(c, p->stem, p->stem_bn, mode, x0, c.f(L.y0), 96, InBn(), false));
     }
+    if (stem_stats) RC(c.sync_reduce(stem_stats, 2 * (int64_t)p->stem_bn.C));     // SyncBN, as conv_bn does it for every other layer
     Act cur = c.act(L.pooled, L.p_pooled, rows * 64);
     RC(launch_stem_pool_fwd(c.f(L.y0), bnref(c, p->stem_bn, mode, (int64_t)B * 2304), cur.f,
                             reinterpret_cast<uint8_t*>(c.ws + L.idx), B, 48, 48, 64, c.stream, cur.pl, stem16));

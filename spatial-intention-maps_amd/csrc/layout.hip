@@ -98,15 +98,11 @@ WLayout make_wlayout(const simq_plan* p) {
         W.wpl = take(p->wp_total * h);
         W.wtpl = take(p->wp_total * h);
         // plain-bf16 plans: the first convolution's weights in the layout of stem_conv_bf16.hip (options.stem_bf16 = 0: fp32 kernel)
-        // (stem_bf16 = 2: and the wide-row layout for 64 <= 7 * Cin <= 95; anything wider keeps the generic kernels)
-        if (p->precision == SIMQ_PREC_BF16 && p->opt.stem_bf16 &&
-            stem_conv_bf16_eligible(96, 96, p->stem.cin, p->stem.cout, p->stem.k, p->stem.stride, p->stem.pad))
-            W.stem16 = take(stem_conv_bf16_wbytes());
-        else if (p->precision == SIMQ_PREC_BF16 && p->opt.stem_bf16 == 2 &&
-                 stem_conv_bf16_wide_eligible(96, 96, p->stem.cin, p->stem.cout, p->stem.k, p->stem.stride, p->stem.pad)) {
-            W.stem16 = take(stem_conv_bf16_wide_wbytes());
-            W.stem_wide = true;
-        }
+        // (stem_bf16 = 2: and the wide-row layout, three k-steps, for 64 <= 7 * Cin <= 95; anything wider keeps the generic kernels)
+        int ks = p->precision == SIMQ_PREC_BF16 && p->opt.stem_bf16
+                     ? stem_conv_bf16_ksteps(96, 96, p->stem.cin, p->stem.cout, p->stem.k, p->stem.stride, p->stem.pad) : 0;
+        if (ks == 3 && p->opt.stem_bf16 != 2) ks = 0;
+        if (ks) { W.stem16 = take(stem_conv_bf16_wbytes(ks)); W.stem_ks = ks; }
     }
     W.total = off;
     return W;
@@ -258,16 +254,12 @@ int simq_plan_create_opts(int cin, int cout, int precision, const simq_plan_opti
     simq_plan* p = new simq_plan();
     p->cin = cin; p->cout = cout; p->precision = precision; p->opt = opt;
     p->stem.cin = cin; p->stem.cout = 64; p->stem.k = 7; p->stem.stride = 2; p->stem.pad = 3;      // (what make_wlayout looks at; bd.conv sets it again)
-    if (opt.bf16_states != 0 && (opt.bf16_states != 1 || make_wlayout(p).stem16 < 0)) {
-        if (opt.stem_bf16 == 2)
-            set_error("plan_create: bf16_states = %d needs a plan whose first convolution runs stem_conv_bf16 or its wide-row form: (1) precision "
-                      "SIMQ_PREC_BF16 (this plan: %d), (2) stem_bf16 = 1 or 2 (this plan: %d), (3) 7 * num_input_channels <= 95 under "
-                      "stem_bf16 = 2, <= 63 under stem_bf16 = 1 (this plan: %d channels); every other plan keeps fp32 states", opt.bf16_states,
-                      precision, opt.stem_bf16, cin);
-        else
-        set_error("plan_create: bf16_states = %d needs a plan whose first convolution runs stem_conv_bf16: (1) precision SIMQ_PREC_BF16 "
-                  "(this plan: %d), (2) stem_bf16 = 1 (this plan: %d), (3) 7 * num_input_channels <= 63 (this plan: %d channels); every "
-                  "other plan keeps fp32 states", opt.bf16_states, precision, opt.stem_bf16, cin);
+    if (opt.bf16_states != 0 && (opt.bf16_states != 1 || make_wlayout(p).stem_ks == 0)) {
+        const bool wide = opt.stem_bf16 == 2;      // (the refusal names the bounds that hold under the plan's stem_bf16)
+        set_error("plan_create: bf16_states = %d needs a plan whose first convolution runs stem_conv_bf16%s: (1) precision SIMQ_PREC_BF16 "
+                  "(this plan: %d), (2) stem_bf16 = 1%s (this plan: %d), (3) 7 * num_input_channels <= %s (this plan: %d channels); every "
+                  "other plan keeps fp32 states", opt.bf16_states, wide ? " or its wide-row form" : "", precision, wide ? " or 2" : "", opt.stem_bf16,
+                  wide ? "95 under stem_bf16 = 2, <= 63 under stem_bf16 = 1" : "63", cin);
         delete p;
         return -1;
     }
@@ -485,11 +477,8 @@ int simq_weights_prepare(const simq_plan* plan, const float* d_params, void* d_w
     }
     RC(launch_weight_prep_all(d_params, weight_table(plan), nullptr, reinterpret_cast<uint16_t*>(wc + W.wpl),
                               reinterpret_cast<uint16_t*>(wc + W.wtpl), plan->np(), plan->wp_total, static_cast<hipStream_t>(stream)));
-    if (W.stem16 >= 0 && W.stem_wide)
-        RC(launch_stem_weight_prep_wide(d_params + plan->stem.w_off, reinterpret_cast<uint16_t*>(wc + W.stem16), plan->stem.cin,
-                                        static_cast<hipStream_t>(stream)));
-    else if (W.stem16 >= 0)
-        RC(launch_stem_weight_prep(d_params + plan->stem.w_off, reinterpret_cast<uint16_t*>(wc + W.stem16), plan->stem.cin,
+    if (W.stem_ks)
+        RC(launch_stem_weight_prep(d_params + plan->stem.w_off, reinterpret_cast<uint16_t*>(wc + W.stem16), plan->stem.cin, W.stem_ks,
                                    static_cast<hipStream_t>(stream)));
     return 0;
 }

@@ -258,86 +258,78 @@ int simq_conv2d_fwd_stem_f32(const float* d_x, const float* d_w, float* d_y, int
     return launch_stem_conv_f32(d_x, d_w, d_y, d_stats, batch, hin, win, cin, static_cast<hipStream_t>(stream));
 }
 
+// The eight stem_bf16 operators: four (element type of d_x, row width) pairs of one forward and one weight gradient.  `name` is the entry's
+// without "simq_", `bf16` says that d_x holds bf16 elements ([batch][hin][win][cin], 2-byte aligned: what a bf16_states plan launches) and `ks`
+// is the k-steps per filter row the entry serves: 2, or 3 for the wide-row forms, 64 <= 7 * cin <= 95 (what a plan with
+// simq_plan_options.stem_bf16 = 2 launches at 10..13 channels).  The checks come in this order and nothing touches the device before them.
+static int stem_bf16_checks(const char* name, bool args_ok, const void* d_x, bool bf16, int ks, int hin, int win, int cin) {
+    SIMQ_REQUIRE(args_ok, "%s: bad argument", name);
+    SIMQ_REQUIRE(!bf16 || ((uintptr_t)d_x & 1) == 0, "%s: d_x must be 2-byte aligned", name);
+    SIMQ_REQUIRE(stem_conv_bf16_ksteps(hin, win, cin, 64, 7, 2, 3) == ks, "%s: geometry not supported (%s, win %% 32 == 0)", name,
+                 ks == 3 ? "64 <= 7 * cin <= 95" : "7 * cin <= 63");
+    return 0;
+}
+
+static int stem_bf16_fwd(const char* name, bool bf16, int ks, const void* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin,
+                         double* d_stats, void* d_scratch, void* stream) {
+    RC(stem_bf16_checks(name, d_x && d_w && d_y && d_scratch && batch >= 1, d_x, bf16, ks, hin, win, cin));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RC(launch_stem_weight_prep(d_w, static_cast<uint16_t*>(d_scratch), cin, ks, st));
+    return launch_stem_conv_bf16(StemX{d_x, bf16}, ks, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
+}
+
+static int stem_bf16_wgrad(const char* name, bool bf16, int ks, const void* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
+                           float* d_scratch, void* stream) {
+    RC(stem_bf16_checks(name, d_x && d_dy && d_dw && d_scratch && batch >= 1, d_x, bf16, ks, hin, win, cin));
+    return launch_stem_wgrad_bf16(StemX{d_x, bf16}, ks, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
+}
+
 int simq_conv2d_fwd_stem_bf16(const float* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
                               void* d_scratch, void* stream) {
-    SIMQ_REQUIRE(d_x && d_w && d_y && d_scratch && batch >= 1, "conv2d_fwd_stem_bf16: bad argument");
-    SIMQ_REQUIRE(stem_conv_bf16_eligible(hin, win, cin, 64, 7, 2, 3), "conv2d_fwd_stem_bf16: geometry not supported (7 * cin <= 63, win %% 32 == 0)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RC(launch_stem_weight_prep(d_w, static_cast<uint16_t*>(d_scratch), cin, st));
-    return launch_stem_conv_bf16(d_x, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
+    return stem_bf16_fwd("conv2d_fwd_stem_bf16", false, 2, d_x, d_w, d_y, batch, hin, win, cin, d_stats, d_scratch, stream);
 }
 
 int simq_conv2d_wgrad_stem_bf16(const float* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin, float* d_scratch,
                                 void* stream) {
-    SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16: bad argument");
-    SIMQ_REQUIRE(stem_conv_bf16_eligible(hin, win, cin, 64, 7, 2, 3), "conv2d_wgrad_stem_bf16: geometry not supported (7 * cin <= 63, win %% 32 == 0)");
-    return launch_stem_wgrad_bf16(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
+    return stem_bf16_wgrad("conv2d_wgrad_stem_bf16", false, 2, d_x, d_dy, d_dw, batch, hin, win, cin, d_scratch, stream);
 }
 
-// ... the same two operators over bf16 states (d_x [batch][hin][win][cin] bf16, 2-byte aligned): what a bf16_states plan launches
 int simq_conv2d_fwd_stem_bf16_x16(const uint16_t* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
                                   void* d_scratch, void* stream) {
-    SIMQ_REQUIRE(d_x && d_w && d_y && d_scratch && batch >= 1, "conv2d_fwd_stem_bf16_x16: bad argument");
-    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_fwd_stem_bf16_x16: d_x must be 2-byte aligned");
-    SIMQ_REQUIRE(stem_conv_bf16_eligible(hin, win, cin, 64, 7, 2, 3), "conv2d_fwd_stem_bf16_x16: geometry not supported (7 * cin <= 63, win %% 32 == 0)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RC(launch_stem_weight_prep(d_w, static_cast<uint16_t*>(d_scratch), cin, st));
-    return launch_stem_conv_bf16_x16(d_x, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
+    return stem_bf16_fwd("conv2d_fwd_stem_bf16_x16", true, 2, d_x, d_w, d_y, batch, hin, win, cin, d_stats, d_scratch, stream);
 }
 
 int simq_conv2d_wgrad_stem_bf16_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin, float* d_scratch,
                                     void* stream) {
-    SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16_x16: bad argument");
-    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_wgrad_stem_bf16_x16: d_x must be 2-byte aligned");
-    SIMQ_REQUIRE(stem_conv_bf16_eligible(hin, win, cin, 64, 7, 2, 3), "conv2d_wgrad_stem_bf16_x16: geometry not supported (7 * cin <= 63, win %% 32 == 0)");
-    return launch_stem_wgrad_bf16_x16(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
+    return stem_bf16_wgrad("conv2d_wgrad_stem_bf16_x16", true, 2, d_x, d_dy, d_dw, batch, hin, win, cin, d_scratch, stream);
 }
 
-// ... and the wide-row forms of the four, 64 <= 7 * cin <= 95 (what a plan with simq_plan_options.stem_bf16 = 2 launches at 10..13 channels)
-#define SIMQ_WIDE_GEOMETRY(name) \
-    SIMQ_REQUIRE(stem_conv_bf16_wide_eligible(hin, win, cin, 64, 7, 2, 3), name ": geometry not supported (64 <= 7 * cin <= 95, win %% 32 == 0)")
+int simq_conv2d_fwd_stem_bf16_wide(const float* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
+                                   void* d_scratch, void* stream) {
+    return stem_bf16_fwd("conv2d_fwd_stem_bf16_wide", false, 3, d_x, d_w, d_y, batch, hin, win, cin, d_stats, d_scratch, stream);
+}
 
-int64_t simq_conv2d_fwd_stem_bf16_wide_scratch_bytes(void) { return stem_conv_bf16_wide_wbytes(); }
+int simq_conv2d_wgrad_stem_bf16_wide(const float* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin, float* d_scratch,
+                                     void* stream) {
+    return stem_bf16_wgrad("conv2d_wgrad_stem_bf16_wide", false, 3, d_x, d_dy, d_dw, batch, hin, win, cin, d_scratch, stream);
+}
+
+int simq_conv2d_fwd_stem_bf16_wide_x16(const uint16_t* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
+                                       void* d_scratch, void* stream) {
+    return stem_bf16_fwd("conv2d_fwd_stem_bf16_wide_x16", true, 3, d_x, d_w, d_y, batch, hin, win, cin, d_stats, d_scratch, stream);
+}
+
+int simq_conv2d_wgrad_stem_bf16_wide_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin, float* d_scratch,
+                                         void* stream) {
+    return stem_bf16_wgrad("conv2d_wgrad_stem_bf16_wide_x16", true, 3, d_x, d_dy, d_dw, batch, hin, win, cin, d_scratch, stream);
+}
+
+int64_t simq_conv2d_fwd_stem_bf16_wide_scratch_bytes(void) { return stem_conv_bf16_wbytes(3); }
 
 int simq_conv2d_wgrad_stem_bf16_slabs(int batch, int hin, int win, int cin, int64_t capacity_bytes) {
     SIMQ_REQUIRE(batch >= 1 && hin >= 2 && win >= 32 && cin >= 1, "conv2d_wgrad_stem_bf16_slabs: bad argument");
     return stem_wgrad_bf16_slabs_cap(batch, hin, win, cin, capacity_bytes);
 }
-
-int simq_conv2d_fwd_stem_bf16_wide(const float* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
-                                   void* d_scratch, void* stream) {
-    SIMQ_REQUIRE(d_x && d_w && d_y && d_scratch && batch >= 1, "conv2d_fwd_stem_bf16_wide: bad argument");
-    SIMQ_WIDE_GEOMETRY("conv2d_fwd_stem_bf16_wide");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RC(launch_stem_weight_prep_wide(d_w, static_cast<uint16_t*>(d_scratch), cin, st));
-    return launch_stem_conv_bf16_wide(d_x, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
-}
-
-int simq_conv2d_wgrad_stem_bf16_wide(const float* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin, float* d_scratch,
-                                     void* stream) {
-    SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16_wide: bad argument");
-    SIMQ_WIDE_GEOMETRY("conv2d_wgrad_stem_bf16_wide");
-    return launch_stem_wgrad_bf16_wide(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
-}
-
-int simq_conv2d_fwd_stem_bf16_wide_x16(const uint16_t* d_x, const float* d_w, uint16_t* d_y, int batch, int hin, int win, int cin, double* d_stats,
-                                       void* d_scratch, void* stream) {
-    SIMQ_REQUIRE(d_x && d_w && d_y && d_scratch && batch >= 1, "conv2d_fwd_stem_bf16_wide_x16: bad argument");
-    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_fwd_stem_bf16_wide_x16: d_x must be 2-byte aligned");
-    SIMQ_WIDE_GEOMETRY("conv2d_fwd_stem_bf16_wide_x16");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RC(launch_stem_weight_prep_wide(d_w, static_cast<uint16_t*>(d_scratch), cin, st));
-    return launch_stem_conv_bf16_wide_x16(d_x, static_cast<const uint16_t*>(d_scratch), d_y, d_stats, batch, hin, win, cin, st);
-}
-
-int simq_conv2d_wgrad_stem_bf16_wide_x16(const uint16_t* d_x, const uint16_t* d_dy, float* d_dw, int batch, int hin, int win, int cin,
-                                         float* d_scratch, void* stream) {
-    SIMQ_REQUIRE(d_x && d_dy && d_dw && d_scratch && batch >= 1, "conv2d_wgrad_stem_bf16_wide_x16: bad argument");
-    SIMQ_REQUIRE(((uintptr_t)d_x & 1) == 0, "conv2d_wgrad_stem_bf16_wide_x16: d_x must be 2-byte aligned");
-    SIMQ_WIDE_GEOMETRY("conv2d_wgrad_stem_bf16_wide_x16");
-    return launch_stem_wgrad_bf16_wide_x16(d_x, d_dy, d_dw, d_scratch, batch, hin, win, cin, static_cast<hipStream_t>(stream));
-}
-#undef SIMQ_WIDE_GEOMETRY
 
 int simq_states_to_bf16(const float* d_src, uint16_t* d_dst, int64_t n, void* stream) {
     SIMQ_REQUIRE(d_src && d_dst && n >= 1, "states_to_bf16: NULL pointer or n < 1");

@@ -134,7 +134,7 @@ Layout make_layout(const simq_plan* p, int B);      // layout.hip
 // and of their flipped/transposed form.  Filled by simq_weights_prepare.
 struct WLayout {
     int64_t wt = -1, wpl = -1, wtpl = -1, wu = -1, stem16 = -1, total = 0;
-    bool stem_wide = false;      // stem16 >= 0 holds the wide-row layout (64 <= 7 * Cin <= 95, stem_bf16 = 2): the walks launch the *_wide kernels
+    int stem_ks = 0;             // which stem_conv_bf16 form stem16 serves (k-steps per filter row: 2, or 3 = wide rows under stem_bf16 = 2); 0: none, stem16 < 0
 };
 WLayout make_wlayout(const simq_plan* p);            // layout.hip
 
@@ -173,6 +173,8 @@ struct Ctx {
     double bn_rows(int64_t rows) const { return sync ? (double)rows / (double)B * (double)sync->global_batch : (double)rows; }
     int sync_reduce(double* buf, int64_t count) const { return sync ? sync->reduce(sync->user, buf, count, stream) : 0; }
     float* f(int64_t off) const { return reinterpret_cast<float*>(ws + off); }
+    // the minibatch as the bf16 stem reads it: fp32, or bf16 elements behind the same pointer (a bf16_states plan)
+    StemX stem_x(const float* x) const { return StemX{x, p->opt.bf16_states != 0}; }
     float* aux(const BnL& b, int which) const { return f(L.aux) + b.aux_off + (int64_t)which * b.C; }   // 0 scale 1 shift 2 mean 3 invstd
     double* red(const BnL& b) const { return reinterpret_cast<double*>(ws + L.red) + b.red_off; }
     bool mc() const { return p->precision != SIMQ_PREC_FP32; }      // matrix-core bf16 / split-bf16 convolutions

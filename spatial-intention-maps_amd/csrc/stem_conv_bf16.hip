@@ -17,6 +17,7 @@
 //   * Cin = 10..13 (7*Cin = 70..91: simq_plan_options.stem_bf16 = 2): the same kernels with THREE k-steps per filter row
 //     (K = 96, rows of 680 elements in LDS, one block of 16 waves per CU); the figures above are for Cin <= 9.
 #include <cstdint>
+#include <type_traits>
 
 #include "common.h"
 
@@ -422,25 +423,38 @@ int stem_wgrad_bf16_slabs_cap(int B, int H, int W, int C, int64_t capacity_bytes
     return slabs;
 }
 
-bool stem_conv_bf16_eligible(int H, int W, int C, int cout, int k, int stride, int pad) {
-    return cout == COUT && k == R && stride == 2 && pad == 3 && C >= 1 && R * C <= Row<2>::KROW - 1 && H % 2 == 0 && W % 32 == 0;
-}
-
-// the wide-row form: 64 <= 7 * C <= 95
-bool stem_conv_bf16_wide_eligible(int H, int W, int C, int cout, int k, int stride, int pad) {
-    return cout == COUT && k == R && stride == 2 && pad == 3 && R * C >= Row<2>::KROW && R * C <= Row<3>::KROW - 1 && H % 2 == 0 && W % 32 == 0;
+// k-steps per filter row of the form that serves this convolution: 2 (7 * C <= 63), 3 (the wide-row form, 64 <= 7 * C <= 95), 0 = not served
+int stem_conv_bf16_ksteps(int H, int W, int C, int cout, int k, int stride, int pad) {
+    if (cout != COUT || k != R || stride != 2 || pad != 3 || C < 1 || H % 2 != 0 || W % 32 != 0) return 0;
+    return R * C <= Row<2>::KROW - 1 ? 2 : R * C <= Row<3>::KROW - 1 ? 3 : 0;
 }
 
 namespace {
 
-template <int KS> bool eligible_ks(int H, int W, int C) {
-    return KS == 2 ? stem_conv_bf16_eligible(H, W, C, COUT, R, 2, 3) : stem_conv_bf16_wide_eligible(H, W, C, COUT, R, 2, 3);
+// The launch family of an operator, a row width and an input type, for the launch log and the refusal texts: the operator, + "_wide" for
+// three k-steps, + "_x16" over bf16 states.  (String literals: the launch log keeps the pointer.)
+#define SIMQ_STEM_FAMILIES(op) {op, op "_x16", op "_wide", op "_wide_x16"}
+const char* stem_family(bool wgrad, int ks, bool bf16) {
+    static const char* const names[2][4] = {SIMQ_STEM_FAMILIES("stem_conv_bf16"), SIMQ_STEM_FAMILIES("stem_wgrad_bf16")};
+    return names[wgrad ? 1 : 0][(ks == 3 ? 2 : 0) + (bf16 ? 1 : 0)];
+}
+#undef SIMQ_STEM_FAMILIES
+
+// The one place where (input type, row width) become template arguments: f(x as a pointer to its element type, the k-steps as a type),
+// once ks is what the shape takes
+template <int KS> using KSteps = std::integral_constant<int, KS>;
+template <typename F>
+int stem_dispatch(const char* family, StemX x, int ks, int H, int W, int C, F f) {
+    SIMQ_REQUIRE(ks != 0 && stem_conv_bf16_ksteps(H, W, C, COUT, R, 2, 3) == ks, "%s: shape %dx%dx%d not covered", family, H, W, C);
+    const float* xf = static_cast<const float*>(x.p);
+    const uint16_t* x16 = static_cast<const uint16_t*>(x.p);
+    if (ks == 2) return !x.bf16 ? f(xf, KSteps<2>()) : f(x16, KSteps<2>());
+    return !x.bf16 ? f(xf, KSteps<3>()) : f(x16, KSteps<3>());
 }
 
-template <typename XE, int KS>
+template <int KS, typename XE>
 int stem_wgrad_bf16_impl(const char* family, const XE* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
                          int64_t partial_bytes) {
-    SIMQ_REQUIRE(eligible_ks<KS>(H, W, C), "%s: shape %dx%dx%d not covered", family, H, W, C);
     SIMQ_REQUIRE(4.0 * B * H * W * C < 4294967000.0, "%s: input too large", family);     // (elements: the kernels index them with 31 bits to spare)
     StemWgradArgs<XE> p;
     p.x = x; p.dy = dy; p.partial = partial;
@@ -461,44 +475,30 @@ int stem_wgrad_bf16_impl(const char* family, const XE* x, const uint16_t* dy, fl
 }  // namespace
 
 // dy: bf16 [B][H/2][W/2][64];  dw: [64][7][7][C] fp32 (overwritten);  partial: stem_wgrad_bf16_slabs_cap(.., partial_bytes) * 64 * 49 * C floats
-int launch_stem_wgrad_bf16(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream, int64_t partial_bytes) {
-    return stem_wgrad_bf16_impl<float, 2>("stem_wgrad_bf16", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
-}
-// ... over bf16 states: x is [B][H][W][C] bf16
-int launch_stem_wgrad_bf16_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
-                               int64_t partial_bytes) {
-    return stem_wgrad_bf16_impl<uint16_t, 2>("stem_wgrad_bf16_x16", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
-}
-// ... and the wide-row forms (64 <= 7 * C <= 95)
-int launch_stem_wgrad_bf16_wide(const float* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
-                                int64_t partial_bytes) {
-    return stem_wgrad_bf16_impl<float, 3>("stem_wgrad_bf16_wide", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
-}
-int launch_stem_wgrad_bf16_wide_x16(const uint16_t* x, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
-                                    int64_t partial_bytes) {
-    return stem_wgrad_bf16_impl<uint16_t, 3>("stem_wgrad_bf16_wide_x16", x, dy, dw, partial, B, H, W, C, stream, partial_bytes);
+int launch_stem_wgrad_bf16(StemX x, int ks, const uint16_t* dy, float* dw, float* partial, int B, int H, int W, int C, hipStream_t stream,
+                           int64_t partial_bytes) {
+    const char* family = stem_family(true, ks, x.bf16);
+    return stem_dispatch(family, x, ks, H, W, C, [&](auto* xe, auto k) {
+        return stem_wgrad_bf16_impl<decltype(k)::value>(family, xe, dy, dw, partial, B, H, W, C, stream, partial_bytes);
+    });
 }
 
-int stem_conv_bf16_wbytes() { return COUT * Row<2>::WROW * 2; }
-int stem_conv_bf16_wide_wbytes() { return COUT * Row<3>::WROW * 2; }
+// bytes of the prepared weights: [64][WROW] bf16 (58 368 | 87 040)
+int stem_conv_bf16_wbytes(int ks) { return COUT * (ks == 3 ? Row<3>::WROW : Row<2>::WROW) * 2; }
 
-int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, hipStream_t stream) {
-    hipLaunchKernelGGL(stem_weight_prep_kernel<2>, dim3(32), dim3(256), 0, stream, w, w16, C);
-    SIMQ_CHECK_LAUNCH();
-    return 0;
-}
-int launch_stem_weight_prep_wide(const float* w, uint16_t* w16, int C, hipStream_t stream) {
-    hipLaunchKernelGGL(stem_weight_prep_kernel<3>, dim3(32), dim3(256), 0, stream, w, w16, C);
+int launch_stem_weight_prep(const float* w, uint16_t* w16, int C, int ks, hipStream_t stream) {
+    SIMQ_REQUIRE(ks == 2 || ks == 3, "stem_weight_prep: %d k-steps per filter row (2 or 3)", ks);
+    void (*prep)(const float*, uint16_t*, int) = ks == 2 ? stem_weight_prep_kernel<2> : stem_weight_prep_kernel<3>;
+    hipLaunchKernelGGL(prep, dim3(32), dim3(256), 0, stream, w, w16, C);
     SIMQ_CHECK_LAUNCH();
     return 0;
 }
 
 namespace {
 
-template <typename XE, int KS>
+template <int KS, typename XE>
 int stem_conv_bf16_impl(const char* family, const XE* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
     constexpr int NWAVE = Row<KS>::NWAVE;
-    SIMQ_REQUIRE(eligible_ks<KS>(H, W, C), "%s: shape %dx%dx%d not covered", family, H, W, C);
     const double xb = 4.0 * B * H * W * C;
     SIMQ_REQUIRE(xb < 4294967000.0, "%s: input exceeds the 4 GiB buffer-addressing limit", family);
     StemArgs<XE> p;
@@ -524,19 +524,12 @@ int stem_conv_bf16_impl(const char* family, const XE* x, const uint16_t* w16, ui
 }  // namespace
 
 // y: bf16 [B][H/2][W/2][64];  stats: NULL or [2 * 64] doubles (accumulated into)
-int launch_stem_conv_bf16(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_conv_bf16_impl<float, 2>("stem_conv_bf16", x, w16, y, stats, B, H, W, C, stream);
-}
-// ... over bf16 states: x is [B][H][W][C] bf16
-int launch_stem_conv_bf16_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_conv_bf16_impl<uint16_t, 2>("stem_conv_bf16_x16", x, w16, y, stats, B, H, W, C, stream);
-}
-// ... and the wide-row forms (64 <= 7 * C <= 95; w16 in the layout of launch_stem_weight_prep_wide)
-int launch_stem_conv_bf16_wide(const float* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_conv_bf16_impl<float, 3>("stem_conv_bf16_wide", x, w16, y, stats, B, H, W, C, stream);
-}
-int launch_stem_conv_bf16_wide_x16(const uint16_t* x, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
-    return stem_conv_bf16_impl<uint16_t, 3>("stem_conv_bf16_wide_x16", x, w16, y, stats, B, H, W, C, stream);
+// (w16 in the layout launch_stem_weight_prep makes for the same ks)
+int launch_stem_conv_bf16(StemX x, int ks, const uint16_t* w16, uint16_t* y, double* stats, int B, int H, int W, int C, hipStream_t stream) {
+    const char* family = stem_family(false, ks, x.bf16);
+    return stem_dispatch(family, x, ks, H, W, C, [&](auto* xe, auto k) {
+        return stem_conv_bf16_impl<decltype(k)::value>(family, xe, w16, y, stats, B, H, W, C, stream);
+    });
 }
 
 }  // namespace simq

@@ -808,7 +808,7 @@ def test_stem_conv_f32_matches_an_fp64_convolution(L, B, C):
 def test_stem_kernels_refuse_ten_input_channels(L):
     """Cin = 10 (the reference's widest intention-channel variant): 7 * Cin = 70 exceeds the 64-float filter row both dedicated stem
     kernels are built around -- they refuse it with a message, and plans of that width run the generic implicit GEMM / fp32 weight
-    gradient instead (forward_impl: stem_conv_f32_eligible / stem_conv_bf16_eligible; CONV_CASES above cover that path at Cin = 10)."""
+    gradient instead (forward_impl: stem_conv_f32_eligible / WLayout::stem_ks; CONV_CASES above cover that path at Cin = 10)."""
     x = torch.zeros(1, 96, 96, 10, device='cuda'); w = torch.zeros(64, 7, 7, 10, device='cuda'); y = torch.zeros(1, 48, 48, 64, device='cuda')
     with pytest.raises(Exception, match='geometry not supported'):
         L.lib.call('simq_conv2d_fwd_stem_f32', L.ptr(x), L.ptr(w), L.ptr(y), 1, 96, 96, 10, None, L.stream_ptr())
