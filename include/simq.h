@@ -1115,6 +1115,36 @@ int simq_local_state_images_slots_bf16(const simq_local_map* maps, int n_maps, c
                                        const simq_local_channel* channels, int n_channels, const int64_t* slots, void* d_desc,
                                        int64_t desc_bytes, uint16_t* d_pool, int64_t pool_slots, void* stream);
 
+/* simq_local_state_images_slots with a POOL per problem as well: problem p's [96][96][C] image begins at slot dests[p].slot of pool
+ * pools[dests[p].pool], and a slot holds 96 * 96 * C elements of that pool's type -- fp32, or bf16 (the element the bf16 entries
+ * store), so that the states of robot groups whose replay pools differ, in place and in type, are written by one launch.  `pools`
+ * (1 .. SIMQ_LOCAL_MAX_POOLS entries; one may receive no problem) and `dests` (n entries) are HOST arrays and travel behind the
+ * other descriptor blocks: d_desc takes simq_local_state_pools_desc_bytes(...) bytes (the slots size plus the two tables; -1 where
+ * simq_local_state_slots_desc_bytes gives -1).  Checked on the host with everything else, before anything is copied or launched:
+ * every d_pool non-NULL and aligned to its element (4 bytes, or 2), bf16 0 or 1, pool_slots in the slots entry's range, no two pools
+ * sharing a byte (so none listed twice), 0 <= dests[p].pool < n_pools, 0 <= dests[p].slot < that pool's pool_slots, no (pool, slot)
+ * named twice (the same slot number in two pools is fine), and no WRITTEN slot of any pool sharing a byte with a map, the mask bank
+ * or d_desc -- a map kept in another slot of a listed pool is read in place.  Every other rule is simq_local_state_images_slots',
+ * and every byte written is the byte that entry (fp32 pool) or simq_local_state_images_slots_bf16 (bf16 pool) writes for the same
+ * problem into the same slot.  Logged as "local_state_pools". */
+#define SIMQ_LOCAL_MAX_POOLS 16
+typedef struct simq_local_pool {
+    void* d_pool;               /* [pool_slots][96][96][C] on the device */
+    int64_t pool_slots;
+    int32_t bf16;               /* 0: fp32 elements, 1: bf16 elements */
+    int32_t reserved_;
+} simq_local_pool;
+typedef struct simq_local_dest {
+    int64_t slot;               /* of pools[pool] */
+    int32_t pool;
+    int32_t reserved_;
+} simq_local_dest;
+int64_t simq_local_state_pools_desc_bytes(int n_maps, int n_robots, int n, int n_channels, int n_pools);
+int simq_local_state_images_pools(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks, const simq_local_robot* robots,
+                                  int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels,
+                                  int n_channels, const simq_local_pool* pools, int n_pools, const simq_local_dest* dests, void* d_desc,
+                                  int64_t desc_bytes, void* stream);
+
 /* ---- global intention / history maps (Mapper._create_global_intention_or_history_map, envs.py:2301-2346, and the per-robot spatial
  * maps of Mapper._get_intention_channels, envs.py:2360-2366) ----------------------------------------------------------------------
  * One problem = one global map d_out[p][rows][cols] fp32, every map of a call in one launch; the kernel writes every pixel, so the
@@ -1348,7 +1378,8 @@ int simq_profile_stop(double* out, int max_kinds);
 /* ... and a launch log (always on): every launcher names the kernel FAMILY that took a launch -- "igemm_bf16_img_whole" / "_half" (image
  * tile), "igemm_bf16_c64", "igemm_bf16_pp", "igemm_bf16_dma", "igemm_bf16_reg", "wgrad_bf16_img", "wgrad_bf16_pp", "wgrad_bf16_reg",
  * "stem_conv_bf16", "stem_wgrad_bf16", "stem_conv_bf16_wide[_x16]", "stem_wgrad_bf16_wide[_x16]", "bn_apply16", "bn_bwd_apply16[_mask_from_y]", "gemm_f32_batched", "igemm_f32", "conv_img_f32",
- * "stem_conv_f32", "winograd_f2" / "winograd_f4" [_wgrad], "wgrad_f32" [_batched] ... (csrc: note_launch).  simq_launch_count: launches
+ * "stem_conv_f32", "winograd_f2" / "winograd_f4" [_wgrad], "wgrad_f32" [_batched], "local_state" [_bf16], "local_state_slots" [_bf16],
+ * "local_state_pools" ... (csrc: note_launch).  simq_launch_count: launches
  * of one family since the last reset (0 for a name that never ran); simq_launch_counts: "name=count;..." of every family that ran.
  * The parity tests use it to assert that the kernels a batch size is meant to select DID run. */
 int simq_launch_counts_reset(void);

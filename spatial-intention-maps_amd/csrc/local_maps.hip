@@ -58,6 +58,33 @@ __device__ __forceinline__ OT* image_of(const SlotDesc& d, OT* pool, unsigned p)
     return slot >= 0 && slot < d.pool_slots ? pool + slot * ((int64_t)kPix * d.C) : nullptr;
 }
 
+struct PoolDesc : Desc {                          // simq_local_state_images_pools: problem p is written to slot dests[p].slot of pool dests[p].pool
+    const simq_local_pool* pools;
+    const simq_local_dest* dests;
+    int n_pools;
+};
+
+struct PoolImage {                                // an image in one of several pools: where it begins and what its elements are
+    void* base;
+    bool bf16;
+};
+
+// Both table entries are indexed by values that are uniform over the workgroup (blockIdx, then the entry just read), so they are scalar
+// loads and `bf16` is a scalar: the branch on it at the store is taken by the whole workgroup.  NULL as in the slot form: a pool index or
+// a slot outside its table.
+__device__ __forceinline__ PoolImage image_of(const PoolDesc& d, void*, unsigned p) {
+    const simq_local_dest t = d.dests[p];
+    if (t.pool < 0 || t.pool >= d.n_pools) return {nullptr, false};
+    const simq_local_pool q = d.pools[t.pool];
+    if (t.slot < 0 || t.slot >= q.pool_slots) return {nullptr, false};
+    const int64_t slot_bytes = (int64_t)kPix * d.C * (q.bf16 ? 2 : 4);
+    return {static_cast<char*>(q.d_pool) + t.slot * slot_bytes, q.bf16 != 0};
+}
+
+template <typename OT>
+__device__ __forceinline__ bool no_image(const OT* o) { return o == nullptr; }
+__device__ __forceinline__ bool no_image(const PoolImage& o) { return o.base == nullptr; }
+
 // input index along both axes of an n x n image for output index (oi, oj) of its rotation; false: outside (the pixel is 0)
 __device__ __forceinline__ bool rotate_index(const simq_local_rotation& t, int n, int oi, int oj, int* i0, int* i1) {
     // HIP's __dmul_rn / __dadd_rn are plain * and + and hipcc contracts them into v_fmac_f64 by default: the pragma is what keeps every
@@ -94,8 +121,19 @@ __device__ __forceinline__ float robot_value(const Desc& d, const simq_local_pro
 __device__ __forceinline__ void store_state(float* o, float v) { *o = v; }
 __device__ __forceinline__ void store_state(uint16_t* o, float v) { *o = __builtin_bit_cast(uint16_t, (__bf16)v); }
 
-// D: Desc (out is the [n][96][96][C] batch) or SlotDesc (out is the pool); OT: float, or uint16_t for bf16 states; everything but the
-// image's base and the last store is the same code
+// element `it` of an image: of a typed one, or of a pool image as the pool's type (the one branch of the pools form)
+template <typename OT>
+__device__ __forceinline__ void store_element(OT* o, int it, float v) { store_state(o + it, v); }
+__device__ __forceinline__ void store_element(const PoolImage& o, int it, float v) {
+    if (o.bf16)
+        store_state(static_cast<uint16_t*>(o.base) + it, v);
+    else
+        store_state(static_cast<float*>(o.base) + it, v);
+}
+
+// D: Desc (out is the [n][96][96][C] batch), SlotDesc (out is the pool) or PoolDesc (out is unused: the pools are in the descriptor);
+// OT: float, or uint16_t for bf16 states (PoolDesc: void, the type comes with the problem's pool); everything but the image's base and
+// the last store is the same code
 template <typename D, typename OT>
 __global__ void __launch_bounds__(kThreads) local_state_kernel(D d, OT* __restrict__ out) {
     __shared__ int gidx[kPix];                    // gi * cols + gj of the local pixel, -1 outside the crop
@@ -137,9 +175,9 @@ __global__ void __launch_bounds__(kThreads) local_state_kernel(D d, OT* __restri
         __syncthreads();
     }
 
-    OT* o = image_of(d, out, blockIdx.x);
-    if constexpr (std::is_same<D, SlotDesc>::value)
-        if (o == nullptr) return;                                        // (uniform over the workgroup)
+    const auto o = image_of(d, out, blockIdx.x);
+    if constexpr (!std::is_same<D, Desc>::value)
+        if (no_image(o)) return;                                         // (uniform over the workgroup)
     const int items = kPix * C;
     for (int it = tid; it < items; it += kThreads) {
         const int pix = it / C, c = it - pix * C;
@@ -160,7 +198,7 @@ __global__ void __launch_bounds__(kThreads) local_state_kernel(D d, OT* __restri
                 if (kind == SIMQ_LOCAL_OVERHEAD && !(v > 0.f)) v = m[g];
             }
         }
-        store_state(o + it, v);
+        store_element(o, it, v);
     }
 }
 
@@ -239,25 +277,26 @@ int check_tables(const char* who, const simq_local_map* maps, int n_maps, int n_
     return 0;
 }
 
-// the descriptor tables of one call, packed into d_desc behind each other (`slots`: NULL, or the n pool slots as a fifth block)
+// the descriptor tables of one call, packed into d_desc behind each other; `more`: the n_more (0 .. 2) blocks of the entry's own behind
+// them -- the n pool slots, or the pool table and the destinations -- and more_at where each of those lies on the device
 template <typename D>
 int upload_tables(D* d, const simq_local_map* maps, int n_maps, const float* d_masks, const simq_local_robot* robots, int n_robots,
-                  const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels, const int64_t* slots,
-                  void* d_desc, const char** slots_at, hipStream_t s) {
-    const HostBlock parts[5] = {{maps, sizeof(simq_local_map) * (size_t)n_maps},
-                                {robots, sizeof(simq_local_robot) * (size_t)n_robots},
-                                {problems, sizeof(simq_local_problem) * (size_t)n},
-                                {channels, sizeof(simq_local_channel) * (size_t)n * n_channels},
-                                {slots, sizeof(int64_t) * (size_t)n}};
-    const char* at[5];
-    SIMQ_CHECK_HIP(upload_descriptors(d_desc, parts, slots ? 5 : 4, at, s));
+                  const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels, const HostBlock* more,
+                  int n_more, void* d_desc, const char** more_at, hipStream_t s) {
+    HostBlock parts[6] = {{maps, sizeof(simq_local_map) * (size_t)n_maps},
+                          {robots, sizeof(simq_local_robot) * (size_t)n_robots},
+                          {problems, sizeof(simq_local_problem) * (size_t)n},
+                          {channels, sizeof(simq_local_channel) * (size_t)n * n_channels}};
+    for (int k = 0; k < n_more; ++k) parts[4 + k] = more[k];
+    const char* at[6];
+    SIMQ_CHECK_HIP(upload_descriptors(d_desc, parts, 4 + n_more, at, s));
     d->maps = reinterpret_cast<const simq_local_map*>(at[0]);
     d->robots = reinterpret_cast<const simq_local_robot*>(at[1]);
     d->probs = reinterpret_cast<const simq_local_problem*>(at[2]);
     d->chans = reinterpret_cast<const simq_local_channel*>(at[3]);
     d->masks = d_masks;
     d->C = n_channels;
-    if (slots) *slots_at = at[4];
+    for (int k = 0; k < n_more; ++k) more_at[k] = at[4 + k];
     return 0;
 }
 
@@ -276,6 +315,11 @@ extern "C" int64_t simq_local_state_desc_bytes(int n_maps, int n_robots, int n, 
 extern "C" int64_t simq_local_state_slots_desc_bytes(int n_maps, int n_robots, int n, int n_channels) {
     const int64_t tables = simq_local_state_desc_bytes(n_maps, n_robots, n, n_channels);
     return tables < 0 ? -1 : tables + (int64_t)sizeof(int64_t) * n;
+}
+
+extern "C" int64_t simq_local_state_pools_desc_bytes(int n_maps, int n_robots, int n, int n_channels, int n_pools) {
+    const int64_t slots = simq_local_state_slots_desc_bytes(n_maps, n_robots, n, n_channels);
+    return slots < 0 || n_pools < 0 ? -1 : slots + (int64_t)sizeof(simq_local_pool) * n_pools + (int64_t)sizeof(simq_local_dest) * n;
 }
 
 namespace {
@@ -312,7 +356,7 @@ int state_images(const char* who, const char* family, const simq_local_map* maps
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     Desc d;
-    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, nullptr, d_desc, nullptr, s)) return rc;
+    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, nullptr, 0, d_desc, nullptr, s)) return rc;
     local_state_kernel<Desc, OT><<<n, kThreads, 0, s>>>(d, d_out);
     SIMQ_CHECK_LAUNCH();
     note_launch(family);
@@ -357,13 +401,86 @@ int state_images_slots(const char* who, const char* family, const simq_local_map
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     SlotDesc d;
+    const HostBlock table = {slots, sizeof(int64_t) * (size_t)n};
     const char* slots_at = nullptr;
-    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, slots, d_desc, &slots_at, s)) return rc;
+    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, &table, 1, d_desc, &slots_at, s)) return rc;
     d.slots = reinterpret_cast<const int64_t*>(slots_at);
     d.pool_slots = pool_slots;
     local_state_kernel<SlotDesc, OT><<<n, kThreads, 0, s>>>(d, d_pool);
     SIMQ_CHECK_LAUNCH();
     note_launch(family);
+    return 0;
+}
+
+// simq_local_state_images_pools: the slots entry's checks, pool by pool
+int state_images_pools(const char* who, const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks, const simq_local_robot* robots,
+                       int n_robots, const simq_local_problem* problems, int n, const simq_local_channel* channels, int n_channels,
+                       const simq_local_pool* pools, int n_pools, const simq_local_dest* dests, void* d_desc, int64_t desc_bytes,
+                       void* stream) {
+    SIMQ_REQUIRE(problems && channels && pools && dests && d_desc, "%s: NULL pointer", who);
+    if (int rc = check_counts(who, maps, n_maps, d_masks, n_masks, robots, n_robots, n, n_channels)) return rc;
+    SIMQ_REQUIRE(n_pools >= 1 && n_pools <= SIMQ_LOCAL_MAX_POOLS, "%s: n_pools = %d (1 .. %d)", who, n_pools, SIMQ_LOCAL_MAX_POOLS);
+    int64_t item_bytes[SIMQ_LOCAL_MAX_POOLS];
+    for (int k = 0; k < n_pools; ++k) {
+        const simq_local_pool& q = pools[k];
+        SIMQ_REQUIRE(q.bf16 == 0 || q.bf16 == 1, "%s: pool %d: bf16 = %d (0: fp32 elements, 1: bf16)", who, k, q.bf16);
+        const int elem = q.bf16 ? 2 : 4;
+        SIMQ_REQUIRE(q.d_pool, "%s: pool %d: NULL d_pool", who, k);
+        SIMQ_REQUIRE(((uintptr_t)q.d_pool & (elem - 1)) == 0, "%s: pool %d: d_pool must be %d-byte aligned", who, k, elem);
+        SIMQ_REQUIRE(q.pool_slots >= 1 && q.pool_slots <= ((int64_t)1 << 40) / (kPix * 4), "%s: pool %d: pool_slots = %lld (1 .. 2^40 bytes of pool)",
+                     who, k, (long long)q.pool_slots);
+        item_bytes[k] = (int64_t)kPix * n_channels * elem;
+    }
+    SIMQ_REQUIRE(((uintptr_t)d_desc & 7) == 0, "%s: d_desc must be 8-byte aligned", who);
+    const int64_t need_desc = simq_local_state_pools_desc_bytes(n_maps, n_robots, n, n_channels, n_pools);
+    SIMQ_REQUIRE(desc_bytes >= need_desc, "%s: d_desc holds %lld bytes, the descriptors, the pool table and the destinations take %lld", who,
+                 (long long)desc_bytes, (long long)need_desc);
+    for (int a = 0; a < n_pools; ++a)
+        for (int b = a + 1; b < n_pools; ++b)
+            SIMQ_REQUIRE(!overlaps(pools[a].d_pool, pools[a].pool_slots * item_bytes[a], pools[b].d_pool, pools[b].pool_slots * item_bytes[b]),
+                         "%s: pool %d overlaps pool %d", who, a, b);
+    std::vector<int64_t> named[SIMQ_LOCAL_MAX_POOLS], sorted[SIMQ_LOCAL_MAX_POOLS];
+    for (int p = 0; p < n; ++p) {
+        SIMQ_REQUIRE(dests[p].pool >= 0 && dests[p].pool < n_pools, "%s: problem %d: pool %d outside the %d given", who, p, dests[p].pool, n_pools);
+        named[dests[p].pool].push_back(dests[p].slot);
+    }
+    for (int k = 0; k < n_pools; ++k) {
+        int64_t which = 0;
+        const int bad = check_slots(named[k].data(), (int)named[k].size(), pools[k].pool_slots, sorted[k], &which);
+        SIMQ_REQUIRE(bad != 1, "%s: slot %lld outside pool %d of %lld", who, (long long)which, k, (long long)pools[k].pool_slots);
+        SIMQ_REQUIRE(bad != 2, "%s: slot %lld of pool %d is named twice", who, (long long)which, k);
+    }
+    // as in the slots entry, only the slots written must be clear of what the launch reads: a pool may hold a map in another slot
+    for (int k = 0; k < n_pools; ++k) {
+        const int64_t hit = written_slot_in(sorted[k], pools[k].d_pool, item_bytes[k], pools[k].pool_slots, d_desc, need_desc);
+        SIMQ_REQUIRE(hit == -1, "%s: slot %lld of pool %d overlaps d_desc", who, (long long)hit, k);
+    }
+    for (int m = 0; m < n_maps; ++m) {
+        if (int rc = check_map(who, maps[m], m)) return rc;
+        for (int k = 0; k < n_pools; ++k) {
+            const int64_t hit = written_slot_in(sorted[k], pools[k].d_pool, item_bytes[k], pools[k].pool_slots, maps[m].d_data,
+                                                (int64_t)maps[m].rows * maps[m].cols * 4);
+            SIMQ_REQUIRE(hit == -1, "%s: slot %lld of pool %d overlaps map %d", who, (long long)hit, k, m);
+        }
+    }
+    if (n_masks > 0 && d_masks)
+        for (int k = 0; k < n_pools; ++k) {
+            const int64_t hit = written_slot_in(sorted[k], pools[k].d_pool, item_bytes[k], pools[k].pool_slots, d_masks, (int64_t)n_masks * kPix * 4);
+            SIMQ_REQUIRE(hit == -1, "%s: slot %lld of pool %d overlaps the mask bank", who, (long long)hit, k);
+        }
+    if (int rc = check_tables(who, maps, n_maps, n_masks, robots, n_robots, problems, n, channels, n_channels)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PoolDesc d;
+    const HostBlock tables[2] = {{pools, sizeof(simq_local_pool) * (size_t)n_pools}, {dests, sizeof(simq_local_dest) * (size_t)n}};
+    const char* at[2] = {nullptr, nullptr};
+    if (int rc = upload_tables(&d, maps, n_maps, d_masks, robots, n_robots, problems, n, channels, n_channels, tables, 2, d_desc, at, s)) return rc;
+    d.pools = reinterpret_cast<const simq_local_pool*>(at[0]);
+    d.dests = reinterpret_cast<const simq_local_dest*>(at[1]);
+    d.n_pools = n_pools;
+    local_state_kernel<PoolDesc, void><<<n, kThreads, 0, s>>>(d, nullptr);
+    SIMQ_CHECK_LAUNCH();
+    note_launch("local_state_pools");
     return 0;
 }
 
@@ -399,4 +516,12 @@ extern "C" int simq_local_state_images_slots_bf16(const simq_local_map* maps, in
                                                   int64_t desc_bytes, uint16_t* d_pool, int64_t pool_slots, void* stream) {
     return state_images_slots<uint16_t>("local_state_images_slots_bf16", "local_state_slots_bf16", maps, n_maps, d_masks, n_masks, robots,
                                         n_robots, problems, n, channels, n_channels, slots, d_desc, desc_bytes, d_pool, pool_slots, stream);
+}
+
+extern "C" int simq_local_state_images_pools(const simq_local_map* maps, int n_maps, const float* d_masks, int n_masks,
+                                             const simq_local_robot* robots, int n_robots, const simq_local_problem* problems, int n,
+                                             const simq_local_channel* channels, int n_channels, const simq_local_pool* pools, int n_pools,
+                                             const simq_local_dest* dests, void* d_desc, int64_t desc_bytes, void* stream) {
+    return state_images_pools("local_state_images_pools", maps, n_maps, d_masks, n_masks, robots, n_robots, problems, n, channels, n_channels,
+                              pools, n_pools, dests, d_desc, desc_bytes, stream);
 }

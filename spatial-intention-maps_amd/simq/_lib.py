@@ -92,6 +92,16 @@ class IntentionArgs(ctypes.Structure):
                     'loss_sum', 'bce_scratch', 'opt_scratch', 'total_norm', 'loss_host', 'stream', 'side_stream')]
 
 
+class LocalPool(ctypes.Structure):
+    """simq_local_pool of include/simq.h (one replay pool of simq_local_state_images_pools)."""
+    _fields_ = [('d_pool', c_void_p), ('pool_slots', c_int64), ('bf16', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
+
+
+class LocalDest(ctypes.Structure):
+    """simq_local_dest of include/simq.h (where one problem of simq_local_state_images_pools is written)."""
+    _fields_ = [('slot', c_int64), ('pool', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
+
+
 _SIGS = {
     'simq_version': (c_int, []),
     'simq_build_flags': (c_int, []),
@@ -228,6 +238,9 @@ _SIGS = {
                                              c_void_p, c_int64, c_void_p]),
     'simq_local_state_images_slots_bf16': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                                    c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    'simq_local_state_pools_desc_bytes': (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    'simq_local_state_images_pools': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                              c_void_p, c_void_p, c_int64, c_void_p]),
     'simq_intention_desc_bytes': (c_int64, [c_int, c_int]),
     'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,

@@ -284,6 +284,19 @@ class _PoolObs(_DeviceObs):
 def pool_of(handles, count=None, channels=None, what='into'):
     """The AliasedDeviceReplayBuffer the handles belong to, after the checks every `into=` makes before anything is launched: handles
     from reserve / adopt that are still held, all of one pool, none twice, `count` of them, the pool's states of `channels` channels."""
+    handles = _held_handles(handles, count, what)
+    pool = handles[0].pool
+    if any(h.pool is not pool for h in handles):
+        raise ValueError('%s: the handles belong to more than one pool' % what)
+    if len({h.slot for h in handles}) != len(handles):
+        raise ValueError('%s: a handle is named twice' % what)
+    if channels is not None and pool.C != channels:
+        raise ValueError('%s: the pool holds states of %d channels, the states have %d' % (what, pool.C, channels))
+    return pool
+
+
+def _held_handles(handles, count, what):
+    """The handles as a list: `count` of them (None: one or more), each from reserve / adopt and still held."""
     handles = list(handles)
     if count is not None and len(handles) != count:
         raise ValueError('%s: %d handles for %d states' % (what, len(handles), count))
@@ -294,14 +307,36 @@ def pool_of(handles, count=None, channels=None, what='into'):
             raise ValueError('%s takes the handles of AliasedDeviceReplayBuffer.reserve, got %s' % (what, type(h).__name__))
         if not h.alive:
             raise ValueError('%s: %r' % (what, h))
-    pool = handles[0].pool
-    if any(h.pool is not pool for h in handles):
-        raise ValueError('%s: the handles belong to more than one pool' % what)
-    if len({h.slot for h in handles}) != len(handles):
+    return handles
+
+
+MAX_POOLS = 16                     # SIMQ_LOCAL_MAX_POOLS of include/simq.h
+
+
+def pools_of(handles, pools, count=None, channels=None, what='into'):
+    """pool_of for `into=` with `pools=`: the listed AliasedDeviceReplayBuffers as a list, after the checks made before anything is
+    launched -- 1 to 16 distinct rings on one device, each holding states of `channels` channels (any mix of element types); handles
+    that are still held, each of one of the listed rings, none twice, `count` of them."""
+    pools = list(pools)
+    if not 1 <= len(pools) <= MAX_POOLS:
+        raise ValueError('%s: %d pools (1 .. %d)' % (what, len(pools), MAX_POOLS))
+    for q in pools:
+        if not isinstance(q, AliasedDeviceReplayBuffer):
+            raise ValueError('%s: pools are AliasedDeviceReplayBuffers, got %s' % (what, type(q).__name__))
+    if len({id(q) for q in pools}) != len(pools):
+        raise ValueError('%s: a pool is named twice' % what)
+    for q in pools:
+        if q.pool.device != pools[0].pool.device:
+            raise ValueError('%s: the pools live on more than one device (%s and %s)' % (what, pools[0].pool.device, q.pool.device))
+        if channels is not None and q.C != channels:
+            raise ValueError('%s: a pool holds states of %d channels, the states have %d' % (what, q.C, channels))
+    handles = _held_handles(handles, count, what)
+    listed = {id(q) for q in pools}
+    if any(id(h.pool) not in listed for h in handles):
+        raise ValueError('%s: a handle belongs to a pool that is not listed' % what)
+    if len({(id(h.pool), h.slot) for h in handles}) != len(handles):
         raise ValueError('%s: a handle is named twice' % what)
-    if channels is not None and pool.C != channels:
-        raise ValueError('%s: the pool holds states of %d channels, the states have %d' % (what, pool.C, channels))
-    return pool
+    return pools
 
 
 class _PinnedStaging:
@@ -770,6 +805,26 @@ class AliasedDeviceReplayBuffer(DeviceReplayBuffer):
             lib.call(entry, *args_of(slots, d_desc))
         finally:
             self.note_write()                                # (a call that fails after its launch has still written)
+
+    @staticmethod
+    def write_pool_slots(entry, pools, handles, args_of, desc_bytes):
+        """write_slots for handles of several pools (pools_of's list) in ONE library call: `args_of(table, dests, d_desc)` gives the
+        arguments of `entry` for the host pool table (simq_local_pool, `pools`' order), the host destinations (simq_local_dest, the
+        handles' order) and a scratch tensor of desc_bytes bytes.  Every pool that receives a state is put into its stream order
+        around the call; a listed pool that receives none is not touched."""
+        from ._lib import LocalDest, LocalPool
+        index = {id(q): k for k, q in enumerate(pools)}
+        table = (LocalPool * len(pools))(*[LocalPool(q.pool.data_ptr(), q.pool.shape[0], int(q.pool.dtype == torch.bfloat16), 0) for q in pools])
+        dests = (LocalDest * len(handles))(*[LocalDest(h.slot, index[id(h.pool)], 0) for h in handles])
+        written = [pools[k] for k in sorted({d.pool for d in dests})]
+        d_desc = torch.empty(max(int(desc_bytes), 8), dtype=torch.uint8, device=pools[0].device)
+        for q in written:
+            q.order_write()
+        try:
+            lib.call(entry, *args_of(table, dests, d_desc))
+        finally:
+            for q in written:
+                q.note_write()
 
 
 class _HardwareQueues:

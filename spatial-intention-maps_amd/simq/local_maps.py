@@ -167,7 +167,7 @@ def _channel(spec, n_maps):
     return LocalChannel(KINDS[name], k, 0.0, 0), k
 
 
-def local_state_images(maps, channels, poses, robots=None, masks=None, out=None, map_shape=None, into=None):
+def local_state_images(maps, channels, poses, robots=None, masks=None, out=None, map_shape=None, into=None, pools=None):
     """The [P, 96, 96, C] float32 states of P robots in one launch.
 
     maps: a sequence of global maps [rows, cols] float32 -- device tensors are read in place (rows of one [G, rows, cols] tensor
@@ -188,9 +188,13 @@ def local_state_images(maps, channels, poses, robots=None, masks=None, out=None,
     into: instead of `out`, P handles of one AliasedDeviceReplayBuffer (reserve(P)) whose states have C channels: state p is written
     into the pool slot of into[p] (simq_local_state_images_slots), inside the pool's stream order, and the handles are returned.  A
     pool of bf16 states (dtype='bf16') receives the fp32 state rounded once to nearest even (simq_local_state_images_slots_bf16).
+    pools: with `into`, 1 to 16 distinct AliasedDeviceReplayBuffers of C channels on one device, of any mix of dtype: the handles may
+    then belong to any of them, in any interleaving, and state p goes into the slot of into[p] in its own pool -- still one launch
+    (simq_local_state_images_pools, also for one listed pool), inside the stream order of every pool that receives a state.
 
     Raises SimqError, launching nothing, when the 136 x 136 crop around a robot or the stamp of a robot leaves its map (the reference
     would silently wrap or clip the slice), and for any other descriptor the library refuses."""
+    check_pools_argument('local_state_images', out, into, pools)
     if into is None:
         args, out, keep = _prepare(maps, channels, poses, robots, masks, out, map_shape)
         lib.call('simq_local_state_images', *args)
@@ -199,25 +203,51 @@ def local_state_images(maps, channels, poses, robots=None, masks=None, out=None,
     if out is not None:
         raise ValueError('local_state_images: `into` and `out` name two destinations; pass one')
     poses = list(poses)
-    into, pool = check_into(into, 'local_state_images', len(poses))
-    args, _, keep = _prepare(maps, channels, poses, robots, masks, None, map_shape, into=into)
+    count = None
+    if pools is not None:                        # (the listed rings are checked against the channel count before a device is asked for)
+        channels = list(channels)
+        count = len(channels) if all(_is_spec(c) for c in channels) else len(channels[0]) if channels else 0
+    into, pool = check_into(into, 'local_state_images', len(poses), count, pools=pools)
+    args, _, keep = _prepare(maps, channels, poses, robots, masks, None, map_shape, into=into, pools=pools)
     write_into(pool, into, args)
     del keep
     return into
 
 
-def check_into(into, what, count=None, channels=None):
+def check_pools_argument(what, out, into, pools):
+    """`pools=` lists the rings that `into=`'s handles belong to: ValueError where it comes with `out` or without `into`."""
+    if pools is not None and out is not None:
+        raise ValueError('%s: `pools` lists the rings of `into`; `out` is a tensor of its own: pass one destination' % what)
+    if pools is not None and into is None:
+        raise ValueError('%s: `pools` without `into`: the handles say which slot of which pool a state goes to' % what)
+
+
+def check_into(into, what, count=None, channels=None, pools=None):
     """(handles, their pool) of an `into=` argument; ValueError for anything but distinct live handles of one pool (and, once the
-    caller knows them, `count` of them for states of `channels` channels)."""
-    from .learner import pool_of
+    caller knows them, `count` of them for states of `channels` channels).  pools (not None): (handles, the listed pools as a list),
+    the handles each of one of them (learner.pools_of)."""
+    from .learner import pool_of, pools_of
     into = list(into)
+    if pools is not None:
+        return into, pools_of(into, pools, count, channels, '%s(into=, pools=)' % what)
     return into, pool_of(into, count, channels, '%s(into=)' % what)
+
+
+def rings(pool):
+    """check_into's second result as a list of rings."""
+    return pool if isinstance(pool, list) else [pool]
 
 
 def write_into(pool, handles, args):
     """simq_local_state_images_slots for _prepare(into=)'s arguments: the slot table and the scratch come from the pool, which puts the
-    launch into its stream order."""
+    launch into its stream order.  pool a list (check_into(pools=)): simq_local_state_images_pools, one call for all of them."""
     n_maps, n_robots, P, C = args[1], args[5], args[7], args[9]
+    if isinstance(pool, list):
+        from .learner import AliasedDeviceReplayBuffer
+        AliasedDeviceReplayBuffer.write_pool_slots('simq_local_state_images_pools', pool, handles, lambda table, dests, d_desc: args[:10] + (
+            table, len(table), dests, ptr(d_desc), ctypes.c_int64(d_desc.numel()), stream_ptr(d_desc.device)),
+            lib.c.simq_local_state_pools_desc_bytes(n_maps, n_robots, P, C, len(pool)))
+        return
     # (a pool of bf16 states: the entry that rounds every element once as it stores it)
     entry = 'simq_local_state_images_slots_bf16' if pool.pool.dtype == torch.bfloat16 else 'simq_local_state_images_slots'
     pool.write_slots(entry, handles, lambda slots, d_desc: args[:10] + (
@@ -225,10 +255,11 @@ def write_into(pool, handles, args):
         lib.c.simq_local_state_slots_desc_bytes(n_maps, n_robots, P, C))
 
 
-def _prepare(maps, channels, poses, robots, masks, out, map_shape, into=None):
+def _prepare(maps, channels, poses, robots, masks, out, map_shape, into=None, pools=None):
     """The argument tuple of simq_local_state_images for local_state_images' inputs, the output tensor and the device tensors the
     call reads (tools/local_maps_rate.py times the library call alone with it).  into (checked handles of one pool): no output tensor
-    and no descriptor scratch are made; the first ten arguments are those of simq_local_state_images_slots (write_into)."""
+    and no descriptor scratch are made; the first ten arguments are those of simq_local_state_images_slots (write_into).  pools:
+    check_into's, for handles of several pools."""
     dev = _batch.device('local state images')
     maps, _ = _batch.as_maps(maps, 'maps', _batch.check_map)      # (numpy maps are uploaded, device tensors read in place)
     poses = list(poses)
@@ -319,7 +350,7 @@ def _prepare(maps, channels, poses, robots, masks, out, map_shape, into=None):
 
     want = (P, WIDTH, WIDTH, C)
     if into is not None:
-        check_into(into, 'local_state_images', P, C)
+        check_into(into, 'local_state_images', P, C, pools)
         return (c_maps if d_maps else None, len(d_maps), ptr(d_masks), n_masks, c_robots if n_robots else None, n_robots, c_probs, P, c_chans,
                 C), None, (d_maps, d_masks)
     if out is None:

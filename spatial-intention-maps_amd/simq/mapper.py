@@ -865,7 +865,7 @@ class BatchedMapper:
             out.append(path)
         return out
 
-    def get_states(self, robots, mappers=None, out=None, into=None):
+    def get_states(self, robots, mappers=None, out=None, into=None, pools=None):
         """Mapper.get_state() (envs.py:2067-2112) for the named mappers (all when omitted): a float32 [P, 96, 96, C] device tensor,
         state p that of mapper mappers[p], the channels in `self.channels`' order.  robots: per environment the RobotState of each
         robot, in env.robots' order (only the environments of the named mappers are read), or one RobotArrays with the same robots as
@@ -875,6 +875,10 @@ class BatchedMapper:
         written where it will be sampled from, the pool slot of into[p], and the handles are returned -- for TransitionTracker,
         the policies' step_many and ring.push, which all take them where they take an ndarray.  A pool of bf16 states
         (AliasedDeviceReplayBuffer(..., dtype='bf16')) receives each state rounded once to nearest even (simq_local_state_images_slots_bf16).
+        pools: with `into`, the rings of all robot groups among the named mappers -- 1 to 16 distinct AliasedDeviceReplayBuffers of C
+        channels on the mapper's device, of any mix of dtype.  into[p] is then a handle of the ring of mapper p's group, in any
+        interleaving, and the states of all groups are written by the one state launch (simq_local_state_images_pools, also for one
+        listed ring): one chain and one status read-back per call however many groups there are.
 
         The distance images and the states are one launch each; the drawn maps one launch per room shape among the named mappers
         (simq_intention_maps draws maps of one shape).  Raises ValueError for a wrong robot count or `out`; SimqError, after the
@@ -889,7 +893,8 @@ class BatchedMapper:
         if into is not None:
             if out is not None:
                 raise ValueError('get_states: `into` and `out` name two destinations; pass one')
-            into, pool = local_maps.check_into(into, 'get_states', P, C)
+            into, pool = local_maps.check_into(into, 'get_states', P, C, pools)
+        local_maps.check_pools_argument('get_states', out, into, pools)
         if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == want and out.is_contiguous()):
             raise ValueError('out must be a contiguous float32 device tensor of shape %s, got %s' % (
                 want, '%s %s' % (out.dtype, tuple(out.shape)) if isinstance(out, torch.Tensor) else type(out).__name__))
@@ -937,8 +942,9 @@ class BatchedMapper:
             self._allocate()
         if out is not None and out.device != self.device:
             raise ValueError('out must be a contiguous float32 device tensor of shape %s on %s' % (want, self.device))
-        if pool is not None and pool.pool.device != self.device:
-            raise ValueError('get_states(into=): the pool lives on %s, the maps on %s' % (pool.pool.device, self.device))
+        for ring in local_maps.rings(pool) if pool is not None else ():
+            if ring.pool.device != self.device:
+                raise ValueError('get_states(into=): the pool lives on %s, the maps on %s' % (ring.pool.device, self.device))
 
         # ---- stage 1: the distance images, every source snapped through the closest cells on the device
         status, images = None, []
@@ -991,7 +997,7 @@ class BatchedMapper:
             channels.append(ch)
         stamps = {e: self._stamps(e, s) for e, s in states.items()}
         poses = [(states[e][r].position, states[e][r].heading) for e, r in own]
-        args, out, keep = local_maps._prepare(maps, channels, poses, [stamps[e] for e, _ in own], self.masks, out, None, into=into)
+        args, out, keep = local_maps._prepare(maps, channels, poses, [stamps[e] for e, _ in own], self.masks, out, None, into=into, pools=pools)
         if pool is None:
             lib.call('simq_local_state_images', *args)
         else:
@@ -1135,8 +1141,9 @@ class BatchedMapper:
         dev = self.device
         if out is not None and out.device != dev:
             raise ValueError('out must be a contiguous float32 device tensor of shape %s on %s' % (want, dev))
-        if pool is not None and pool.pool.device != dev:
-            raise ValueError('get_states(into=): the pool lives on %s, the maps on %s' % (pool.pool.device, dev))
+        for ring in local_maps.rings(pool) if pool is not None else ():
+            if ring.pool.device != dev:
+                raise ValueError('get_states(into=): the pool lives on %s, the maps on %s' % (ring.pool.device, dev))
         fixed = plan.on_device(self)
         c_maps = fixed['maps'].copy()
         buffers, as_ctypes = {}, local_maps.as_ctypes

@@ -3,7 +3,7 @@
     python tools/collect_rate.py [--reps 10] [--sizes 1,8,64,256] [--room 184x232]
 
 A collection step is what a worker that owns E environments does between two environment steps: `BatchedMapper.get_states` for the M
-deciding robots, `DQNPolicy.step_many` on their states, and the `push` of the M transitions that `TransitionTracker` completes.  Three
+deciding robots, `DQNPolicy.step_many` on their states, and the `push` of the M transitions that `TransitionTracker` completes.  Four
 forms of it run in one process, on the same commit, in alternating repetitions:
   host     get_states -> .cpu().numpy() -> the ndarrays through the tracker, step_many and push (every state crosses the bus twice:
            down after the mapper, up again at push -- and once more for the policy's batch)
@@ -12,6 +12,8 @@ forms of it run in one process, on the same commit, in alternating repetitions:
            group, because a call writes into one pool and every group has its ring.
   arrays   the handles form with the robots handed to get_states as a simq.RobotArrays instead of lists of
            RobotState; the arrays of a round exist before the clock starts, the RobotArrays is made from them inside it
+  pools    the handles form with ONE get_states(into=, pools=rings) per step over all deciding robots: handle p
+           comes from the ring of robot p's group, and the states of all groups are written by one chain of launches
 Workload: a recorded episode (tests/golden/mapper_*.npz), the full channel set with spatial intention channels (9 channels),
 environments of three robots in two robot groups replicated until M = 1, 8, 64, 256 robots decide.  `update` runs once before the
 clock; the maps do not change between the steps, the robots' poses follow the recorded rounds.  Per M and form:
@@ -40,7 +42,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import mapper_oracle as oracle  # noqa: E402
 
 
-FORMS = ('host', 'handles', 'arrays')
+FORMS = ('host', 'handles', 'arrays', 'pools')
 
 
 class Worker:
@@ -95,9 +97,17 @@ class Worker:
                 of_mapper.update(zip(mine, handles))
         return self.nested(of_mapper)
 
+    def states_pools(self, t):
+        rings = self.rings['pools']
+        group_of = [self.fx['groups'][m % 3] for m in self.deciding]
+        reserved = {g: iter(rings[i].reserve(group_of.count(g))) for i, g in enumerate(self.groups)}
+        handles = [next(reserved[g]) for g in group_of]
+        self.bm.get_states(self.robot_states(t), mappers=self.deciding, into=handles, pools=rings)
+        return self.nested(dict(zip(self.deciding, handles)))
+
     def step(self, form, t, eps=0.1):
         """get_states, step_many, push of the completed transitions; returns (states, actions)."""
-        states = self.states_host(t) if form == 'host' else self.states_handles(t, form)
+        states = self.states_host(t) if form == 'host' else self.states_pools(t) if form == 'pools' else self.states_handles(t, form)
         actions = self.policy.step_many(states, exploration_eps=eps)
         if self.trackers[form] is None:                               # the first step of an episode completes no transition
             self.trackers[form] = [self.simq.TransitionTracker(st) for st in states]
@@ -145,6 +155,7 @@ def main():
                 for a, b in zip((s for st in host_states for g in st for s in g), (s for st in pool_states for g in st for s in g)):
                     assert (a is None) == (b is None) and (a is None or np.array_equal(a.view(np.int32), np.asarray(b).view(np.int32))), (M, t, form)
         assert all([len(r) for r in w.rings['host']] == [len(r) for r in w.rings[form]] for form in FORMS) and sum(len(r) for r in w.rings['host']) == M
+        del host_states, pool_states                                  # (the handles of the form checked last would hold their slots to the end)
         times = {form: ([], []) for form in FORMS}
         for t in range(2, 4 + args.reps):                             # two warm-up steps, then `reps`; the forms alternate
             for form in FORMS:
