@@ -1180,6 +1180,31 @@ int64_t simq_intention_desc_bytes(int n_segments, int n);
 /* segments may be NULL when n_segments == 0. */
 int simq_intention_maps(const simq_intention_segment* segments, int n_segments, const simq_intention_problem* problems, int n, int rows,
                         int cols, int radius, void* d_desc, int64_t desc_bytes, float* d_out, int64_t out_floats, void* stream);
+/* ---- the same maps for problems of several room shapes and line thicknesses in one launch ------------------------------------------
+ * Problem p gives exactly the map simq_intention_maps gives for the same segments with rows = rows_p, cols = cols_p and
+ * radius = radius_p, written row-major at d_out[out_offset_p .. out_offset_p + rows_p * cols_p): every pixel of every problem is
+ * written, no other float of d_out is touched (the maps may lie in any order, with gaps).  One launch for all problems: its grid is
+ * the sum of the problems' counts of 32 x 256 tiles, and the workgroups find their problem by a binary search over the prefix of those
+ * counts.  d_desc (at least simq_intention_shapes_desc_bytes(...) bytes of device scratch, 8-byte aligned) receives the segments, the
+ * problems and that prefix -- int32 [n + 1], the last entry the grid size, padded to a multiple of 8 bytes -- in this order.
+ * Two problems may name one segment range; the segments then have to fit the maps of both.  The launch log names it
+ * "intention_maps_shapes".
+ * Everything is validated on the host before anything is copied or launched: n in 1 .. 2^20, n_segments in 0 .. 2^24; per problem
+ * rows, cols >= 1, rows * cols < 2^28, radius in [0, SIMQ_INTENTION_MAX_RADIUS], its segment range inside the segment array, its
+ * floats inside d_out and disjoint from d_desc; every segment of a problem's range ends inside that problem's map; modes, flags, finite
+ * doubles and the stored-value rule as above; no two problems' floats overlap; at most 2^31 - 1 workgroups; d_desc 8-byte and d_out
+ * 4-byte aligned, d_desc large enough. */
+typedef struct simq_intention_shaped_problem {
+    int64_t out_offset;             /* the first float of the map in d_out */
+    int32_t rows, cols;             /* the map's shape */
+    int32_t seg_begin, seg_count;   /* the map's segments: segments[seg_begin .. seg_begin + seg_count); none: a map of zeros */
+    int32_t radius;                 /* intention_map_line_thickness - 1 */
+    int32_t reserved_;
+} simq_intention_shaped_problem;
+int64_t simq_intention_shapes_desc_bytes(int n_segments, int n);
+/* segments may be NULL when n_segments == 0. */
+int simq_intention_maps_shapes(const simq_intention_segment* segments, int n_segments, const simq_intention_shaped_problem* problems, int n,
+                               void* d_desc, int64_t desc_bytes, float* d_out, int64_t out_floats, void* stream);
 
 /* ---- occupancy maps: configuration space, thin configuration space and closest free cells (OccupancyMap.update, envs.py:2452-2455,
  * read through OccupancyMap._closest_valid_cspace_indices, envs.py:2522-2523) ------------------------------------------------------
@@ -1379,7 +1404,7 @@ int simq_profile_stop(double* out, int max_kinds);
  * tile), "igemm_bf16_c64", "igemm_bf16_pp", "igemm_bf16_dma", "igemm_bf16_reg", "wgrad_bf16_img", "wgrad_bf16_pp", "wgrad_bf16_reg",
  * "stem_conv_bf16", "stem_wgrad_bf16", "stem_conv_bf16_wide[_x16]", "stem_wgrad_bf16_wide[_x16]", "bn_apply16", "bn_bwd_apply16[_mask_from_y]", "gemm_f32_batched", "igemm_f32", "conv_img_f32",
  * "stem_conv_f32", "winograd_f2" / "winograd_f4" [_wgrad], "wgrad_f32" [_batched], "local_state" [_bf16], "local_state_slots" [_bf16],
- * "local_state_pools" ... (csrc: note_launch).  simq_launch_count: launches
+ * "local_state_pools", "intention_maps", "intention_maps_shapes" ... (csrc: note_launch).  simq_launch_count: launches
  * of one family since the last reset (0 for a name that never ran); simq_launch_counts: "name=count;..." of every family that ran.
  * The parity tests use it to assert that the kernels a batch size is meant to select DID run. */
 int simq_launch_counts_reset(void);

@@ -102,6 +102,12 @@ class LocalDest(ctypes.Structure):
     _fields_ = [('slot', c_int64), ('pool', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
 
 
+class IntentionShapedProblem(ctypes.Structure):
+    """simq_intention_shaped_problem of include/simq.h (one map of simq_intention_maps_shapes: its place, shape, segments and radius)."""
+    _fields_ = [('out_offset', c_int64), ('rows', ctypes.c_int32), ('cols', ctypes.c_int32), ('seg_begin', ctypes.c_int32),
+                ('seg_count', ctypes.c_int32), ('radius', ctypes.c_int32), ('reserved_', ctypes.c_int32)]
+
+
 _SIGS = {
     'simq_version': (c_int, []),
     'simq_build_flags': (c_int, []),
@@ -243,6 +249,8 @@ _SIGS = {
                                               c_void_p, c_void_p, c_int64, c_void_p]),
     'simq_intention_desc_bytes': (c_int64, [c_int, c_int]),
     'simq_intention_maps': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    'simq_intention_shapes_desc_bytes': (c_int64, [c_int, c_int]),
+    'simq_intention_maps_shapes': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'simq_occupancy_maps': (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                     c_void_p]),
     'simq_occupancy_maps_large_work_bytes': (c_int64, [c_int, c_int]),

@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from . import _batch
-from ._lib import lib, ptr, stream_ptr
-from .local_maps import distances, pixel_indices_many, position_to_pixel_indices
+from ._lib import IntentionShapedProblem as ShapedProblem, lib, ptr, stream_ptr
+from .local_maps import as_ctypes, distances, pixel_indices_many, position_to_pixel_indices
 
 ENCODINGS = ('circle', 'ramp', 'binary', 'line', 'history')
 STORE, RAMP = 0, 1
@@ -95,6 +95,7 @@ def segments(robots, map_shape, encoding, scale=1.0):
 
 
 SEGMENT, PROBLEM = np.dtype(Segment), np.dtype(Problem)      # the descriptor tables as numpy structured arrays (local_maps.as_ctypes)
+SHAPED_PROBLEM = np.dtype(ShapedProblem)                     # simq_intention_shaped_problem: a problem with its own place, shape and radius
 
 
 def _starts(counts):
@@ -180,11 +181,107 @@ def intention_maps(paths, map_shape, encoding, scale=1.0, line_thickness=2, out=
     pixel is written.
 
     A row of the result is a global map for simq.local_state_images: local_state_images(maps, [('map', k), ...], poses).
+
+    Several room shapes or line thicknesses in the one launch (simq_intention_maps_shapes): map_shape may be a list of P (rows, cols)
+    pairs and line_thickness a list of P whole numbers.  With a list of shapes the result is a list of P device views [rows_p, cols_p]
+    of one flat float32 tensor, packed in problem order (each is a global map for simq.local_state_images as it is), and `out` a
+    contiguous flat float32 device tensor of at least the sum of the cells; with one shape and a list of thicknesses the result and
+    `out` are the [P, rows, cols] tensor.
     Raises SimqError, launching nothing, for what the library refuses."""
+    if _is_list(line_thickness) or _shape_list(map_shape):
+        args, out, keep = _prepare_shapes(paths, map_shape, encoding, scale, line_thickness, out)
+        lib.call('simq_intention_maps_shapes', *args)
+        del keep
+        return out
     args, out, keep = _prepare(paths, map_shape, encoding, scale, line_thickness, out)
     lib.call('simq_intention_maps', *args)
     del keep                                     # (the descriptor scratch: alive until the launch is queued)
     return out
+
+
+def _is_list(x):
+    return isinstance(x, (list, tuple, np.ndarray))
+
+
+def _shape_list(map_shape):
+    """map_shape is a list of (rows, cols) pairs and not one pair."""
+    return _is_list(map_shape) and len(map_shape) > 0 and _is_list(map_shape[0])
+
+
+def _shape(map_shape):
+    """(rows, cols) of one map_shape argument as two ints."""
+    try:
+        rows, cols = int(map_shape[0]), int(map_shape[1])
+    except (TypeError, IndexError, ValueError):
+        raise ValueError('map_shape is (rows, cols), got %r' % (map_shape,)) from None
+    if rows < 1 or cols < 1 or len(map_shape) != 2:
+        raise ValueError('map_shape is (rows, cols) with rows, cols >= 1, got %r' % (map_shape,))
+    return rows, cols
+
+
+def _prepare_shapes(paths, map_shape, encoding, scale, line_thickness, out):
+    """_prepare for problems with their own shapes or thicknesses: the argument tuple of simq_intention_maps_shapes, what
+    intention_maps returns (the views of a flat tensor for a list of shapes, the [P, rows, cols] tensor for one shape) and the device
+    tensors the call reads."""
+    paths = list(paths)
+    P = len(paths)
+    if P < 1:
+        raise ValueError('intention_maps needs at least one problem')
+    several = _shape_list(map_shape)
+    shapes = [_shape(s) for s in map_shape] if several else [_shape(map_shape)] * P
+    if len(shapes) != P:
+        raise ValueError('%d map shapes for %d problems' % (len(shapes), P))
+    thicknesses = list(line_thickness) if _is_list(line_thickness) else [line_thickness] * P
+    if len(thicknesses) != P:
+        raise ValueError('%d line thicknesses for %d problems' % (len(thicknesses), P))
+    encodings = [encoding] * P if isinstance(encoding, str) else list(encoding)
+    if len(encodings) != P:
+        raise ValueError('%d encodings for %d problems' % (len(encodings), P))
+    for thickness in thicknesses:
+        check_drawing(scale, thickness)
+
+    tables, counts = [], np.zeros(P, np.int64)
+    for p in range(P):
+        rows = segments(paths[p], shapes[p], encodings[p], scale)
+        table = np.zeros(len(rows), SEGMENT)
+        for k, (r0, c0, r1, c1, mode, drop_last, v, start, stop, step) in enumerate(rows):
+            table[k] = (start, stop, step, r0, c0, r1, c1, mode, drop_last, v, 0)
+        tables.append(table)
+        counts[p] = len(rows)
+    c_segs = np.concatenate([t.view(np.uint8) for t in tables]).view(SEGMENT)
+    cells = np.asarray([r * c for r, c in shapes], np.int64)
+    c_probs = shaped_problems(shapes, _starts(cells), _starts(counts), counts, np.asarray(thicknesses, np.int64) - 1)
+    total = int(cells.sum())
+    if several:
+        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.dim() == 1 and out.is_contiguous()
+                                    and out.numel() >= total):
+            raise ValueError('out must be a contiguous flat float32 tensor of at least %d elements for maps of several shapes, got %s' % (
+                total, '%s %s' % (out.dtype, tuple(out.shape)) if isinstance(out, torch.Tensor) else type(out).__name__))
+    dev = _batch.device('intention maps')       # (after the argument checks: those need no device)
+    want = (total,) if several else (P,) + shapes[0]
+    if out is None:
+        out = torch.empty(want, dtype=torch.float32, device=dev)
+    elif not _batch.out_fits(out, torch.float32, dev, None if several else want, total):
+        raise ValueError('out must be a contiguous float32 tensor of %s on %s' % ('at least %d elements' % total if several else 'shape %s' % (want,), dev))
+    args, d_desc = shapes_call(c_segs, c_probs, out, dev)
+    return args, (_batch.views(out[:total], shapes) if several else out), (d_desc, c_segs, c_probs)
+
+
+def shaped_problems(shapes, out_offset, seg_begin, seg_count, radius):
+    """The SHAPED_PROBLEM table of len(shapes) problems from arrays of its fields (radius: one int or an array)."""
+    table = np.zeros(len(shapes), SHAPED_PROBLEM)
+    shapes = np.asarray(shapes, np.int64).reshape(-1, 2)
+    table['rows'], table['cols'], table['out_offset'] = shapes[:, 0], shapes[:, 1], out_offset
+    table['seg_begin'], table['seg_count'], table['radius'] = seg_begin, seg_count, radius
+    return table
+
+
+def shapes_call(c_segs, c_probs, out, dev):
+    """The argument tuple of simq_intention_maps_shapes for a SEGMENT and a SHAPED_PROBLEM table and the tensor the maps go to, and
+    the descriptor scratch of the call (to keep until the launch is queued).  The tables are read during the call only."""
+    d_desc = torch.empty(max(int(lib.c.simq_intention_shapes_desc_bytes(len(c_segs), len(c_probs))), 8), dtype=torch.uint8, device=dev)
+    return (as_ctypes(c_segs, Segment) if len(c_segs) else None, len(c_segs), as_ctypes(c_probs, ShapedProblem), len(c_probs), ptr(d_desc),
+            ctypes.c_int64(d_desc.numel()), ptr(out), ctypes.c_int64(out.numel()), stream_ptr(dev)), d_desc
 
 
 def _prepare(paths, map_shape, encoding, scale, line_thickness, out):

@@ -273,23 +273,37 @@ class _Plan:
         self.jobs = []
         if slots['history'] is None and slots['intention'] is None and not self.spatial:
             return
-        for shape in sorted(set(bm.shapes[m] for m in self.ms.tolist())):
-            sel = np.flatnonzero((self.rows == shape[0]) & (self.cols == shape[1]))
+        shapes = sorted(set(bm.shapes[m] for m in self.ms.tolist()))
+        if bm.one_drawing_launch and len(shapes) > 1:
+            # one job over every p: the buffer 'drawn' is flat, each problem with its shape and its offset (simq_intention_maps_shapes)
+            shapes = [None]
+        for shape in shapes:
+            sel = np.arange(self.P) if shape is None else np.flatnonzero((self.rows == shape[0]) & (self.cols == shape[1]))
             pairs = np.flatnonzero(np.isin(self.pair_p, sel))
             of_pair = np.searchsorted(sel, self.pair_p[pairs])
-            problem, maps, n = [], [], 0
+            buffer = 'drawn' if shape is None else shape
+            problem, maps, owner, n = [], [], [], 0
             for name in ('history', 'intention'):
                 if slots[name] is not None:
                     problem.append(n + of_pair)
                     maps.append(slots[name][sel])
-                    self.stage_keys.update({(name, int(p)): (shape, n + k) for k, p in enumerate(sel)})
+                    owner.append(sel)
+                    self.stage_keys.update({(name, int(p)): (buffer, n + k) for k, p in enumerate(sel)})
                     n += len(sel)
             if self.spatial:
                 problem.append(n + np.arange(len(sel) * nq))
                 maps.append(slots['channels'][sel].reshape(-1))
-                self.stage_keys.update({('channel', int(p), q): (shape, n + k * nq + q) for k, p in enumerate(sel) for q in range(nq)})
+                owner.append(np.repeat(sel, nq))
+                self.stage_keys.update({('channel', int(p), q): (buffer, n + k * nq + q) for k, p in enumerate(sel) for q in range(nq)})
                 n += len(sel) * nq
-            self.jobs.append((shape, {'p': sel, 'pairs': pairs, 'problem': np.concatenate(problem), 'n': n, 'maps': np.concatenate(maps)}))
+            job = {'p': sel, 'pairs': pairs, 'problem': np.concatenate(problem), 'n': n, 'maps': np.concatenate(maps)}
+            if shape is None:                                        # every problem's shape, and where its map begins in the flat tensor
+                owner = np.concatenate(owner)
+                job['shapes'] = np.stack([self.rows[owner], self.cols[owner]], axis=1).astype(np.int64)
+                cells = job['shapes'][:, 0] * job['shapes'][:, 1]
+                job['at'], job['cells'] = intention_drawing._starts(cells), int(cells.sum())
+                job['shape_list'] = [(int(r), int(c)) for r, c in job['shapes']]
+            self.jobs.append((shape, job))
 
     def _stage3(self, bm, slots):
         """Stage 3: the channels in get_state's order, with every field but the constants of the nonspatial encoding."""
@@ -464,17 +478,26 @@ class BatchedMapper:
     room-mask box has more than 20 000 cells with its halo by store_new_actions, both by the library.  With it the constructor decides
     per mapper, from the shapes and the room masks' boxes, which entry point each stage uses (`occupancy_entry`, `action_entry`: one
     name per mapper) and allocates the two workspaces once; update / flush and store_new_actions then make at most two launches per
-    stage, the mappers under the caps first, and a set of mappers on both sides of a cap works as one."""
+    stage, the mappers under the caps first, and a set of mappers on both sides of a cap works as one.
+
+    one_drawing_launch: without it get_states draws the history and intention maps with one simq_intention_maps launch per room shape
+    among the named mappers.  With it a call whose mappers have more than one room shape draws them all in one
+    simq_intention_maps_shapes launch, into one flat tensor, with one descriptor upload; a call whose mappers
+    share a shape makes the call it makes without it.  The states are the same either way."""
 
     def __init__(self, room_width, room_length, robot_types, robot_masks, group_indices=None, receptacle_position=None, *,
                  use_robot_map=True, use_distance_to_receptacle_map=False, use_shortest_path_to_receptacle_map=False,
                  use_shortest_path_map=False, use_history_map=False, use_intention_map=False, use_intention_channels=False,
                  intention_map_encoding='ramp', intention_map_scale=1.0, intention_map_line_thickness=2, intention_channel_encoding='spatial',
-                 intention_channel_nonspatial_scale=0.1, distance_to_receptacle_map_scale=0.25, shortest_path_map_scale=0.25, seg_values=None, large_rooms=False):
+                 intention_channel_nonspatial_scale=0.1, distance_to_receptacle_map_scale=0.25, shortest_path_map_scale=0.25, seg_values=None, large_rooms=False,
+                 one_drawing_launch=False):
         given = locals()
         if not isinstance(large_rooms, bool):
             raise ValueError('large_rooms must be True or False, got %r' % (large_rooms,))
         self.large_rooms = large_rooms
+        if not isinstance(one_drawing_launch, bool):
+            raise ValueError('one_drawing_launch must be True or False, got %r' % (one_drawing_launch,))
+        self.one_drawing_launch = one_drawing_launch
         self.flags = {f: bool(given[f]) for f in FLAGS}
         try:
             self.robot_types = [[str(t) for t in env] for env in robot_types]
@@ -881,7 +904,8 @@ class BatchedMapper:
         listed ring): one chain and one status read-back per call however many groups there are.
 
         The distance images and the states are one launch each; the drawn maps one launch per room shape among the named mappers
-        (simq_intention_maps draws maps of one shape).  Raises ValueError for a wrong robot count or `out`; SimqError, after the
+        (simq_intention_maps draws maps of one shape) or, for an object made with one_drawing_launch=True, one launch whatever the
+        shapes (simq_intention_maps_shapes).  Raises ValueError for a wrong robot count or `out`; SimqError, after the
         whole chain has run, naming the mappers whose distance images could not be computed (no successful update yet, a
         configuration space without a free cell): their distance channels come from images of zeros, every other mapper's state is
         right."""
@@ -957,8 +981,17 @@ class BatchedMapper:
             images = list(images) if uniform else _batch.views(images.view(-1), shapes)
 
         # ---- stage 2: history maps, intention maps and the maps behind the spatial intention channels: one launch per room shape
+        # (one_drawing_launch: one simq_intention_maps_shapes launch for all of them, `drawn` views of its flat tensor)
         drawn = {}
-        for shape in sorted(set(self.shapes[ms[p]] for _, p, _, _ in jobs)):
+        drawn_shapes = sorted(set(self.shapes[ms[p]] for _, p, _, _ in jobs))
+        if self.one_drawing_launch and len(drawn_shapes) > 1:
+            args, maps, keep = intention_drawing._prepare_shapes([j[2] for j in jobs], [self.shapes[ms[j[1]]] for j in jobs], [j[3] for j in jobs],
+                                                                 self.intention_map_scale, self.intention_map_line_thickness, None)
+            lib.call('simq_intention_maps_shapes', *args)
+            del keep
+            drawn.update({j[0]: maps[k] for k, j in enumerate(jobs)})
+            drawn_shapes = []
+        for shape in drawn_shapes:
             mine = [j for j in jobs if self.shapes[ms[j[1]]] == shape]
             args, maps, keep = intention_drawing._prepare([j[2] for j in mine], shape, [j[3] for j in mine], self.intention_map_scale,
                                                           self.intention_map_line_thickness, None)
@@ -1116,9 +1149,14 @@ class BatchedMapper:
                 first = np.concatenate([begin[e][m] for e, m in who])
                 n = np.concatenate([count[e][m] for e, m in who])
                 c_segs = tables[intention_drawing.ragged(first, n)]
-                c_probs = np.zeros(sel['n'], intention_drawing.PROBLEM)
-                c_probs['seg_count'] = np.bincount(sel['problem'], weights=n, minlength=sel['n'])
-                c_probs['seg_begin'] = intention_drawing._starts(c_probs['seg_count'])
+                seg_count = np.bincount(sel['problem'], weights=n, minlength=sel['n']).astype(np.int64)
+                if shape is None:                                    # all room shapes in one call: every problem with its own
+                    c_probs = intention_drawing.shaped_problems(sel['shapes'], sel['at'], intention_drawing._starts(seg_count), seg_count,
+                                                                self.intention_map_line_thickness - 1)
+                else:
+                    c_probs = np.zeros(sel['n'], intention_drawing.PROBLEM)
+                    c_probs['seg_count'] = seg_count
+                    c_probs['seg_begin'] = intention_drawing._starts(c_probs['seg_count'])
                 launches.append((shape, c_segs, c_probs))
 
         # stage 3: the robots as they are stamped, the problems, the channel values of this call
@@ -1162,8 +1200,15 @@ class BatchedMapper:
             c_maps['d_data'][plan.image_maps] = images.data_ptr() + 4 * plan.image_at
             buffers['image'] = (images.view(-1), plan.image_at.tolist(), plan.image_shapes)
 
-        # ---- stage 2: one launch per room shape
+        # ---- stage 2: one launch per room shape, or (one_drawing_launch) one for all of them
         for (shape, c_segs, c_probs), (_, sel) in zip(launches, plan.jobs):
+            if shape is None:
+                flat = torch.empty(sel['cells'], dtype=torch.float32, device=dev)
+                args, d_desc = intention_drawing.shapes_call(c_segs, c_probs, flat, dev)
+                lib.call('simq_intention_maps_shapes', *args)
+                c_maps['d_data'][sel['maps']] = flat.data_ptr() + 4 * sel['at']
+                buffers['drawn'] = (flat, sel['at'].tolist(), sel['shape_list'])
+                continue
             maps = torch.empty((len(c_probs),) + shape, dtype=torch.float32, device=dev)
             d_desc = torch.empty(max(int(lib.c.simq_intention_desc_bytes(len(c_segs), len(c_probs))), 8), dtype=torch.uint8, device=dev)
             lib.call('simq_intention_maps', as_ctypes(c_segs, intention_drawing.Segment) if len(c_segs) else None, len(c_segs),

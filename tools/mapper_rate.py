@@ -1,6 +1,6 @@
 """Rate of simq.BatchedMapper on the GPU, beside the same work through the hand-written chain of the public functions: one JSON line.
 
-    python tools/mapper_rate.py [--reps 10] [--sizes 1,8,64,256] [--reference-ms-per-state MS] [--profile]
+    python tools/mapper_rate.py [--reps 10] [--sizes 1,8,64,256] [--rooms small|large|both] [--reference-ms-per-state MS] [--profile]
 
 Workload: the two recorded episodes (tests/golden/mapper_*.npz, rooms 184 x 232 and 232 x 232), the full channel set with spatial
 intention channels (9 channels), environments of three robots replicated until M = 1, 8, 64, 256 mappers are named; every repetition is
@@ -24,6 +24,7 @@ form and of one in the array form (room 184 x 232, after two warm-up calls; cPro
 checked against the golden (M <= 3) before anything is timed.  The reference Mapper's host time per state is what
 tools/gen_mapper_golden.py prints (it needs the reference checkout); --reference-ms-per-state repeats that figure in the line
 (`reference_host_ms_per_state`, null when not given): it is not measured here.
+--rooms small / large times one room alone; --rooms both the two rooms in one object (both_rooms below).
 """
 import argparse
 import cProfile
@@ -74,10 +75,91 @@ class LibraryClock:
         return ms, n
 
 
+def both_rooms(args, simq, _lib):
+    """--rooms both: the two recorded episodes in one object, environments of the two rooms alternating, M = 3 * E mappers (E even).
+    Per M four ways of the same step alternate in one process: the list form and the array form, each on an object that draws the maps
+    of the two room shapes with one simq_intention_maps launch per shape (`per_shape`, the default) and on one made with
+    one_drawing_launch=True (`one_launch`: one simq_intention_maps_shapes launch).  The fields are main()'s; host_ms_all lists the
+    host_ms of every repetition."""
+    from simq.observation import CameraGeometry, IdRanges
+    cfg = oracle.configurations()['full_spatial']
+    flags = {f: cfg[f] for f in oracle.FLAGS}
+    rest = {k: v for k, v in cfg.items() if k not in oracle.FLAGS}
+    fxs = [oracle.load_fixture(os.path.join(ROOT, 'tests', 'golden', f)) for f in ('mapper_184x232.npz', 'mapper_232x232.npz')]
+    masks = {name: fxs[0]['masks'][k] for k, name in enumerate(fxs[0]['mask_names'])}
+    n_rounds = len(fxs[0]['rounds'])
+    result = {'tool': 'mapper_rate', 'rooms': 'both', 'device': torch.cuda.get_device_name(0), 'channels': len(oracle.channel_names(cfg, 3)),
+              'reps': args.reps, 'rows': {}}
+    for M in [int(x) for x in args.sizes.split(',')]:
+        E = max(2, 2 * ((M + 5) // 6))
+        M = 3 * E
+        ms = list(range(M))
+        of = [fxs[e % 2] for e in range(E)]
+        objects = {name: simq.BatchedMapper([f['room_width'] for f in of], [f['room_length'] for f in of], [f['types'] for f in of], masks,
+                                            [f['groups'] for f in of], [f['receptacle_position'] for f in of], **flags, **rest,
+                                            one_drawing_launch=flag) for name, flag in (('per_shape', False), ('one_launch', True))}
+
+        def step_inputs(t):
+            rnds = [f['rounds'][t % n_rounds] for f in of]
+            f = [rnds[m // 3]['frames'][m % 3] for m in ms]
+            frames = ([x['depth'] for x in f], [x['ids'] for x in f], [CameraGeometry(*x['geometry']) for x in f], [IdRanges(*x['ranges']) for x in f])
+            states = [[simq.RobotState(r['position'], r['heading'], r['type'], r['lift_state'], r['idle'], r['target'], r['intention_path'],
+                                       r['history_path']) for r in rnd['robots']] for rnd in rnds]
+            return frames, states
+
+        arrays = {}
+        for t in range(n_rounds):
+            ra = simq.RobotArrays.from_states(objects['per_shape'], step_inputs(t)[1])
+            arrays[t] = (ra.position, ra.heading, ra.lifting, ra.idle, ra.target, ra.intention_path, ra.history_path)
+        split = []
+
+        def step(bm, as_arrays):
+            def run(t):
+                frames, states = step_inputs(t)
+                bm.update(*frames, mappers=ms)
+                split.append(time.perf_counter())
+                return bm.get_states(simq.RobotArrays(*arrays[t % n_rounds]) if as_arrays else states, mappers=ms)
+            return run
+        forms = [('%s_%s' % (form, name), step(bm, form == 'arrays')) for form in ('object', 'arrays') for name, bm in objects.items()]
+        first = [run(0) for _, run in forms]
+        want = np.stack([oracle.expected_state(cfg, of[m // 3]['rounds'][0]['images'], m % 3, 3) for m in ms])
+        for got in first:
+            assert np.array_equal(got.cpu().numpy().view(np.int32), want.view(np.int32)), M
+        taken = {name: ([], [], [], []) for name, _ in forms}
+        with LibraryClock(_lib.lib) as clock:
+            for t in range(1, 3 + args.reps):
+                for name, run in forms:                              # the forms alternate step by step
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    run(t)
+                    torch.cuda.synchronize()
+                    dt = 1e3 * (time.perf_counter() - t0)
+                    ms_lib, launches = clock.take()
+                    if t >= 3:
+                        host, library, update, counts = taken[name]
+                        host.append(dt)
+                        library.append(ms_lib)
+                        update.append(1e3 * (split[-1] - t0))
+                        counts.append(launches)
+        row = {}
+        for name, (host, library, update, counts) in taken.items():
+            states = np.asarray(host) - np.asarray(update)
+            row[name] = {'host_ms': round(float(np.median(host)), 3), 'host_ms_min': round(min(host), 3), 'host_ms_max': round(max(host), 3),
+                         'states_host_ms': round(float(np.median(states)), 3), 'states_host_ms_min': round(float(states.min()), 3),
+                         'states_host_ms_max': round(float(states.max()), 3), 'library_ms': round(float(np.median(library)), 3),
+                         'library_ms_min': round(min(library), 3), 'library_ms_max': round(max(library), 3), 'launches': counts[-1],
+                         'host_ms_all': [round(x, 3) for x in host]}
+        result['rows'][str(M)] = row
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
-    ap.add_argument('--sizes', default='1,8,64,256')
+    ap.add_argument('--sizes', default=None, help='the numbers of mappers (default 1,8,64,256; with --rooms both 6,48,192)')
+    ap.add_argument('--rooms', choices=('small', 'large', 'both'), default=None,
+                    help='small / large: the 184 x 232 / 232 x 232 room alone; both: the two rooms in one object, its drawn maps with one launch '
+                         'per room shape and with one launch for both (one_drawing_launch); omitted: each room on its own, one after the other')
     ap.add_argument('--reference-ms-per-state', type=float, default=None,
                     help='the host time per state tools/gen_mapper_golden.py printed for the reference Mapper, repeated in the line')
     ap.add_argument('--profile', action='store_true', help='print a cProfile breakdown of one get_states per form and M instead of the timings')
@@ -87,12 +169,18 @@ def main():
     import simq
     from simq import _lib
     from simq.observation import CameraGeometry, IdRanges
+    if args.sizes is None:
+        args.sizes = '6,48,192' if args.rooms == 'both' else '1,8,64,256'
+    if args.rooms == 'both':
+        if args.profile:
+            raise SystemExit('--profile is for one room at a time')
+        return both_rooms(args, simq, _lib)
     cfg = oracle.configurations()['full_spatial']
     flags = {f: cfg[f] for f in oracle.FLAGS}
     rest = {k: v for k, v in cfg.items() if k not in oracle.FLAGS}
     result = {'tool': 'mapper_rate', 'device': torch.cuda.get_device_name(0), 'channels': len(oracle.channel_names(cfg, 3)), 'reps': args.reps,
               'reference_host_ms_per_state': args.reference_ms_per_state, 'rooms': {}}
-    for fname in ('mapper_184x232.npz', 'mapper_232x232.npz'):
+    for fname in {'small': ('mapper_184x232.npz',), 'large': ('mapper_232x232.npz',)}.get(args.rooms, ('mapper_184x232.npz', 'mapper_232x232.npz')):
         fx = oracle.load_fixture(os.path.join(ROOT, 'tests', 'golden', fname))
         masks = {name: fx['masks'][k] for k, name in enumerate(fx['mask_names'])}
         rounds = fx['rounds']
